@@ -13,8 +13,11 @@ ffn_down by input columns with an all-reduce (RCCL over xGMI) of the partial res
 output.weight by vocabulary rows with an all-gather of the logits.  The total work is fixed, so
 scaling is "strong".
 
-Prints ONE JSON line (rank 0).  `roofline` is the dominant kernel (the decode Q4_K GEMV) measured
-live with HIP events; `cpu_baseline` is the CPU restatement (oracle, kind "port") on the host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and reports `value` and
+`ms_per_step`; `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.  `--full` adds
+every other measurement: the phase split, `roofline` (the dominant kernel, the decode Q4_K GEMV, measured live
+with HIP events), `roofline_prefill_gemm`, `small_batch`, `config3` / `config4` and `cpu_baseline` (the CPU
+restatement, oracle kind "port", on the host cores).
 """
 from __future__ import annotations
 
@@ -45,6 +48,11 @@ def parse():
     p.add_argument("--prefill", type=int, default=512)
     p.add_argument("--decode", type=int, default=128)
     p.add_argument("--no-graph", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline figure, run every other leg: phase split, exact and staged prefill, rooflines, small "
+                        "batches, config 3 / config 4 and the CPU baseline (a plain run times the steps only)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the output buffers of the last timed step as DIR/<pass>.<mat-mul>.npy (float32; rank 0)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--force-dist", action="store_true",
                    help="rehearsal: initialise the process group and issue the collectives even at world size 1")
@@ -53,7 +61,7 @@ def parse():
                    help="build the op list from a GGUF model file (tensor types and shapes as stored) and run on ITS weights, "
                         "uploaded straight from the read-only mapping, instead of --model's synthetic inventory")
     p.add_argument("--no-extra-configs", action="store_true",
-                   help="skip the BASELINE config 3 (Llama-3-8B Q8_0) and config 4 (Mixtral-8x7B expert path) legs of the line")
+                   help="with --full: skip the BASELINE config 3 (Llama-3-8B Q8_0) and config 4 (Mixtral-8x7B expert path) legs")
     return p.parse_args()
 
 
@@ -248,6 +256,47 @@ def staged_prefill(runner, n):
             if rc:
                 _hip.check(rc, "mul_mat_multi_types (staged pass)")
     return run, counts
+
+
+DUMP_BYTES = 60 << 20  # all files of --dump-outputs together (float32 samples + .npy headers stay under 64 MB)
+DUMP_MAX_ELEMS = 1 << 20  # per file; a larger output is sampled
+
+
+def dump_sample_index(name, numel, cap):
+    """Sorted flat indices of the fixed sample of an output of `numel` elements: all of them up to `cap`, else `cap` drawn
+    without replacement by a generator seeded from the file name (the same indices in every run and every build)."""
+    import zlib
+
+    import numpy as np
+    if numel <= cap:
+        return None
+    rng = np.random.default_rng(0x0D5EED + zlib.crc32(name.encode()))
+    return np.sort(rng.choice(numel, size=cap, replace=False))
+
+
+def dump_outputs(runner, path):
+    """--dump-outputs: the output buffers of the prefill pass and of the decode pass as the last timed step left them, float32.
+    A pass reuses one buffer per (rows, position in the fused call), so each file holds the last mat-mul of the pass that wrote
+    that buffer and is named after it: DIR/prefill.blk.31.ffn_down.npy, DIR/decode.output.npy, ...  Buffers larger than the
+    per-file share of DUMP_BYTES are a seeded sample of their flattened elements (dump_sample_index).  Returns the file names."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    last = {}  # buffer -> (file name, tensor), in the order of the calls of each pass
+    for n in sorted(runner.buf, reverse=True):
+        phase = "decode" if n == 1 else "prefill"
+        for _, g, _, outs, *_ in runner.buf[n]["calls"]:
+            for o, out in zip(g, outs):
+                last[out.data_ptr()] = (f"{phase}.{o.spec.name}".replace(os.sep, "_"), out)
+    cap = min(DUMP_MAX_ELEMS, DUMP_BYTES // 4 // max(len(last), 1))
+    torch.cuda.synchronize()
+    names = []
+    for name, out in last.values():
+        idx = dump_sample_index(name, out.numel(), cap)
+        if idx is not None:  # (a sample is one-dimensional; a whole buffer keeps its [n, rows] shape)
+            out = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+        np.save(os.path.join(path, name + ".npy"), out.float().cpu().numpy())
+        names.append(name)
+    return names
 
 
 def cpu_share():
@@ -679,6 +728,8 @@ def run():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed * 1000.0 / a.steps
+    if a.dump_outputs and rank == 0:  # before anything else runs a pass: the buffers still hold the last timed step
+        dump_outputs(runner, a.dump_outputs)
 
     # ---- the collectives of the timed region are verified AFTER it: no peer was lost (lfamd_comm_check) and one more
     # known-answer all-reduce is right on every rank; a line measured over void sums is marked invalid and the run fails
@@ -698,7 +749,7 @@ def run():
             print("bench.py: " + comm_invalid, file=sys.stderr)
         # what the residual-stream exchange of one decode pass costs: its 2 x n_layers all-reduces back to back
         n_ar = sum(1 for ops in runner.layers for o in ops if o.spec.shard == "cols")
-        if n_ar:
+        if n_ar and a.full:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             buf = torch.zeros(next(o.m for ops in runner.layers for o in ops if o.spec.shard == "cols"), device=dev)
             barrier()
@@ -708,6 +759,48 @@ def run():
             e1.record()
             torch.cuda.synchronize()
             allreduce_us = round(e0.elapsed_time(e1) * 1e3, 1)
+
+    def headline():
+        """The keys of the line that the timed steps alone determine."""
+        tokens = a.prefill + a.decode
+        out = {
+            "metric": "prefill + decode tokens/sec, Llama-3-8B Q4_K_M, 1/2/4/8 MI355X vs CPU tinyBLAS",
+            "value": round(tokens / (ms_per_step / 1000.0), 2),
+            "unit": "tokens/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "int8",
+            "data": "synthetic" if not a.gguf else f"weights of {os.path.basename(a.gguf)} (GGUF v{gguf_file.version}, {len(gguf_tensors)} mat-mul tensors), synthetic activations",
+            "config": {
+                "workload": f"{a.model} mat-muls ({sum(len(l) for l in layers)} GGML_OP_MUL_MAT per pass, f32 activations in, quantisation fused, sibling ops fused at decode" + "), "
+                            f"{a.prefill}-token prefill + {a.decode} decode, matmul-only",
+                "numerics": "decode: exact int8 x int4/int6 block dot products with f32 scales (v_dot4_i32_i8); prefill: Q4_K on grids of up "
+                            "to 256 tiles of 128x128 (attn_q and its Q4_K siblings, attn_output, ffn_down) on the int8 matrix cores, exact integer sub-block dots "
+                            "(2e-6 of the oracle); larger Q4_K grids and Q6_K on f16 MFMA with scaled operands f16(d*sc*q) x f16(d8*code) "
+                            "(<= 1e-3 relative, measured ~3e-4; exact integer codes with LFAMD_FLAG_PRECISE)",
+                "model": a.model, "prefill_tokens": a.prefill, "decode_tokens": a.decode,
+                "parallelism": "single GPU" if world == 1 else f"tp{world} (all-reduce on attn_output/ffn_down: {comm.describe() if comm is not None else 'torch.distributed ' + os.environ.get('LFAMD_DIST_BACKEND', 'nccl')})",
+                "hip_graph": use_graph, "weight_bytes_per_gpu": runner.weight_bytes(),
+                "decode_launches_per_pass": sum(1 for _ in runner.buf[1]["calls"]),
+            },
+        }
+        if comm_invalid:
+            out["invalid"] = comm_invalid
+        return out
+
+    if not a.full:  # a plain run: the headline figure only
+        out = None
+        if rank == 0:
+            out = headline()
+            out["cpu_baseline"] = None
+        if dist_on:
+            torch.distributed.destroy_process_group()
+        return json.dumps(out) if out is not None else None
 
     # ---- phase split (informational): prefill pass and decode pass timed apart with events
     def time_region(fn, reps):
@@ -892,45 +985,19 @@ def run():
             torch.distributed.destroy_process_group()
         return None
 
-    tokens = a.prefill + a.decode
-    out = {
-        "metric": "prefill + decode tokens/sec, Llama-3-8B Q4_K_M, 1/2/4/8 MI355X vs CPU tinyBLAS",
-        "value": round(tokens / (ms_per_step / 1000.0), 2),
-        "unit": "tokens/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "int8",
-        "data": "synthetic" if not a.gguf else f"weights of {os.path.basename(a.gguf)} (GGUF v{gguf_file.version}, {len(gguf_tensors)} mat-mul tensors), synthetic activations",
-        "config": {
-            "workload": f"{a.model} mat-muls ({sum(len(l) for l in layers)} GGML_OP_MUL_MAT per pass, f32 activations in, quantisation fused, sibling ops fused at decode" + "), "
-                        f"{a.prefill}-token prefill + {a.decode} decode, matmul-only",
-            "numerics": "decode: exact int8 x int4/int6 block dot products with f32 scales (v_dot4_i32_i8); prefill: Q4_K on grids of up "
-                        "to 256 tiles of 128x128 (attn_q and its Q4_K siblings, attn_output, ffn_down) on the int8 matrix cores, exact integer sub-block dots "
-                        "(2e-6 of the oracle); larger Q4_K grids and Q6_K on f16 MFMA with scaled operands f16(d*sc*q) x f16(d8*code) "
-                        "(<= 1e-3 relative, measured ~3e-4; exact integer codes with LFAMD_FLAG_PRECISE)",
-            "model": a.model, "prefill_tokens": a.prefill, "decode_tokens": a.decode,
-            "parallelism": "single GPU" if world == 1 else f"tp{world} (all-reduce on attn_output/ffn_down: {comm.describe() if comm is not None else 'torch.distributed ' + os.environ.get('LFAMD_DIST_BACKEND', 'nccl')})",
-            "hip_graph": use_graph, "weight_bytes_per_gpu": runner.weight_bytes(),
-            "prefill_tokens_per_s": round(a.prefill / (pf_us * 1e-6), 1),
-            "decode_tokens_per_s": round(1.0 / (dc_us * 1e-6), 1),
-            "prefill_pass_ms": round(pf_us / 1e3, 3), "decode_pass_ms": round(dc_us / 1e3, 4),
-            "prefill_exact": {"flags": "LFAMD_FLAG_PRECISE", "pass_ms": round(pfx_us / 1e3, 3),
-                              "tokens_per_s": round(a.prefill / (pfx_us * 1e-6), 1), "numerics": "2e-6 of the oracle"},
-            **({"prefill_behind_fused_producers": staged_leg} if staged_leg else {}),
-            "decode_launches_per_pass": sum(1 for _ in runner.buf[1]["calls"]),
-            "decode_GBps_whole_pass": round(runner.weight_bytes() / (dc_us * 1e-6) / 1e9, 1),
-        },
-        "roofline": roofline,
-    }
+    out = headline()
+    out["config"].update({
+        "prefill_tokens_per_s": round(a.prefill / (pf_us * 1e-6), 1),
+        "decode_tokens_per_s": round(1.0 / (dc_us * 1e-6), 1),
+        "prefill_pass_ms": round(pf_us / 1e3, 3), "decode_pass_ms": round(dc_us / 1e3, 4),
+        "prefill_exact": {"flags": "LFAMD_FLAG_PRECISE", "pass_ms": round(pfx_us / 1e3, 3),
+                          "tokens_per_s": round(a.prefill / (pfx_us * 1e-6), 1), "numerics": "2e-6 of the oracle"},
+        **({"prefill_behind_fused_producers": staged_leg} if staged_leg else {}),
+        "decode_GBps_whole_pass": round(runner.weight_bytes() / (dc_us * 1e-6) / 1e9, 1),
+    })
+    out["roofline"] = roofline
     if allreduce_us is not None:
         out["roofline"]["allreduce_us"] = allreduce_us  # the 2 x n_layers residual-stream all-reduces of one decode pass, back to back
-    if comm_invalid:
-        out["invalid"] = comm_invalid
     if roofline_gemm:
         out["roofline_prefill_gemm"] = roofline_gemm
     if small_batch:

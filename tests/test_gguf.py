@@ -150,7 +150,8 @@ def test_bench_runs_from_a_model_file(gpu, tmp_path):
     p, _ = _tiny_llama(tmp_path)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gguf", str(p), "--steps", "1", "--warmup", "1", "--prefill", "128",
-                        "--decode", "4", "--no-cpu-baseline", "--no-extra-configs"], capture_output=True, text=True, timeout=600)
+                        "--decode", "4", "--full", "--no-cpu-baseline", "--no-extra-configs"], capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["value"] > 0 and d["config"]["model"] == "gguf:tiny.gguf" and "tiny.gguf" in d["data"]

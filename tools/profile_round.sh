@@ -5,7 +5,7 @@
 # Summaries are written to gpurun_out/prof/*.json|csv; copy what should be judged into profiles/.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/prof; rm -rf $OUT; mkdir -p $OUT
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/bench_profiled.json 2> $OUT/stats.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs > $OUT/bench_profiled.json 2> $OUT/stats.err
 f=$(find $OUT/stats -name "*kernel_stats.csv" | head -1)
 python3 - "$f" $OUT/kernel_stats_trimmed.csv <<'PY'
 import csv, sys
@@ -20,7 +20,7 @@ with open(sys.argv[2], "w") as o:
 PY
 rm -rf $OUT/stats/*/*kernel_trace.csv
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $ctr --output-format csv -d $OUT/pmc_$ctr -- python3 bench.py --steps 1 --warmup 0 --decode 4 --no-graph --no-cpu-baseline --no-extra-configs > $OUT/pmc_$ctr.json 2> $OUT/pmc_$ctr.err
+  timeout -k 10 300 rocprofv3 --pmc $ctr --output-format csv -d $OUT/pmc_$ctr -- python3 bench.py --full --steps 1 --warmup 0 --decode 4 --no-graph --no-cpu-baseline --no-extra-configs > $OUT/pmc_$ctr.json 2> $OUT/pmc_$ctr.err
 done
 python3 - $OUT <<'PY'
 import csv, glob, json, sys, collections

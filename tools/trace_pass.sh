@@ -2,7 +2,7 @@
 # development: kernel trace of a short bench run; prints start / duration / gap of the kernels of one decode pass
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/trace; rm -rf $OUT; mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 bench.py --steps 1 --warmup 1 --decode 8 --no-cpu-baseline --no-extra-configs > $OUT/bench.json 2> $OUT/err.log
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 bench.py --full --steps 1 --warmup 1 --decode 8 --no-cpu-baseline --no-extra-configs > $OUT/bench.json 2> $OUT/err.log
 f=$(find $OUT/t -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys
