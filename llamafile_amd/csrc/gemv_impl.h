@@ -403,6 +403,7 @@ struct q5k_traits {
 
 // Q6_K: sub-blocks are 16 wide (one per K-step), codes are 6 bit, offset -32 handled as
 // sum sc*(dot(code,q8) - 32*sum(q8)) like DequantizerQ6K (iqk_mul_mat.inc:570-599).
+typedef short short2_t __attribute__((ext_vector_type(2)));
 struct q6k_traits {
     static constexpr int ACT = LFAMD_TYPE_Q8_K; // activation quantisation the reference uses for this type
     static constexpr int TILE = P6K_TILE;
@@ -418,6 +419,13 @@ struct q6k_traits {
         ch.sc[s] = buf_ld8(r, off + P6K_SC + hrow * 16 + gsel * 8); // scales of K-steps 8*gsel..+7
         ch.d[s] = buf_ld2(r, off + P6K_D + hrow * 2);
     }
+    // Per lane: sumi = sum_t sc_t * <c_t, y_t> - 32 * sum_t sc_t * hs_t over its eight K-steps t (exact integers).
+    //   codes: the two K-steps of a qh dword H share its bytes.  The fields of the lo bytes (j0,j4,j1,j5) sit at bits 4-5 /
+    //   6-7 of H's bytes (even / odd K-step); those of the hi bytes (j2,j6,j3,j7) at bits 0-1 / 2-3 of H's bytes 1,0,3,2 —
+    //   one v_perm per pair puts them in byte order, after which both halves are a shift and a mask away.
+    //   offset term: once per super-block as four v_dot2_i32_i16 of the sign-extended scale pairs (two v_perm per four
+    //   scales) against the staged int16 group sums, which already sit in pairs of K-steps.
+    //   |<c_t, y_t>| <= 16 * 63 * 128 < 2^23, so sc_t * <c_t, y_t> is a 24-bit multiply.
     __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
         const uint4 l0 = ch.l0[s], l1 = ch.l1[s], hq = ch.hq[s];
         const uint2 scb = ch.sc[s];
@@ -429,24 +437,36 @@ struct q6k_traits {
         const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
                                  yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
         const uint4 hbw = *(const uint4 *)(xb + XBLK_HB + 32 * gsel + 16 * h);
-        const uint32_t hbv[4] = {hbw.x, hbw.y, hbw.z, hbw.w};
+        const uint32_t hbv[4] = {hbw.x, hbw.y, hbw.z, hbw.w}; // int16 group sums of K-steps (2p, 2p + 1)
+        // int16 pairs (sc_2p, sc_2p+1): bytes (s, sign s, s', sign s') — v_perm selectors 8-11 copy the sign of bytes 1, 3,
+        // 5, 7 of {a, b}, so b = scales << 8 puts s0 / s2 there and a = scales s1 / s3
+        const uint32_t scw[2] = {scb.x, scb.y};
+        int sums = 0;
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const uint32_t sh = scw[u] << 8;
+            const uint32_t p01 = __builtin_amdgcn_perm(scw[u], sh, 0x0A050801), p23 = __builtin_amdgcn_perm(scw[u], sh, 0x0B070903);
+            sums = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, p01), __builtin_bit_cast(short2_t, hbv[2 * u]), sums, false);
+            sums = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, p23), __builtin_bit_cast(short2_t, hbv[2 * u + 1]), sums, false);
+        }
         int sumi = 0;
 #pragma unroll
-        for (int t8 = 0; t8 < 8; t8++) { // t8 = 4 gi + dd
-            const uint32_t x = lw[t8];
-            uint32_t H = hw[t8 >> 1];
-            if (t8 & 1)
-                H >>= 2;
-            // lo bytes (j0,j4,j1,j5): high fields at bits 4-5 of each byte already
-            const uint32_t clo = (x & 0x0F0F0F0F) | (H & 0x30303030);
-            // hi bytes (j2,j6,j3,j7): fields at bits 8-9 / 0-1 / 24-25 / 16-17
-            const uint32_t chi = ((x >> 4) & 0x0F0F0F0F) | ((H >> 4) & 0x00300030) | ((H << 12) & 0x30003000);
-            int isum = sdot4(clo, yw[2 * t8], 0);
-            isum = sdot4(chi, yw[2 * t8 + 1], isum);
-            const int hs = (int)(int16_t)((hbv[t8 >> 1] >> (16 * (t8 & 1))) & 0xffff);
-            const int sc = (int)(int8_t)(((t8 < 4 ? scb.x : scb.y) >> (8 * (t8 & 3))) & 0xff);
-            sumi += sc * (isum - 32 * hs);
+        for (int p = 0; p < 4; p++) { // K-steps t8 = 2p (even dd), 2p + 1 (odd dd)
+            const uint32_t H = hw[p];
+            const uint32_t P = __builtin_amdgcn_perm(H, H, 0x02030001); // bytes 1,0,3,2: hi-byte fields at bits 0-3
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const int t8 = 2 * p + e;
+                const uint32_t x = lw[t8];
+                const uint32_t clo = (x & 0x0F0F0F0F) | ((e ? H >> 2 : H) & 0x30303030);
+                const uint32_t chi = ((x >> 4) & 0x0F0F0F0F) | ((e ? P << 2 : P << 4) & 0x30303030);
+                int isum = sdot4(clo, yw[2 * t8], 0);
+                isum = sdot4(chi, yw[2 * t8 + 1], isum);
+                const int sc = (int)(int8_t)((scw[t8 >> 2] >> (8 * (t8 & 3))) & 0xff);
+                sumi += sc * ((int)((uint32_t)isum << 8) >> 8); // (an i24 operand: v_mul_i32_i24, the shifts fold away)
+            }
         }
+        sumi -= 32 * sums;
         const float d8 = *(const float *)(xb + XBLK_D);
         return (d * d8) * (float)sumi;
     }
@@ -1214,10 +1234,22 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
     static_assert(!(PAIR && (EARLY || IDS)), "the paired item is a variant of the plain launch");
     constexpr bool early = EARLY && !IDS; // (a kernel variant, not a run-time branch: hipcc merges its wait counts at a join)
     (void)cnt_pre;
+    // Tiles whose size is not a multiple of the 128-byte cache line (P6K: 6720 B) start 64 B into a line every other
+    // super-block: then every 256-byte run of a half-tile has its edge lines in common with the other half-tile of the
+    // tile, and both halves' d sit in one line.  Fetched by two work-groups on two XCDs, such a line crosses the fabric
+    // twice (Q6_K 4096 x 14336: 61.3 MB fetched for a 48.2 MB matrix).  Work-groups b and b + 8 share an XCD (blocks are
+    // dealt round-robin over the eight), so in every run of 16 items, items q and q + 8 take the two halves of one tile and
+    // the shared lines are fetched into one L2.  A bijection of [0, n_ht): the items past the last full run keep their
+    // order.  Which rows a work-group computes changes, not how: same bits.
+    constexpr bool XPAIR = !PAIR && TR::TILE % 128 != 0;
+    auto ht_of = [&](int q) __attribute__((always_inline)) {
+        return (XPAIR && q < (n_ht & ~15)) ? ((q & ~15) | ((q & 7) << 1) | ((q >> 3) & 1)) : q;
+    };
     if constexpr (early) {
-        const int hh = bid & 1;
+        const int hb = ht_of(bid);
+        const int hh = hb & 1;
         const uint32_t rtb = (uint32_t)nb * TR::TILE;
-        const lfamd_rsrc r = make_rsrc(A0_pre + (size_t)(bid >> 1) * rtb, bid < n_ht ? rtb : 0u);
+        const lfamd_rsrc r = make_rsrc(A0_pre + (size_t)(hb >> 1) * rtb, hb < n_ht ? rtb : 0u);
 #pragma unroll
         for (int s = 0; s < GEMV_CH; s++)
             TR::load(bufA, s, r, (uint32_t)(wave + NW * s) * TR::TILE, gsel, h * 32 + hh * 16 + i16, hh * 16 + i16);
@@ -1242,7 +1274,7 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
     // CU's vector-memory queue is simply full — both 2-7 % slower on every decode shape)
 #define KQ_ISSUE(buf)                                                                                                  \
     do {                                                                                                               \
-        kq_issue<TR, NW, GEMV_CH, IDS>(buf, mats, tab, ci, n_ht, rt_bytes, wave, i16, h, gsel);                            \
+        kq_issue<TR, NW, GEMV_CH, IDS>(buf, mats, tab, kq_cursor{ht_of(ci.ht), ci.chunk}, n_ht, rt_bytes, wave, i16, h, gsel); \
         if constexpr (PAIR) {                                                                                          \
             const kq_cursor c2{ci.ht + 1, ci.chunk};                                                                   \
             kq_issue<TR, NW, GEMV_CH, IDS>(buf##2, mats, tab, c2, n_ht, rt_bytes, wave, i16, h, gsel);                 \
@@ -1256,12 +1288,13 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
         GSTAMP_ARRIVAL();                                                                                              \
         _Pragma("unroll") for (int s = 0; s < GEMV_CH; s++) {                                                          \
             const int b = wave + NW * (cc.chunk * GEMV_CH + s);                                                        \
-            /* a super-block beyond the row was loaded as zeros; its image slot belongs to nobody: discard */          \
-            const float t = TR::dot(buf, s, lds + (size_t)(b < nb ? b : 0) * XBLK, gsel, h);                           \
-            acc += b < nb ? t : 0.0f;                                                                                  \
-            if constexpr (PAIR) {                                                                                      \
-                const float t2 = TR::dot(buf##2, s, lds + (size_t)(b < nb ? b : 0) * XBLK, gsel, h);                   \
-                acc2 += b < nb ? t2 : 0.0f;                                                                            \
+            /* a super-block beyond the row was loaded as zeros and its image slot belongs to nobody: no dot (b is   \
+               wave-uniform, a scalar branch; the loads stay unconditional, see kq_issue).  acc is never -0, so       \
+               skipping an addend of zero changes no bit */                                                            \
+            if (b < nb) {                                                                                              \
+                acc += TR::dot(buf, s, lds + (size_t)b * XBLK, gsel, h);                                               \
+                if constexpr (PAIR)                                                                                    \
+                    acc2 += TR::dot(buf##2, s, lds + (size_t)b * XBLK, gsel, h);                                       \
             }                                                                                                          \
         }                                                                                                              \
         if (cc.chunk == cpt - 1) {                                                                                     \
@@ -1284,7 +1317,7 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
                 const int i = threadIdx.x;                                                                             \
                 float t = 0.0f;                                                                                        \
                 _Pragma("unroll") for (int w = 0; w < NW; w++) t += rb[w * RW + i];                                    \
-                const kq_sel p = kq_pick(tab, cc.ht);                                                               \
+                const kq_sel p = kq_pick(tab, ht_of(cc.ht));                                                           \
                 const long row = (long)(p.ht >> 1) * 32 + (p.ht & 1) * 16 + i; /* (PAIR: p.ht even, i < 32) */         \
                 bool ok = true;                                                                                        \
                 if constexpr (IDS) { /* an out-of-range expert id leaves its result row untouched */                   \
