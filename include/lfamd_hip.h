@@ -100,22 +100,41 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
 
 /* Batches (n > 8) of Q4_K / Q5_K / Q6_K run the scaled-operand MFMA body by default: weights as f16(d * sc * q), activations as
  * f16(d8 * code), f32 accumulate — one f16 rounding per operand, relative error ~1e-4 (north star: 1e-3), no scaling per
- * super-block.  Its constants need |d| * 63 < 64 and |dmin| * 63 <= 65504 for every block, which every ggml-quantised
+ * super-block.  Its constants need f16(|d| * 63) * 1024 <= 65504 and |dmin| * 63 <= 65504 for every block, which every ggml-quantised
  * model satisfies (d = max|w| / (15 * 63)).  lfamd_scaled_gemm_ok checks a packed matrix once after the upload
  * (synchronises the stream): 1 = in range, 0 = out of range -> pass LFAMD_FLAG_PRECISE with this matrix (exact integer
  * codes, f32 scales; out-of-range scales would otherwise surface as inf / NaN outputs), < 0 = error.  Types other than
- * the K-quants with a resident layout: always 1.  (Q6_K: |d| * 127 * 32 <= 65504.)
+ * the K-quants and Q8_0: always 1.  (Q4_K / Q5_K: the body forms f16(d * sc) * -1024, so f16(|d| * 63) * 1024 <= 65504;
+ * Q6_K: |d| * 127 * 32 <= 65504; Q8_0: the f16 batch body's weight image f16(d * q) needs |d| * 127 <= 65504 — an
+ * out-of-range Q8_0 matrix passes LFAMD_FLAG_Q80_EXACT instead, lfamd_exact_flag.)
  * Activations are normalised per token by a power of two before the f16 staging and the output column is scaled back
  * (exact), so their magnitude is not limited by f16; only a spread of more than ~2^24 INSIDE one token underflows its
  * smallest super-blocks (they contribute < 1e-7 of the result). */
 int lfamd_scaled_gemm_ok(int type, long rows, long cols, const void *d_packed, void *stream);
+/* The flag a call on a matrix that lfamd_scaled_gemm_ok answered 0 for must carry: LFAMD_FLAG_Q80_EXACT for Q8_0 (type 8; its
+ * GEMVs keep their arithmetic), LFAMD_FLAG_PRECISE for the K-quants. */
+static inline unsigned lfamd_exact_flag(int type) {
+    return type == 8 ? LFAMD_FLAG_Q80_EXACT : LFAMD_FLAG_PRECISE;
+}
 
 /* Which arithmetic a lfamd_mul_mat call with these arguments runs: 1 = exact integer block dot products with f32 scales (the
- * reference's CPU arithmetic, iqk_mul_mat.inc:601-643; within 2e-6 of it: only the order of the f32 sums differs) — every call
- * of up to 32 columns, LFAMD_FLAG_PRECISE, and since round 4 the Q4_K batches that run on the int8 matrix cores
- * (llamafile_amd/csrc/gemm_i8.hip: grids of at most 256 tiles of 128 x 128 that still fill half the chip — attn_q, attn_output,
- * ffn_down of an 8B model at 512 tokens); 0 = scaled operands on the f16 matrix cores (one f16 rounding per operand, <= 1e-3,
- * measured ~3e-4; Q6_K's exact body also rounds sc * (q - 32) above 2048).  No device call is made. */
+ * reference's CPU arithmetic, iqk_mul_mat.inc:601-643; within 2e-6 of it: only the order of the f32 sums differs); 0 = scaled
+ * operands on the f16 matrix cores (one f16 rounding per operand, <= 1e-3, measured ~3e-4).  In order:
+ *   LFAMD_FLAG_FORCE_GENERIC: 1 (the generic kernels; packed types refuse the flag);
+ *   every call of up to 8 columns (the GEMVs; Q8_0 bit-exact): 1;
+ *   F32 / F16 / BF16 weights: 1 — the activations are taken in, or rounded from F32 to, the weight's own type, as the
+ *     reference's vec_dot_type conversion does, and the products of two 16-bit values are exact in f32;
+ *   Q8_0 batches: 0 on the f16 MFMA body (rows of whole 128-weight quads, or the vendor GEMM), 1 on the bit-exact kernel
+ *     (LFAMD_FLAG_Q80_EXACT / LFAMD_FLAG_PRECISE, other row lengths);
+ *   IQ4_XS batches: 0 (the canonical image rounds |sc * kvalue| above 2048 to f16); Q2_K / Q3_K (|sc * q| <= 128) and the
+ *     legacy 32-block bodies: 1;
+ *   Q4_K / Q5_K / Q6_K batches of 9 .. 32 columns that run the small-batch kernel (gemm_sb.hip; where lfamd_mul_mat picks it:
+ *     at most a few row tiles per CU, or deep rows): 1; other Q6_K batches: 0 (both batch bodies round sc * (q - 32) above
+ *     2048); LFAMD_FLAG_PRECISE / _GEMM_NARROW / _GEMM_PLAIN: 1; the Q4_K batches on the int8 matrix cores (gemm_i8.hip: grids
+ *     of at most 256 tiles of 128 x 128 that still fill half the chip): 1; the rest: 0.
+ * The answer is per matrix: it does not hold for a matrix inside a mixed-type lfamd_mul_mat_multi_types launch (a Q4_K matrix
+ * that would run the int8 body alone shares the scaled f16 staging with its Q6_K sibling there).  A matrix that
+ * lfamd_scaled_gemm_ok found out of range is asked about with lfamd_exact_flag(type) in `flags`.  No device call is made. */
 int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags);
 
 /* ---- activations --------------------------------------------------------------------------

@@ -312,9 +312,9 @@ int lfamd_scaled_gemm_ok(int type, long rows, long cols, const void *d_packed, v
     (void)hipGetLastError();
     if (!type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "scaled_gemm_ok: unsupported ggml type%s", "");
-    if ((type != LFAMD_TYPE_Q4_K && type != LFAMD_TYPE_Q5_K && type != LFAMD_TYPE_Q6_K) || rows <= 0 || cols <= 0)
+    if ((type != LFAMD_TYPE_Q4_K && type != LFAMD_TYPE_Q5_K && type != LFAMD_TYPE_Q6_K && type != LFAMD_TYPE_Q8_0) || rows <= 0 || cols <= 0)
         return 1;
-    if (cols % 256 || !d_packed)
+    if (cols % (type == LFAMD_TYPE_Q8_0 ? 32 : 256) || !d_packed)
         return fail(LFAMD_ERR_INVALID, "scaled_gemm_ok: bad shape%s", "");
     hipStream_t s = (hipStream_t)stream;
     int *d_flag = nullptr, h_flag = 0;
@@ -456,9 +456,18 @@ static bool gemv_quantise_separately(int Atype, long m) {
 int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags) {
     if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
-    const bool kq = Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K;
-    if (n <= 8 || !kq)
-        return Atype != LFAMD_TYPE_Q8_0 || n <= 8 || !(use_gemm_q80_lt(Atype, n, flags, k) || use_gemm_q80_lf(Atype, n, flags, k)) ? 1 : 0;
+    if (flags & LFAMD_FLAG_FORCE_GENERIC) // the generic kernels: integer block dots at every n (packed types refuse the flag)
+        return 1;
+    if (n <= 8) // the GEMVs (Q8_0: bit-exact)
+        return 1;
+    if (Atype == LFAMD_TYPE_F32 || Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16)
+        return 1; // activations in (or rounded from F32 to) the weight's own type, as the reference's vec_dot_type; exact f32 products
+    if (Atype == LFAMD_TYPE_Q8_0)
+        return use_gemm_q80_lt(Atype, n, flags, k) || use_gemm_q80_lf(Atype, n, flags, k) ? 0 : 1;
+    if (Atype == LFAMD_TYPE_IQ4_XS) // the canonical image rounds |sc * kvalue| above 2048 to f16
+        return use_gemm_canon(Atype, n, flags) ? 0 : 1;
+    if (Atype != LFAMD_TYPE_Q4_K && Atype != LFAMD_TYPE_Q5_K && Atype != LFAMD_TYPE_Q6_K)
+        return 1; // Q2_K / Q3_K canonical image (|sc * q| <= 128), P40 / PCL legacy bodies: integer codes, f32 scales
     if (use_gemm_sb(Atype, n, flags, k, m))
         return 1;
     if (Atype == LFAMD_TYPE_Q6_K)

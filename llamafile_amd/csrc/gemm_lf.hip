@@ -99,7 +99,7 @@ extern "C" int lfamd_debug_lf_stamps(unsigned long long *dst) {
 
 template <int NT>
 __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, int nq, const _Float16 *__restrict__ Xh, long n, long n_pad,
-                                                           int n_rb, int n_ct) {
+                                                           int n_rb, int n_ct, const float *__restrict__ tok_scale) {
 #ifdef LF_CHECK_NQ // tools/isa_hazards.py: a fixed trip count
     nq = LF_CHECK_NQ;
 #endif
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
             for (int e = 0; e < 16; e++) {
                 const long tk = n0 + 32 * t + 8 * (e >> 2) + 4 * h + (e & 3);
                 if (tk < n)
-                    C[tk * ldc + row] = acc[t][e];
+                    C[tk * ldc + row] = acc[t][e] * tok_scale[tk]; // (2^e of the token's staging: exact)
             }
     }
 #ifdef LF_STAMPS
@@ -451,9 +451,44 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
 // or the caller's Q8_0 blocks), written as Xh [quad][n_pad][256 B]: 16-byte chunk 2 s + h of a token and quad = K-step s = 2 jj + e,
 // K half h = {block 2 e, block 2 e + 1} x {elements 4 j .. 4 j + 3}, j = 4 h + jj.  One thread per eight consecutive elements
 // (two groups j = 2 o, 2 o + 1 of block bq of the quad); the block maximum over the four threads of a block by DPP.
+// Every token is normalised by a power of two first (lf_tok_scale_kernel, the rule of prep_scaled_kernel): its largest |d8| * 127
+// lands in [512, 1024), so neither a 3e5 token overflows f16 nor a 1e-7 one sinks into its subnormals, and the store multiplies the
+// column back.  A power of two commutes with the rounding: tokens the unnormalised staging held in f16's normal range keep their bits.
+template <bool F32IN>
+__global__ __launch_bounds__(256) void lf_tok_scale_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long k,
+                                                           float *__restrict__ stage, float *__restrict__ tok_scale) {
+    __shared__ float wmax[4];
+    const long tok = (long)blockIdx.x;
+    const int t = threadIdx.x;
+    const uint8_t *row = X + (size_t)tok * x_row_bytes;
+    float dmax = 0.0f;
+    if constexpr (F32IN) { // f16(amax / 127) is monotonic in amax: the row maximum gives the largest block scale
+        for (long c = 4 * (long)t; c < k; c += 1024) {
+            const float4 f = *(const float4 *)((const float *)row + c);
+            dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w))));
+        }
+    } else {
+        for (long b = t; b < k / 32; b += 256)
+            dmax = fmaxf(dmax, fabsf(h2f(((const lfamd_block_q8_0 *)row + b)->d)));
+    }
+    dmax = wave_max_f32(dmax);
+    if ((t & 63) == 0)
+        wmax[t >> 6] = dmax;
+    __syncthreads();
+    if (t != 0)
+        return;
+    dmax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if constexpr (F32IN)
+        dmax = (float)(_Float16)(dmax / 127.0f);
+    dmax *= 127.0f;
+    const bool ok = dmax > 0.0f && dmax < 3.0e38f; // (zero / non-finite rows: no normalisation)
+    stage[tok] = ok ? ldexpf(1.0f, 9 - ilogbf(dmax)) : 1.0f;
+    tok_scale[tok] = ok ? ldexpf(1.0f, ilogbf(dmax) - 9) : 1.0f;
+}
+
 template <bool F32IN>
 __global__ __launch_bounds__(256) void prep_lf_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long n, long n_pad, int nq,
-                                                       _Float16 *__restrict__ Xh) {
+                                                       _Float16 *__restrict__ Xh, const float *__restrict__ stage) {
     const long tok = (long)blockIdx.x;
     const int c8 = (int)blockIdx.y * 256 + (int)threadIdx.x; // eight elements 8 c8 .. 8 c8 + 7 of the row
     const bool live = c8 < nq * 16;
@@ -487,6 +522,8 @@ __global__ __launch_bounds__(256) void prep_lf_kernel(const uint8_t *__restrict_
     }
     if (!live)
         return;
+    if (tok < n)
+        d *= stage[tok]; // (exact: a power of two)
     const int quad = cc >> 4, blk = (cc >> 2) & 3, o = cc & 3;
     uint8_t *dst = (uint8_t *)Xh + ((size_t)quad * n_pad + tok) * 256;
 #pragma unroll
@@ -785,9 +822,9 @@ static int lf_nt(long row_blocks128, long n) {
     return row_blocks128 * ((n + 63) / 64) <= 256 ? 2 : 4;
 }
 
-extern "C" size_t lfamd_gemm_lf_workspace(long k, long n) { // Xh
+extern "C" size_t lfamd_gemm_lf_workspace(long k, long n) { // Xh, then the staging and store factors of every token
     const size_t n_pad = ((size_t)n + 127) / 128 * 128;
-    return n_pad * (size_t)k * 2;
+    return n_pad * (size_t)k * 2 + n_pad * 8;
 }
 
 // B: f32 rows or Q8_0 blocks; ws: lfamd_gemm_lf_workspace(k, n) bytes; A[j]: P80 images of m[j] x k.
@@ -800,11 +837,15 @@ extern "C" hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, 
     const int nq = (int)(k / 128);
     const long n_pad = (n + 127) / 128 * 128;
     _Float16 *Xh = (_Float16 *)ws;
+    float *stage = (float *)((uint8_t *)ws + (size_t)n_pad * (size_t)k * 2), *tok_scale = stage + n_pad;
     const dim3 pg((unsigned)n_pad, (unsigned)((nq * 16 + 255) / 256));
-    if (Btype == LFAMD_TYPE_F32)
-        prep_lf_kernel<true><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh);
-    else
-        prep_lf_kernel<false><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh);
+    if (Btype == LFAMD_TYPE_F32) {
+        lf_tok_scale_kernel<true><<<(unsigned)n, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, k, stage, tok_scale);
+        prep_lf_kernel<true><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh, stage);
+    } else {
+        lf_tok_scale_kernel<false><<<(unsigned)n, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, k, stage, tok_scale);
+        prep_lf_kernel<false><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh, stage);
+    }
     gemm_mats mats;
     int n_rb = 0;
     mats.count = 0;
@@ -825,10 +866,10 @@ extern "C" hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, 
         mats.A[q] = mats.A[0], mats.C[q] = mats.C[0], mats.m[q] = 0, mats.ldc[q] = 0, mats.rb_end[q] = n_rb;
     if (lf_nt(n_rb, n) == 4) {
         const int n_ct = (int)((n + 127) / 128);
-        gemm_lf_q80_kernel<4><<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nq, Xh, n, n_pad, n_rb, n_ct);
+        gemm_lf_q80_kernel<4><<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nq, Xh, n, n_pad, n_rb, n_ct, tok_scale);
     } else {
         const int n_ct = (int)((n + 63) / 64);
-        gemm_lf_q80_kernel<2><<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nq, Xh, n, n_pad, n_rb, n_ct);
+        gemm_lf_q80_kernel<2><<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nq, Xh, n, n_pad, n_rb, n_ct, tok_scale);
     }
     return hipGetLastError();
 }

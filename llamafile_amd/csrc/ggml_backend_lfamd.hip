@@ -394,8 +394,8 @@ const packed *get_packed_rows(void *&scratch, size_t &scratch_cap, int type, con
             (void)hipFree(p.d);
         return nullptr;
     }
-    // (only the K-quant batch bodies have a scaled-operand form whose range must be checked; the check synchronises the stream)
-    const bool scaled_form = type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K;
+    // (only the K-quant and Q8_0 batch bodies have a scaled-operand form whose range must be checked; the check synchronises the stream)
+    const bool scaled_form = type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K || type == LFAMD_TYPE_Q8_0;
     p.exact_only = scaled_form && lfamd_scaled_gemm_ok(type, rows, cols, p.d, nullptr) == 0;
     if (keep)
         return &(g_packed[raw] = p);
@@ -520,7 +520,7 @@ enum ggml_status run_mul_mat_split(backend_ctx *ctx, struct ggml_tensor *dst) {
                 if (!grow(ws, ws_cap, lfamd_mul_mat_workspace(a->type, rows, k, n)))
                     return GGML_STATUS_ALLOC_FAILED;
                 if (lfamd_mul_mat(a->type, w->d, rows, k, LFAMD_TYPE_F32, B, brb, n, C, c_ld, ws, ws_cap,
-                                  (w->exact_only ? LFAMD_FLAG_PRECISE : 0u) | LFAMD_FLAG_Q0_VREGS32, nullptr) != LFAMD_OK) {
+                                  (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | LFAMD_FLAG_Q0_VREGS32, nullptr) != LFAMD_OK) {
                     logf("%s: lfamd_mul_mat (row slice): %s\n", "ggml_backend_lfamd", lfamd_last_error());
                     return GGML_STATUS_FAILED;
                 }
@@ -568,7 +568,7 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
             const uint8_t *bp = (const uint8_t *)b->data + i12 * b->nb[2] + i13 * b->nb[3];
             float *cp = (float *)((uint8_t *)dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]);
             if (lfamd_mul_mat(a->type, w->d, m, k, LFAMD_TYPE_F32, bp, b->nb[1], n, cp, (long)(dst->nb[1] / sizeof(float)), ctx->ws,
-                              ctx->ws_cap, (w->exact_only ? LFAMD_FLAG_PRECISE : 0u) | LFAMD_FLAG_Q0_VREGS32, nullptr) != LFAMD_OK) {
+                              ctx->ws_cap, (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | LFAMD_FLAG_Q0_VREGS32, nullptr) != LFAMD_OK) {
                 logf("%s: lfamd_mul_mat: %s\n", "ggml_backend_lfamd", lfamd_last_error());
                 return GGML_STATUS_FAILED;
             }
@@ -617,7 +617,9 @@ const packed *get_packed_stack(backend_ctx *ctx, const struct ggml_tensor *as, p
                 (void)hipFree(p.d);
             return nullptr;
         }
-    p.exact_only = lfamd_scaled_gemm_ok(as->type, (long)experts * ((rows + 31) / 32) * 32, cols, p.d, nullptr) == 0;
+    // (K-quant stacks: rows of every expert rounded to the 32-row tiles; a Q8_0 expert stack is not checked)
+    const bool kq = as->type == LFAMD_TYPE_Q4_K || as->type == LFAMD_TYPE_Q5_K || as->type == LFAMD_TYPE_Q6_K;
+    p.exact_only = kq && lfamd_scaled_gemm_ok(as->type, (long)experts * ((rows + 31) / 32) * 32, cols, p.d, nullptr) == 0;
     if (keep)
         return &(g_packed[as_bytes] = p);
     *tmp = p;
@@ -734,7 +736,7 @@ enum ggml_status run_mul_mat_siblings(backend_ctx *ctx, struct ggml_tensor *cons
             return GGML_STATUS_ALLOC_FAILED;
         types[j] = a->type, A[j] = w->d, m[j] = (long)a->ne[1], ldc[j] = (long)a->ne[1], C[j] = (float *)dsts[j]->data;
         if (w->exact_only)
-            flags |= LFAMD_FLAG_PRECISE;
+            flags |= lfamd_exact_flag(a->type);
         const size_t need = lfamd_mul_mat_workspace(a->type, m[j], k, n);
         wsb = need > wsb ? need : wsb;
     }

@@ -834,10 +834,11 @@ hipError_t lfamd_launch_prep_q8k(const void *B, size_t b_row_bytes, long n, long
 }
 
 // ---------------------------------------------------------------------------------------------
-// Range check for the scaled-operand GEMM (gemm_lw.hip FAST): every row header of a P4K / P5K / P6K image.
+// Range check for the scaled-operand GEMM (gemm_lw.hip FAST): every row header of a P4K / P5K / P6K image; for Q8_0 every block
+// scale of the P80 image that the f16 batch body (gemm_lf.hip) turns into f16(d * q).
 
-__global__ void scaled_ok_kernel(const uint8_t *__restrict__ img, long tiles, int tile_bytes, int q6, int *__restrict__ bad) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; // (tile, row in tile)
+__global__ void scaled_ok_kernel(const uint8_t *__restrict__ img, long tiles, int tile_bytes, int mode, int *__restrict__ bad) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; // (tile, row in tile) / P80: (tile, row r * 4 + block)
     if (idx >= tiles * 32)
         return;
     union {
@@ -845,7 +846,13 @@ __global__ void scaled_ok_kernel(const uint8_t *__restrict__ img, long tiles, in
         _Float16 h;
     } d, dm;
     const uint8_t *tile = img + (size_t)(idx >> 5) * tile_bytes;
-    if (q6) { // f16(d * sc) * (code - 32): |d| * 127 * 32 must stay inside f16
+    if (mode == 2) { // f16(d * q), |q| <= 127 (padding scales are 0)
+        d.u = *(const uint16_t *)(tile + P80_D + (idx & 31) * 2);
+        if (!(fabsf((float)d.h) * 127.0f <= 65504.0f))
+            atomicOr(bad, 1);
+        return;
+    }
+    if (mode == 1) { // f16(d * sc) * (code - 32): |d| * 127 * 32 must stay inside f16
         d.u = *(const uint16_t *)(tile + P6K_D + (idx & 31) * 2);
         if (!(fabsf((float)d.h) * (127.0f * 32.0f) <= 65504.0f))
             atomicOr(bad, 1);
@@ -854,15 +861,17 @@ __global__ void scaled_ok_kernel(const uint8_t *__restrict__ img, long tiles, in
     const uint32_t dd = *(const uint32_t *)(tile + P4K_HDR + (idx & 31) * 16);
     d.u = (uint16_t)(dd & 0xffff), dm.u = (uint16_t)(dd >> 16);
     const float fd = fabsf((float)d.h), fm = fabsf((float)dm.h);
-    if (!(fd * 63.0f < 64.0f) || !(fm * 63.0f <= 65504.0f)) // also catches NaN / inf
+    // the body forms S = f16(d * sc) and O = S * -1024 in f16 (q4_consts_pair_scaled): f16(|d| * 63) * 1024 must stay inside f16
+    if (!((float)(_Float16)(fd * 63.0f) * 1024.0f <= 65504.0f) || !(fm * 63.0f <= 65504.0f)) // also catches NaN / inf
         atomicOr(bad, 1);
 }
 
 extern "C" hipError_t lfamd_launch_scaled_ok(int type, long rows, long cols, const void *packed, int *d_flag, hipStream_t s) {
-    const long tiles = ((rows + 31) / 32) * (cols / 256);
-    const int tile_bytes = type == LFAMD_TYPE_Q5_K ? P5K_TILE : type == LFAMD_TYPE_Q6_K ? P6K_TILE : P4K_TILE;
+    const bool q80 = type == LFAMD_TYPE_Q8_0;
+    const long tiles = q80 ? ((rows + 7) / 8) * ((cols / 32 + 3) / 4) : ((rows + 31) / 32) * (cols / 256);
+    const int tile_bytes = q80 ? P80_TILE : type == LFAMD_TYPE_Q5_K ? P5K_TILE : type == LFAMD_TYPE_Q6_K ? P6K_TILE : P4K_TILE;
     const long threads = tiles * 32;
     scaled_ok_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)packed, tiles, tile_bytes,
-                                                                       type == LFAMD_TYPE_Q6_K ? 1 : 0, d_flag);
+                                                                       q80 ? 2 : type == LFAMD_TYPE_Q6_K ? 1 : 0, d_flag);
     return hipGetLastError();
 }

@@ -460,7 +460,7 @@ bool run_mul_mat(int Atype, const void *A, long m, long kelems, size_t a_row_byt
     if (n == 1 && zero_copy && reserve_host(g_hb, bbytes) && reserve_host(g_hc, cbytes)) {
         memcpy(g_hb.p, B, bbytes);
         if (g.api.mul_mat(Atype, w.d_packed, m, kelems, Btype, g_hb.p, b_row_bytes, n, (float *)g_hc.p, ldc, g.ws.p, g.ws.cap,
-                          flags_now() | (w.exact_only ? LFAMD_FLAG_PRECISE : 0u), nullptr) != LFAMD_OK)
+                          flags_now() | (w.exact_only ? lfamd_exact_flag(Atype) : 0u), nullptr) != LFAMD_OK)
             return false;
         if (g.api.sync(nullptr) != LFAMD_OK)
             return false;
@@ -475,7 +475,7 @@ bool run_mul_mat(int Atype, const void *A, long m, long kelems, size_t a_row_byt
         if (g.api.h2d(g.c.p, C, cbytes, nullptr) != LFAMD_OK)
             return false;
     if (g.api.mul_mat(Atype, w.d_packed, m, kelems, Btype, g.b.p, b_row_bytes, n, (float *)g.c.p, ldc, g.ws.p, g.ws.cap,
-                      flags_now() | (w.exact_only ? LFAMD_FLAG_PRECISE : 0u), nullptr) != LFAMD_OK)
+                      flags_now() | (w.exact_only ? lfamd_exact_flag(Atype) : 0u), nullptr) != LFAMD_OK)
         return false;
     if (g.api.d2h(C, g.c.p, cbytes, nullptr) != LFAMD_OK)
         return false;
@@ -708,7 +708,10 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
                     g.api.sync(nullptr))
                     die("expert weight upload failed");
             }
-            const int in_range = g.api.scaled_ok(wt, (long)experts * ((rows + 31) / 32) * 32, cols, dst, nullptr);
+            // (K-quant stacks only: the check walks 32-row K-quant tiles over the whole stack; a Q8_0 expert stack never runs the
+            // f16 batch body, whose P80 range this check would otherwise read at the wrong tile geometry and past the stack's end)
+            const bool kq = wt == LFAMD_TYPE_Q4_K || wt == LFAMD_TYPE_Q5_K || wt == LFAMD_TYPE_Q6_K;
+            const int in_range = kq ? g.api.scaled_ok(wt, (long)experts * ((rows + 31) / 32) * 32, cols, dst, nullptr) : 1;
             if (in_range < 0)
                 die("expert weight range check failed");
             w = {dst, in_range == 0};
@@ -760,7 +763,7 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
     if (g.api.h2d(g.plan.p, hplan.data(), hplan.size() * 4, nullptr) || g.api.sync(nullptr))
         die("plan upload failed");
     if (g.api.mul_mat_id(wt, w.d_packed, rows, cols, experts, bt, g.b.p, brow, tasks, tokens, (const int32_t *)g.plan.p,
-                         thinkers, (float *)g.c.p, g.ws.p, g.ws.cap, flags_now() | (w.exact_only ? LFAMD_FLAG_PRECISE : 0u), nullptr))
+                         thinkers, (float *)g.c.p, g.ws.p, g.ws.cap, flags_now() | (w.exact_only ? lfamd_exact_flag(wt) : 0u), nullptr))
         die("device mul_mat_id failed");
     std::vector<float> &hres = g.h_out;
     hres.resize((size_t)tokens * thinkers * rows);

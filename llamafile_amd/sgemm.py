@@ -58,7 +58,12 @@ class PackedWeights:
     rows: int
     cols: int
     data: torch.Tensor  # uint8, cuda
-    exact_only: bool = False  # Q4_K / Q5_K block scales outside the scaled-operand GEMM's range (lfamd_scaled_gemm_ok)
+    exact_only: bool = False  # block scales outside the scaled-operand GEMM's range (lfamd_scaled_gemm_ok): Q4_K / Q5_K / Q6_K, Q8_0
+
+    @property
+    def exact_flag(self) -> int:
+        """What a call on an exact_only matrix adds: the bit-exact Q8_0 batch kernel, exact integer codes for the K-quants."""
+        return _hip.FLAG_Q80_EXACT if self.type == T.Q8_0 else _hip.FLAG_PRECISE
 
     @property
     def nbytes(self) -> int:
@@ -89,8 +94,8 @@ def upload_weights(t: int, raw, rows: int, cols: int, device="cuda") -> PackedWe
     out = torch.empty(max(size, 16), dtype=torch.uint8, device=raw.device)
     _hip.check(L.lfamd_pack_weights(t, rows, cols, _ptr(raw), raw.shape[1], _ptr(out), _stream()), "lfamd_pack_weights")
     W = PackedWeights(t, rows, cols, out[:size] if size else out[:0])
-    if t in (T.Q4_K, T.Q5_K, T.Q6_K) and rows and cols:
-        # scaled-operand batches need |d| < 64/63 (include/lfamd_hip.h): out-of-range matrices always run exact
+    if t in (T.Q4_K, T.Q5_K, T.Q6_K, T.Q8_0) and rows and cols:
+        # scaled-operand batches need their f16 operands in range (include/lfamd_hip.h): out-of-range matrices always run exact
         ok = L.lfamd_scaled_gemm_ok(t, rows, cols, _ptr(out), _stream())
         if ok < 0:
             raise _hip.LfamdError("lfamd_scaled_gemm_ok failed")
@@ -126,7 +131,7 @@ def mul_mat(W: PackedWeights, B: torch.Tensor, Btype: int, n: int | None = None,
         out = torch.empty((n, ldc), dtype=torch.float32, device=B.device)
     flags = host_variant_flags() if flags is None else flags
     if getattr(W, "exact_only", False):
-        flags |= _hip.FLAG_PRECISE
+        flags |= W.exact_flag
     need = L.lfamd_mul_mat_workspace(W.type, W.rows, W.cols, n)
     if need and (workspace is None or workspace.numel() < need):
         workspace = torch.empty(need, dtype=torch.uint8, device=B.device)
@@ -148,8 +153,9 @@ def mul_mat_multi(Ws: list, B: torch.Tensor, Btype: int, n: int | None = None, f
     mixed = any(w.type != Ws[0].type for w in Ws)
     n = B.shape[0] if n is None else n
     flags = host_variant_flags() if flags is None else flags
-    if any(getattr(w, "exact_only", False) for w in Ws):
-        flags |= _hip.FLAG_PRECISE
+    for w in Ws:
+        if getattr(w, "exact_only", False):
+            flags |= w.exact_flag
     outs = [torch.empty((n, w.rows), dtype=torch.float32, device=B.device) for w in Ws]
     need = max(L.lfamd_mul_mat_workspace(w.type, w.rows, w.cols, n) for w in Ws)
     if need and (workspace is None or workspace.numel() < need):
