@@ -56,7 +56,6 @@ hipError_t lfamd_launch_gemv_multi(int, int, const void *const *, const long *, 
 hipError_t lfamd_launch_gemm_q80(const void *, long, long, int, const void *, size_t, long, float *, long, void *, int, int,
                                  hipStream_t);
 size_t lfamd_gemm_q80_workspace(long, long);
-#define LW_MIN_TILES 1 // the 128 x 64 loader-wave tile beats the split-K body at every grid measured (8 .. 128 tiles: 5-10 %)
 hipError_t lfamd_launch_gemv_dual(int, int, const void *const *, const long *, float *const *, const long *, int, int,
                                   const void *const *, const long *, float *const *, const long *, long, int, const void *, size_t,
                                   hipStream_t);
@@ -344,62 +343,40 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
 }
 
 // ---------------------------------------------------------------------------------------------
+// Dispatch.  plan_mul_mat answers, once per call, which body runs it; lfamd_mul_mat launches that body, and lfamd_mul_mat_is_exact,
+// _takes_staged, _takes_staged_scaled and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
+// HIP call (lfamd_blaslt_ok() touches the device only when a host opted into the vendor library, LFAMD_USE_BLASLT=1).
 
 // Q4_0 rows that are whole 256-weight groups are kept in the P40 layout and served by the tuned kernels
 static bool packed40(int Atype, long k) {
     return Atype == LFAMD_TYPE_Q4_0 && k % 256 == 0;
 }
-
-static bool use_gemm(int Atype, long n, unsigned flags, long k) {
-    if (flags & LFAMD_FLAG_FORCE_GENERIC)
-        return false;
-    return n > 8 && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K || packed40(Atype, k));
+// legacy 32-block types whose rows are whole 256-weight groups (Q4_1, Q5_0, Q5_1): resident PCL image
+static bool packed_pcl(int Atype, long k) {
+    return k % 256 == 0 && (Atype == LFAMD_TYPE_Q4_1 || Atype == LFAMD_TYPE_Q5_0 || Atype == LFAMD_TYPE_Q5_1);
 }
-
-// K-quants whose resident layout is the canonical image the MFMA body reads (Q2_K, Q3_K: PCK; IQ4_XS: PC8)
-static bool use_gemm_canon(int Atype, long n, unsigned flags) {
-    return !(flags & LFAMD_FLAG_FORCE_GENERIC) && n > 8 &&
-           (Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K || Atype == LFAMD_TYPE_IQ4_XS);
+static bool kquant(int Atype) {
+    return Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K;
+}
+static bool float_type(int Atype) {
+    return Atype == LFAMD_TYPE_F32 || Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16;
+}
+// weights in a layout only the tuned kernels read: the decode GEMVs take them, the generic kernels do not
+static bool packed(int Atype, long k) {
+    return kquant(Atype) || Atype == LFAMD_TYPE_Q8_0 || Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K || Atype == LFAMD_TYPE_IQ4_XS ||
+           packed40(Atype, k) || packed_pcl(Atype, k);
+}
+// F16 / BF16 matrices the loader-wave body can address (32-bit byte offsets)
+static bool float_lf_fits(int Atype, long m, long k) {
+    return (size_t)m * lfamd_row_size(Atype, k) < ((size_t)1 << 32);
 }
 
 static size_t gemm_act_ws(long k, long n) { // Xh + d8T + Xm of the K-quant GEMM
     size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
     return align_up(n_pad * (size_t)k * 2, 256) + align_up(nb * n_pad * 4, 256) + align_up(n_pad * nb * 32, 256);
 }
-
-// legacy 32-block types whose rows are whole 256-weight groups (Q4_1, Q5_0, Q5_1): resident PCL image
-static bool packed_pcl(int Atype, long k) {
-    return k % 256 == 0 && (Atype == LFAMD_TYPE_Q4_1 || Atype == LFAMD_TYPE_Q5_0 || Atype == LFAMD_TYPE_Q5_1);
-}
-static bool use_gemm_canon32(int Atype, long n, unsigned flags, long k) {
-    return !(flags & LFAMD_FLAG_FORCE_GENERIC) && n > 8 && packed_pcl(Atype, k);
-}
-
-// F16 / BF16 weights, batches, rows of whole 256-element groups: MFMA body straight on the RAW rows
-static bool use_gemm_float(int Atype, long n, unsigned flags, long k) {
-    return !(flags & LFAMD_FLAG_FORCE_GENERIC) && n > 8 && k % 256 == 0 && (Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16);
-}
-
-// Q8_0 batches.  Default (rows of whole 128-weight quads): this module's f16 MFMA body on the resident P80 image (gemm_lf.hip) —
-// f16(d * q) x f16(d8 * q8), what the reference's GPU path computes for such a batch, <= 1e-3 (the north star's tolerance for
-// f16 MFMA paths).  The north star asks for bit-exactness of the Q8_0 VECDOT (n <= 8: the GEMV), not for replaying tinyBLAS's
-// 8-lane chains at n = 512; LFAMD_FLAG_PRECISE / LFAMD_FLAG_Q80_EXACT (or other row lengths): the register-tiled BIT-EXACT kernel
-// (gemm_q80.hip), an order of magnitude slower.  A host that opted into the vendor library (LFAMD_USE_BLASLT=1) gets its f16 GEMM
-// on a second resident image instead (use_gemm_q80_lt).
-static bool use_gemm_q80_lt(int Atype, long n, unsigned flags, long k) {
-    return !(flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT)) && n > 8 && Atype == LFAMD_TYPE_Q8_0 && k % 32 == 0 &&
-           lfamd_blaslt_ok();
-}
-static bool use_gemm_q80_lf(int Atype, long n, unsigned flags, long k) {
-    return !(flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT)) && n > 8 && Atype == LFAMD_TYPE_Q8_0 && k % 128 == 0 &&
-           !lfamd_blaslt_ok();
-}
 static size_t gemm_lt_ws(long k, long n) { // the 16-bit activation rows, then the library's workspace
     return align_up((size_t)n * (size_t)k * 2, 256) + lfamd_blaslt_workspace();
-}
-static bool use_gemm_q80(int Atype, long n, unsigned flags, long k) {
-    return !(flags & LFAMD_FLAG_FORCE_GENERIC) && n > 8 && Atype == LFAMD_TYPE_Q8_0 && !use_gemm_q80_lf(Atype, n, flags, k) &&
-           !use_gemm_q80_lt(Atype, n, flags, k);
 }
 
 // Small batches of Q4_K / Q5_K / Q6_K (up to 32 tokens) on gemm_sb.hip, where it is the fastest route (MI355X; old -> new, us).
@@ -413,14 +390,9 @@ static bool use_gemm_q80(int Atype, long n, unsigned flags, long k) {
 //   up to four row tiles per CU             : 6 <= n <= 24, not Q6_K
 // Below that the multi-column GEMV is faster (one launch, no staging pass); taller matrices keep the GEMV / the 128-token GEMM
 // tiles.  The testing flags that force a GEMM body or the generic kernels keep their meaning.
-static bool use_gemm_sb(int Atype, long n, unsigned flags, long k, long m) {
-    if (flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN))
+static bool sb_takes(int Atype, long m, long k, long n, unsigned flags) {
+    if ((flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN)) || !lfamd_gemm_sb_ok(Atype, k, n))
         return false;
-    if (!lfamd_gemm_sb_ok(Atype, k, n))
-        return false;
-    static const bool force = getenv("LFAMD_SB_FORCE") != nullptr; // development: threshold sweeps
-    if (force)
-        return true;
     const long tiles_per_cu = ((m + 31) / 32 + 255) / 256;
     if (Atype == LFAMD_TYPE_Q4_K && n <= 8) // the int8 body
         return k > 8192 || tiles_per_cu > 4 ? n >= 2 : tiles_per_cu > 1 ? n >= 3 : n >= 4;
@@ -432,146 +404,164 @@ static bool use_gemm_sb(int Atype, long n, unsigned flags, long k, long m) {
 }
 
 // Q4_K batches on the int8 matrix cores (gemm_i8.hip): exact integer dots; every launch whose 128 x 64 tiles fill at least half
-// the CUs, unless a testing flag asks for one of the f16 bodies
-static bool use_gemm_i8(int Atype, long n, unsigned flags, long k, long row_blocks) {
+// the CUs (row_blocks: of all the matrices of the launch), unless a testing flag asks for one of the f16 bodies
+static bool i8_takes(int Atype, long k, long n, unsigned flags, long row_blocks) {
     if (flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN | LFAMD_FLAG_PRECISE))
         return false;
     return n > 8 && k > 0 && k % 256 == 0 && lfamd_gemm_i8_ok(Atype, row_blocks, n);
 }
 
-static bool use_gemv(int Atype, long n, unsigned flags, long k) {
-    if (flags & LFAMD_FLAG_FORCE_GENERIC)
-        return false;
-    return n <= 8 && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K ||
-                      Atype == LFAMD_TYPE_Q8_0 || Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K ||
-                      Atype == LFAMD_TYPE_IQ4_XS || packed40(Atype, k) || packed_pcl(Atype, k));
-}
+// The bodies of one lfamd_mul_mat call and their arithmetic (exact: integer block dots or 16-bit products with f32 sums, what
+// lfamd_mul_mat_is_exact calls 1; f16-rounded: one f16 rounding per operand, <= 1e-3).
+enum class mm_body {
+    gemv,       // n <= 8, packed weights: the decode GEMVs (gemv.hip); exact (Q8_0: bit-exact)
+    gemv_float, // n <= 8, F32 / F16 / BF16 (gemv_float.hip); exact.  Operands that are not 16-byte aligned: generic
+    sb,         // 2 .. 32 tokens of Q4_K / Q5_K / Q6_K (gemm_sb.hip); exact
+    i8,         // Q4_K batches on the int8 matrix cores (gemm_i8.hip); exact; reads LFAMD_TYPE_STAGED_Q8K
+    kq_narrow,  // K-quant batches, the 128 x 64 split-K body on integer codes (gemm_mfma.hip); exact, Q6_K f16-rounded
+    wide,       // K-quant batches, the 128 x 128 family (gemm_wide.hip).  scaled: f16-rounded, reads LFAMD_TYPE_STAGED_SCALED;
+                // else integer codes: exact, Q6_K f16-rounded
+    q40_wide,   // P40 Q4_0 batches on Q8_0-quantised activations, the 128 x 128 body; exact
+    canon,      // Q2_K / Q3_K / IQ4_XS batches: canonical image expanded per call, the 128 x 128 body; exact, IQ4_XS f16-rounded
+    canon32,    // PCL Q4_1 / Q5_0 / Q5_1 batches, the 128 x 128 body; exact
+    float_lt,   // F16 / BF16 batches on the vendor GEMM (LFAMD_USE_BLASLT=1); exact.  Declined or unaligned: float_lf / float_wide
+    float_lf,   // F16 / BF16 batches, the loader-wave body on the RAW rows (gemm_lf.hip); exact.  Unaligned weights: float_wide
+    float_wide, // F16 / BF16 batches that the testing flags or a 32-bit byte offset keep off gemm_lf, the 128 x 128 body; exact
+    q80_lt,     // Q8_0 batches on the vendor f16 GEMM (second resident image); f16-rounded.  Declined: q80_exact
+    q80_lf,     // Q8_0 batches, rows of whole 128-weight quads: the f16 MFMA body on the P80 image (gemm_lf.hip); f16-rounded
+    q80_exact,  // Q8_0 batches, the bit-exact kernel (gemm_q80.hip)
+    generic,    // every other call (generic.hip); exact.  f32 activations of quantised weights are quantised into the workspace first
+    refused,    // LFAMD_FLAG_FORCE_GENERIC on packed weights: LFAMD_ERR_UNSUPPORTED (is_exact answers 1, the flag's promise)
+};
+struct mm_plan {
+    mm_body body;
+    bool scaled;      // wide: the activations are staged scaled (prep mode 2) for the scaled-operand loader-wave bodies
+    bool exact;       // lfamd_mul_mat_is_exact
+    size_t workspace; // bytes lfamd_mul_mat asks for (generic: only when it quantises f32 activations)
+};
 
-static bool gemv_quantise_separately(int Atype, long m) {
-    (void)Atype;
-    (void)m;
-    return false; // persistent GEMV work-groups stage the activations once each: fused is always cheaper
+static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
+    const unsigned forced = flags & (LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN); // (a module body, by name)
+    const bool f16_q80 = !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT));
+    mm_plan p = {mm_body::generic, false, true, 0};
+    if (flags & LFAMD_FLAG_FORCE_GENERIC)
+        p.body = packed(Atype, k) ? mm_body::refused : mm_body::generic;
+    else if (sb_takes(Atype, m, k, n, flags))
+        p.body = mm_body::sb;
+    else if (n > 8 && (kquant(Atype) || packed40(Atype, k))) {
+        if (i8_takes(Atype, k, n, flags, (m + 127) / 128))
+            p.body = mm_body::i8;
+        else if (Atype == LFAMD_TYPE_Q4_0)
+            p.body = mm_body::q40_wide;
+        else {
+            // Two families: 128 x 128 / 256 x 128 tiles with K streamed once (gemm_wide.hip and its loader-wave / K-split-wave /
+            // row-split descendants), and the 128 x 64 split-K body (gemm_mfma.hip, exact codes) for grids below 192 tiles.  The
+            // wide family runs scaled operands unless the caller wants the integer codes (LFAMD_FLAG_PRECISE / _GEMM_PLAIN); its
+            // 128 x 64 tile replaces the split-K body then at every grid.
+            const long tiles128 = ((m + 127) / 128) * (long)(align_up((size_t)n, 128) / 128);
+            const bool can_scale = !(flags & LFAMD_FLAG_PRECISE) && lfamd_gemm_wide_scaled_ok(Atype, (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0);
+            const bool narrow = (flags & LFAMD_FLAG_GEMM_NARROW) || (!(flags & LFAMD_FLAG_GEMM_WIDE) && tiles128 < 192 && !can_scale);
+            p.body = narrow ? mm_body::kq_narrow : mm_body::wide;
+            p.scaled = !narrow && can_scale;
+            p.exact = !p.scaled && Atype != LFAMD_TYPE_Q6_K; // (both Q6_K batch bodies round sc * (q - 32) above 2048)
+        }
+    } else if (n > 8 && k % 256 == 0 && (Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16))
+        p.body = forced                  ? mm_body::float_wide
+                 : lfamd_blaslt_ok()     ? mm_body::float_lt
+                 : float_lf_fits(Atype, m, k) ? mm_body::float_lf
+                                         : mm_body::float_wide;
+    else if (n <= 8 && float_type(Atype) && lfamd_gemv_float_ok(Atype, k, n))
+        p.body = mm_body::gemv_float;
+    else if (n > 8 && packed_pcl(Atype, k))
+        p.body = mm_body::canon32;
+    else if (n > 8 && (Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K || Atype == LFAMD_TYPE_IQ4_XS)) {
+        p.body = mm_body::canon;
+        p.exact = Atype != LFAMD_TYPE_IQ4_XS; // (the canonical image rounds |sc * kvalue| above 2048 to f16; Q2_K / Q3_K: |sc * q| <= 128)
+    } else if (n > 8 && Atype == LFAMD_TYPE_Q8_0) {
+        p.body = f16_q80 && k % 32 == 0 && lfamd_blaslt_ok()     ? mm_body::q80_lt
+                 : f16_q80 && k % 128 == 0 && !lfamd_blaslt_ok() ? mm_body::q80_lf
+                                                                 : mm_body::q80_exact;
+        p.exact = p.body == mm_body::q80_exact;
+    } else if (n <= 8 && packed(Atype, k))
+        p.body = mm_body::gemv;
+
+    const size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
+    switch (p.body) {
+    case mm_body::sb:
+        p.workspace = align_up(lfamd_gemm_sb_workspace(k), 256);
+        break;
+    case mm_body::i8: // (the staging layout every K-quant batch body shares, then partial tiles of a K-split launch)
+    case mm_body::kq_narrow:
+    case mm_body::wide:
+        p.workspace = gemm_act_ws(k, n) + lfamd_gemm_lw_ksplit_bytes(m, n);
+        break;
+    case mm_body::q40_wide:
+        p.workspace = gemm_act_ws(k, n);
+        break;
+    case mm_body::canon: // (+ the canonical image of the matrix, rebuilt from the compact one per call)
+        p.workspace = gemm_act_ws(k, n) + align_up(Atype == LFAMD_TYPE_IQ4_XS ? lfamd_wprep8_bytes(m, k) : lfamd_wprep16_bytes(m, k), 256);
+        break;
+    case mm_body::canon32: // Xh, d8T [nb*8][n_pad], sT [nb*8][n_pad]
+        p.workspace = align_up(n_pad * (size_t)k * 2, 256) + 2 * align_up(nb * 8 * n_pad * 4, 256);
+        break;
+    case mm_body::float_lt: // (each one may fall back on the others)
+    case mm_body::float_lf:
+    case mm_body::float_wide: {
+        const size_t own = align_up(n_pad * (size_t)k * 2, 256), lt = lfamd_blaslt_ok() ? gemm_lt_ws(k, n) : 0;
+        p.workspace = own > lt ? own : lt;
+        break;
+    }
+    case mm_body::q80_lt:
+        p.workspace = gemm_lt_ws(k, n);
+        break;
+    case mm_body::q80_lf:
+        p.workspace = align_up(lfamd_gemm_lf_workspace(k, n), 256);
+        break;
+    case mm_body::q80_exact:
+        p.workspace = align_up(lfamd_gemm_q80_workspace(k, n), 256);
+        break;
+    case mm_body::generic:
+        p.workspace = float_type(Atype) ? 0 : align_up((size_t)n * lfamd_row_size(lfamd_vec_dot_type(Atype), k), 256);
+        break;
+    default:
+        break;
+    }
+    return p;
 }
 
 int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags) {
     if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
-    if (flags & LFAMD_FLAG_FORCE_GENERIC) // the generic kernels: integer block dots at every n (packed types refuse the flag)
-        return 1;
-    if (n <= 8) // the GEMVs (Q8_0: bit-exact)
-        return 1;
-    if (Atype == LFAMD_TYPE_F32 || Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16)
-        return 1; // activations in (or rounded from F32 to) the weight's own type, as the reference's vec_dot_type; exact f32 products
-    if (Atype == LFAMD_TYPE_Q8_0)
-        return use_gemm_q80_lt(Atype, n, flags, k) || use_gemm_q80_lf(Atype, n, flags, k) ? 0 : 1;
-    if (Atype == LFAMD_TYPE_IQ4_XS) // the canonical image rounds |sc * kvalue| above 2048 to f16
-        return use_gemm_canon(Atype, n, flags) ? 0 : 1;
-    if (Atype != LFAMD_TYPE_Q4_K && Atype != LFAMD_TYPE_Q5_K && Atype != LFAMD_TYPE_Q6_K)
-        return 1; // Q2_K / Q3_K canonical image (|sc * q| <= 128), P40 / PCL legacy bodies: integer codes, f32 scales
-    if (use_gemm_sb(Atype, n, flags, k, m))
-        return 1;
-    if (Atype == LFAMD_TYPE_Q6_K)
-        return 0; // (both batch bodies round sc * (q - 32) above 2048)
-    if (flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_PLAIN))
-        return 1;
-    return use_gemm_i8(Atype, n, flags, k, (m + 127) / 128) ? 1 : (lfamd_gemm_wide_scaled_ok(Atype, 0) ? 0 : 1);
-}
-
-// Which body a K-quant batch runs when it is not the int8 one.  Two families: 128 x 128 / 256 x 128 tiles with K streamed once
-// (gemm_wide.hip and its loader-wave / K-split-wave / row-split descendants) when that grid fills the 256 CUs; the 128 x 64 split-K body
-// (gemm_mfma.hip, exact codes) for smaller grids; LFAMD_GEMM_BODY=narrow|wide forces one.  The wide family runs scaled operands (one
-// f16 rounding each, ~1e-4 relative) unless the caller wants the exact integer-code arithmetic (LFAMD_FLAG_PRECISE); it has a 128 x 64
-// tile for the grids the 128 x 128 tile cannot fill, so it also replaces the split-K body down to LW_MIN_TILES.  Returns `scaled`.
-static bool gemm_body_choice(int Atype, long m, long n, unsigned flags, bool &narrow) {
-    static const char *body = getenv("LFAMD_GEMM_BODY");
-    const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
-    const long tiles128 = ((m + 127) / 128) * (long)(align_up((size_t)n, 128) / 128);
-    const int can_scale = !(flags & LFAMD_FLAG_PRECISE) && lfamd_gemm_wide_scaled_ok(Atype, plain);
-    narrow = (flags & LFAMD_FLAG_GEMM_NARROW) ? true
-             : (flags & LFAMD_FLAG_GEMM_WIDE) ? false
-             : body                           ? body[0] == 'n'
-                                              : (tiles128 < 192 && !(can_scale && tiles128 >= LW_MIN_TILES));
-    return !narrow && can_scale;
+    return plan_mul_mat(Atype, m, k, n, flags).exact ? 1 : 0;
 }
 
 // Does a call accept the scaled-operand staged image a fused producer wrote (LFAMD_TYPE_STAGED_SCALED)?  The K-quant batches whose
 // body reads it: what lfamd_mul_mat would stage with prep_scaled_kernel itself.
 int lfamd_mul_mat_takes_staged_scaled(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0 || Atype == LFAMD_TYPE_Q4_0)
+    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
-    bool narrow;
-    return !(flags & LFAMD_FLAG_FORCE_GENERIC) && !use_gemm_sb(Atype, n, flags, k, m) && use_gemm(Atype, n, flags, k) &&
-                   !use_gemm_i8(Atype, n, flags, k, (m + 127) / 128) && gemm_body_choice(Atype, m, n, flags, narrow)
-               ? 1
-               : 0;
-}
-
-struct scaled_image_ptrs {
-    const void *Xh, *d8T, *Xm;
-    size_t n_pad;
-};
-static scaled_image_ptrs scaled_image_of(const void *image, long k, long n) {
-    scaled_image_ptrs p;
-    p.n_pad = align_up((size_t)n, 128);
-    const size_t nb = (size_t)(k / 256);
-    p.Xh = image;
-    p.d8T = (const uint8_t *)image + align_up(p.n_pad * (size_t)k * 2, 256);
-    p.Xm = (const uint8_t *)p.d8T + align_up(nb * p.n_pad * 4, 256);
-    return p;
-}
-
-// sibling matrices of one type on one launch of the int8 body: their row blocks together must make a grid it takes
-static bool multi_i8_ok(int Atype, int count, const long *m, const long *ldc, long k, long n, unsigned flags) {
-    long rbs = 0;
-    for (int j = 0; j < count; j++) {
-        if (m[j] < 0 || ldc[j] < m[j])
-            return false;
-        rbs += (m[j] + 127) / 128;
-    }
-    return rbs > 0 && use_gemm(Atype, n, flags, k) && use_gemm_i8(Atype, n, flags, k, rbs);
+    const mm_plan p = plan_mul_mat(Atype, m, k, n, flags);
+    return p.body == mm_body::wide && p.scaled ? 1 : 0;
 }
 
 // Does a call accept the staged image a fused producer wrote (LFAMD_TYPE_STAGED_Q8K)?  Exactly the calls that run the int8 body.
 int lfamd_mul_mat_takes_staged(int Atype, long m, long k, long n, unsigned flags) {
     if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
-    return !use_gemm_sb(Atype, n, flags, k, m) && use_gemm(Atype, n, flags, k) && use_gemm_i8(Atype, n, flags, k, (m + 127) / 128) ? 1 : 0;
+    return plan_mul_mat(Atype, m, k, n, flags).body == mm_body::i8 ? 1 : 0;
 }
 
-static size_t mul_mat_workspace_base(int Atype, long m, long k, long n) {
-    if (use_gemv(Atype, n, 0, k) && gemv_quantise_separately(Atype, m))
-        return align_up((size_t)n * lfamd_row_size(lfamd_vec_dot_type(Atype), k), 256);
-    if (use_gemm(Atype, n, 0, k)) {
-        size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-        return align_up(n_pad * (size_t)k * 2, 256) + align_up(nb * n_pad * 4, 256) + align_up(n_pad * nb * 32, 256) +
-               (Atype == LFAMD_TYPE_Q4_0 ? 0 : lfamd_gemm_lw_ksplit_bytes(m, n)); // partial tiles of a K-split launch
-    }
-    if (Atype == LFAMD_TYPE_Q8_0 && n > 8) { // (either body may be asked for through the flags: the largest)
-        const size_t exact = align_up(lfamd_gemm_q80_workspace(k, n), 256);
-        const size_t mfma = use_gemm_q80_lt(Atype, n, 0, k) ? gemm_lt_ws(k, n) : k % 128 == 0 ? align_up(lfamd_gemm_lf_workspace(k, n), 256) : 0;
-        return exact > mfma ? exact : mfma;
-    }
-    if (use_gemm_float(Atype, n, 0, k)) {
-        const size_t own = align_up(align_up((size_t)n, 128) * (size_t)k * 2, 256);
-        const size_t lt = lfamd_blaslt_ok() ? gemm_lt_ws(k, n) : 0;
-        return own > lt ? own : lt;
-    }
-    if (use_gemm_canon(Atype, n, 0)) // (+ the canonical image of a Q2_K / Q3_K matrix, rebuilt from the compact one per call)
-        return gemm_act_ws(k, n) + align_up(Atype == LFAMD_TYPE_IQ4_XS ? lfamd_wprep8_bytes(m, k) : lfamd_wprep16_bytes(m, k), 256);
-    if (use_gemm_canon32(Atype, n, 0, k)) { // Xh, d8T [nb*8][n_pad], sT [nb*8][n_pad], image
-        size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-        return align_up(n_pad * (size_t)k * 2, 256) + 2 * align_up(nb * 8 * n_pad * 4, 256);
-    }
-    if (use_gemv(Atype, n, 0, k) || !type_known(Atype) || lfamd_blck_size(Atype) == 1)
-        return 0;
-    // generic kernels given f32 activations quantise them into the workspace first
-    return align_up((size_t)n * lfamd_row_size(lfamd_vec_dot_type(Atype), k), 256);
-}
-
+// The largest workspace of the bodies this call can run: the default one and any a testing flag can force.
 size_t lfamd_mul_mat_workspace(int Atype, long m, long k, long n) {
-    const size_t base = mul_mat_workspace_base(Atype, m, k, n); // (the body a testing flag may force)
-    const size_t sb = use_gemm_sb(Atype, n, 0, k, m) ? align_up(lfamd_gemm_sb_workspace(k), 256) : 0;
-    return base > sb ? base : sb;
+    if (!type_known(Atype))
+        return 0;
+    size_t best = 0;
+    for (unsigned f : {0u, (unsigned)LFAMD_FLAG_PRECISE, (unsigned)LFAMD_FLAG_Q80_EXACT, (unsigned)LFAMD_FLAG_GEMM_NARROW,
+                       (unsigned)LFAMD_FLAG_GEMM_WIDE, (unsigned)LFAMD_FLAG_GEMM_PLAIN}) {
+        const size_t w = plan_mul_mat(Atype, m, k, n, f).workspace;
+        best = w > best ? w : best;
+    }
+    return best;
 }
 
 // The largest workspace any batch of 1 .. n rows can ask for (which body serves a batch depends on n, so the size is not monotonic
@@ -593,157 +583,119 @@ size_t lfamd_mul_mat_workspace_upto(int Atype, long m, long k, long n) {
     return best;
 }
 
-int lfamd_mul_mat(int Atype, const void *d_A, long m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n,
-                  float *d_C, long ldc, void *d_ws, size_t ws_bytes, unsigned flags, void *stream) {
-    (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
-    const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
+struct scaled_image_ptrs {
+    const void *Xh, *d8T, *Xm;
+    size_t n_pad;
+};
+static scaled_image_ptrs scaled_image_of(const void *image, long k, long n) {
+    scaled_image_ptrs p;
+    p.n_pad = align_up((size_t)n, 128);
+    const size_t nb = (size_t)(k / 256);
+    p.Xh = image;
+    p.d8T = (const uint8_t *)image + align_up(p.n_pad * (size_t)k * 2, 256);
+    p.Xm = (const uint8_t *)p.d8T + align_up(nb * p.n_pad * 4, 256);
+    return p;
+}
+
+static bool aligned16(const void *p) {
+    return ((uintptr_t)p & 15) == 0;
+}
+
+// Everything lfamd_mul_mat checks before its first launch: LFAMD_OK and the plan, or the error the call returns.
+static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n, long ldc, const void *d_ws,
+                         size_t ws_bytes, unsigned flags, mm_plan &p) {
     if (!type_known(Atype))
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: unsupported weight type%s", "");
     if (m < 0 || n < 0 || k < 0 || ldc < m || k % lfamd_blck_size(Atype))
         return fail(LFAMD_ERR_INVALID, "mul_mat: bad shape%s", "");
-    if (Btype == LFAMD_TYPE_STAGED_Q8K) { // a fused producer wrote the int8 body's staged image: the GEMM alone, no staging launch
-        if (m == 0 || n == 0)
-            return LFAMD_OK;
-        if (!lfamd_mul_mat_takes_staged(Atype, m, k, n, flags))
+    const bool staged = Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED;
+    if (!staged) {
+        if (float_type(Atype)) {
+            if (!(Btype == LFAMD_TYPE_F32 || Btype == Atype))
+                return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: float weights need F32 or same-type activations%s", "");
+        } else if (Btype != lfamd_vec_dot_type(Atype) && Btype != LFAMD_TYPE_F32) {
+            // f32 activations (the GGML_OP_MUL_MAT boundary) are quantised on the device to the vec_dot type
+            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: activations must be F32 or the weight type's vec_dot format%s", "");
+        }
+        if (b_row_bytes < lfamd_row_size(Btype, k))
+            return fail(LFAMD_ERR_INVALID, "mul_mat: activation row stride too small%s", "");
+    }
+    if (m == 0 || n == 0)
+        return LFAMD_OK;
+    p = plan_mul_mat(Atype, m, k, n, flags);
+    size_t need = p.workspace;
+    bool uses_ws = !(p.body == mm_body::gemv || p.body == mm_body::gemv_float || p.body == mm_body::refused ||
+                     (p.body == mm_body::generic && (float_type(Atype) || Btype != LFAMD_TYPE_F32)));
+    if (Btype == LFAMD_TYPE_STAGED_Q8K) { // a fused producer wrote the int8 body's staged image
+        if (p.body != mm_body::i8 || !d_B || !aligned16(d_B))
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run the int8 batch body (lfamd_mul_mat_takes_staged)%s", "");
-        const void *A1 = d_A;
-        HIPCHK(lfamd_launch_gemm_i8_staged(1, &A1, &m, k, d_B, n, &d_C, &ldc, (hipStream_t)stream), "gemm_i8 (staged input)");
+        uses_ws = false;
+    } else if (Btype == LFAMD_TYPE_STAGED_SCALED) { // a fused producer wrote the scaled-operand bodies' staged image
+        if (p.body != mm_body::wide || !p.scaled || !d_B || !aligned16(d_B))
+            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run a scaled-operand batch body (lfamd_mul_mat_takes_staged_scaled)%s", "");
+        need = lfamd_gemm_lw_ksplit_bytes(m, n); // partial tiles of a K-split launch: the only workspace left
+        uses_ws = need != 0;
+    }
+    if (p.body == mm_body::refused)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: FORCE_GENERIC needs RAW-layout weights; this type is packed%s", "");
+    if (uses_ws && (ws_bytes < need || !d_ws))
+        return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
+    return LFAMD_OK;
+}
+
+static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, long k, int Btype, const void *d_B, size_t b_row_bytes,
+                          long n, float *d_C, long ldc, void *d_ws, size_t ws_bytes, unsigned flags, hipStream_t s) {
+    const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
+    const int vregs32 = (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0, precise = (flags & LFAMD_FLAG_PRECISE) ? 1 : 0;
+    const int vdt = lfamd_vec_dot_type(Atype);
+    const size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
+    uint8_t *ws = (uint8_t *)d_ws; // the staging layout of the K-quant batch bodies: Xh, d8T, Xm
+    void *Xh = ws, *d8T = ws + align_up(n_pad * (size_t)k * 2, 256), *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
+    if (Btype == LFAMD_TYPE_STAGED_Q8K) { // the GEMM alone, no staging launch
+        HIPCHK(lfamd_launch_gemm_i8_staged(1, &d_A, &m, k, d_B, n, &d_C, &ldc, s), "gemm_i8 (staged input)");
         return LFAMD_OK;
     }
-    if (Btype == LFAMD_TYPE_STAGED_SCALED) { // a fused producer wrote the scaled-operand bodies' staged image
-        if (m == 0 || n == 0)
-            return LFAMD_OK;
-        if (!lfamd_mul_mat_takes_staged_scaled(Atype, m, k, n, flags) || !d_B || ((uintptr_t)d_B & 15))
-            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run a scaled-operand batch body (lfamd_mul_mat_takes_staged_scaled)%s", "");
-        const size_t part = lfamd_gemm_lw_ksplit_bytes(m, n); // partial tiles of a K-split launch: the only workspace left
-        if (part && (ws_bytes < part || !d_ws))
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
+    if (Btype == LFAMD_TYPE_STAGED_SCALED) {
         const scaled_image_ptrs im = scaled_image_of(d_B, k, n);
-        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, im.Xh, im.d8T, im.Xm, n, (long)im.n_pad, d_C, ldc, plain | 2, d_ws, ws_bytes, (hipStream_t)stream),
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, im.Xh, im.d8T, im.Xm, n, (long)im.n_pad, d_C, ldc, plain | 2, d_ws, ws_bytes, s),
                "gemm_wide (staged input)");
         return LFAMD_OK;
     }
-    const int vdt = lfamd_vec_dot_type(Atype);
-    const bool float_a = Atype == LFAMD_TYPE_F32 || Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16;
-    if (float_a) {
-        if (!(Btype == LFAMD_TYPE_F32 || Btype == Atype))
-            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: float weights need F32 or same-type activations%s", "");
-    } else if (Btype != vdt && Btype != LFAMD_TYPE_F32) {
-        // f32 activations (the GGML_OP_MUL_MAT boundary) are quantised on the device to vdt
-        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: activations must be F32 or the weight type's vec_dot format%s", "");
-    }
-    if (b_row_bytes < lfamd_row_size(Btype, k))
-        return fail(LFAMD_ERR_INVALID, "mul_mat: activation row stride too small%s", "");
-    if (m == 0 || n == 0)
-        return LFAMD_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const int vregs32 = (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0, precise = (flags & LFAMD_FLAG_PRECISE) ? 1 : 0;
-
-    if (use_gemm_sb(Atype, n, flags, k, m)) { // a handful of tokens: weights streamed once, MFMA tile of 32 token slots (gemm_sb.hip)
-        if (ws_bytes < align_up(lfamd_gemm_sb_workspace(k), 256) || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
+    switch (p.body) {
+    case mm_body::sb: // a handful of tokens: weights streamed once, MFMA tile of 32 token slots
         HIPCHK(lfamd_launch_gemm_sb(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, 0, s), "gemm_sb");
         return LFAMD_OK;
-    }
-    if (use_gemm(Atype, n, flags, k)) {
-        size_t need = lfamd_mul_mat_workspace(Atype, m, k, n);
-        if (ws_bytes < need || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        if (use_gemm_i8(Atype, n, flags, k, (m + 127) / 128) && (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K)) {
-            const void *A1 = d_A;
-            HIPCHK(lfamd_launch_gemm_i8(1, &A1, &m, k, Btype, d_B, b_row_bytes, n, &d_C, &ldc, d_ws, nullptr, s), "gemm_i8");
-            return LFAMD_OK;
-        }
-        size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-        uint8_t *ws = (uint8_t *)d_ws;
-        void *Xh = ws;
-        void *d8T = ws + align_up(n_pad * (size_t)k * 2, 256);
-        void *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
-        if (Atype == LFAMD_TYPE_Q4_0) { // Q8_0-quantised activations, eight scales per 256 (they take the Xm area too)
-            HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, nullptr, s), "prep80");
-            HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, nullptr, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
-            return LFAMD_OK;
-        }
-        // two bodies: 128 x 128 tiles, K streamed once (gemm_wide.hip) when that grid fills the 256 CUs; the
-        // 128 x 64 split-K body (gemm_mfma.hip) for smaller grids.  LFAMD_GEMM_BODY=narrow|wide forces one.
-        bool narrow;
-        const int scaled = gemm_body_choice(Atype, m, n, flags, narrow) ? 1 : 0;
+    case mm_body::i8:
+        HIPCHK(lfamd_launch_gemm_i8(1, &d_A, &m, k, Btype, d_B, b_row_bytes, n, &d_C, &ldc, d_ws, nullptr, s), "gemm_i8");
+        return LFAMD_OK;
+    case mm_body::q40_wide: // Q8_0-quantised activations, eight scales per 256 (they take the Xm area too)
+        HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, nullptr, s), "prep80");
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, nullptr, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
+        return LFAMD_OK;
+    case mm_body::kq_narrow:
+    case mm_body::wide: {
+        const int mode = p.scaled ? 2 : 0;
         if (Btype == LFAMD_TYPE_F32)
-            HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, scaled ? 2 : 0, nullptr, s), "prep_f32");
+            HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_f32");
         else
-            HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, scaled ? 2 : 0, nullptr, s), "prep_q8k");
-        if (narrow) {
+            HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_q8k");
+        if (p.body == mm_body::kq_narrow) {
             HIPCHK(lfamd_launch_gemm_kq(Atype, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, s), "gemm_kq");
         } else {
-            uint8_t *Pp = (uint8_t *)Xm + align_up(n_pad * nb * 32, 256); // after Xh, d8T, Xm (lfamd_mul_mat_workspace)
-            HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain | (scaled << 1), Pp,
-                                          (size_t)((uint8_t *)d_ws + ws_bytes - Pp), s),
+            uint8_t *Pp = (uint8_t *)Xm + align_up(n_pad * nb * 32, 256); // after Xh, d8T, Xm
+            HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain | mode, Pp, (size_t)(ws + ws_bytes - Pp), s),
                    "gemm_wide");
         }
         return LFAMD_OK;
     }
-    if (use_gemm_float(Atype, n, flags, k)) {
-        size_t need = lfamd_mul_mat_workspace(Atype, m, k, n);
-        if (ws_bytes < need || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        // plain 16-bit float weights: the vendor's GEMM (blaslt.hip) unless a testing flag asks for this module's body
-        if (lfamd_blaslt_ok() && !(flags & (LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_PLAIN)) && ((uintptr_t)d_A & 15) == 0) {
-            uint8_t *ws8 = (uint8_t *)d_ws;
-            const void *X16 = d_B;
-            long ldx = (long)(b_row_bytes / 2);
-            if (Btype == LFAMD_TYPE_F32 || ((uintptr_t)d_B & 15) || (b_row_bytes & 15)) {
-                if (Btype != LFAMD_TYPE_F32)
-                    goto own_float_body; // (unaligned 16-bit rows: rare; the module's kernel takes them)
-                HIPCHK(lfamd_launch_rows_to_16(Atype, d_B, b_row_bytes, n, k, ws8, s), "rows_to_16");
-                X16 = ws8, ldx = k;
-            }
-            uint8_t *ltws = ws8 + align_up((size_t)n * (size_t)k * 2, 256);
-            if (lfamd_blaslt_gemm(Atype, d_A, k, X16, ldx, m, n, k, d_C, ldc, ltws, lfamd_blaslt_workspace(), s) == hipSuccess)
-                return LFAMD_OK;
-            (void)hipGetLastError(); // the library declined this shape: this module's body
-        }
-    own_float_body:
-        size_t n_pad = align_up((size_t)n, 128);
-        HIPCHK(lfamd_launch_prep_float(Atype, Btype, d_B, b_row_bytes, n, (long)n_pad, k, d_ws, s), "prep_float");
-        // default: the loader-wave body on the RAW rows (gemm_lf.hip); the 128 x 128 wide body on request (testing flags), for
-        // unaligned tensors and for matrices beyond a 32-bit byte offset
-        const size_t a_row = lfamd_row_size(Atype, k);
-        if (!(flags & (LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_PLAIN)) && ((uintptr_t)d_A & 15) == 0 &&
-            (size_t)m * a_row < ((size_t)1 << 32)) {
-            HIPCHK(lfamd_launch_gemm_lf_float(Atype, d_A, a_row, m, k, d_ws, n, (long)n_pad, d_C, ldc, s), "gemm_lf (float)");
-            return LFAMD_OK;
-        }
-        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, d_ws, d_ws, d_ws, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
-        return LFAMD_OK;
-    }
-    if (float_a && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && lfamd_gemv_float_ok(Atype, k, n) &&
-        ((uintptr_t)d_A & 15) == 0 && ((uintptr_t)d_B & 15) == 0 && (b_row_bytes & 15) == 0) { // decode on float weights (16-byte loads)
-        HIPCHK(lfamd_launch_gemv_float(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, s), "gemv_float");
-        return LFAMD_OK;
-    }
-    if (use_gemm_canon32(Atype, n, flags, k)) {
-        size_t need = lfamd_mul_mat_workspace(Atype, m, k, n);
-        if (ws_bytes < need || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-        uint8_t *ws = (uint8_t *)d_ws;
-        void *Xh = ws;
-        void *d8T = ws + align_up(n_pad * (size_t)k * 2, 256);
+    case mm_body::canon32: {
         void *sT = (uint8_t *)d8T + align_up(nb * 8 * n_pad * 4, 256);
         const bool q81 = vdt == LFAMD_TYPE_Q8_1;
         HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, q81 ? sT : nullptr, s), "prep80");
         HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, q81 ? sT : nullptr, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
         return LFAMD_OK;
     }
-    if (use_gemm_canon(Atype, n, flags)) {
-        size_t need = lfamd_mul_mat_workspace(Atype, m, k, n);
-        if (ws_bytes < need || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-        uint8_t *ws = (uint8_t *)d_ws;
-        void *Xh = ws;
-        void *d8T = ws + align_up(n_pad * (size_t)k * 2, 256);
-        void *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
+    case mm_body::canon: {
         const int mins16 = Atype == LFAMD_TYPE_Q2_K;
         if (Btype == LFAMD_TYPE_F32)
             HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mins16, nullptr, s), "prep_f32");
@@ -758,63 +710,257 @@ int lfamd_mul_mat(int Atype, const void *d_A, long m, long k, int Btype, const v
         HIPCHK(lfamd_launch_gemm_wide(Atype, img, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
         return LFAMD_OK;
     }
-    if (use_gemm_q80_lt(Atype, n, flags, k)) {
-        if (ws_bytes < gemm_lt_ws(k, n) || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        uint8_t *ws8 = (uint8_t *)d_ws;
+    case mm_body::float_lt: // the vendor's GEMM on plain 16-bit float weights
+        if (aligned16(d_A) && (Btype == LFAMD_TYPE_F32 || (aligned16(d_B) && !(b_row_bytes & 15)))) {
+            const void *X16 = d_B;
+            long ldx = (long)(b_row_bytes / 2);
+            if (Btype == LFAMD_TYPE_F32) {
+                HIPCHK(lfamd_launch_rows_to_16(Atype, d_B, b_row_bytes, n, k, ws, s), "rows_to_16");
+                X16 = ws, ldx = k;
+            }
+            if (lfamd_blaslt_gemm(Atype, d_A, k, X16, ldx, m, n, k, d_C, ldc, ws + align_up((size_t)n * (size_t)k * 2, 256),
+                                  lfamd_blaslt_workspace(), s) == hipSuccess)
+                return LFAMD_OK;
+            (void)hipGetLastError(); // the library declined this shape: this module's body
+        }
+        [[fallthrough]];
+    case mm_body::float_lf:
+    case mm_body::float_wide:
+        HIPCHK(lfamd_launch_prep_float(Atype, Btype, d_B, b_row_bytes, n, (long)n_pad, k, d_ws, s), "prep_float");
+        if (p.body != mm_body::float_wide && aligned16(d_A) && float_lf_fits(Atype, m, k)) {
+            HIPCHK(lfamd_launch_gemm_lf_float(Atype, d_A, lfamd_row_size(Atype, k), m, k, d_ws, n, (long)n_pad, d_C, ldc, s), "gemm_lf (float)");
+            return LFAMD_OK;
+        }
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, d_ws, d_ws, d_ws, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
+        return LFAMD_OK;
+    case mm_body::q80_lt: {
         const void *img = (const uint8_t *)d_A + q80_p80_bytes(m, k); // f16(d * q) rows, built once by lfamd_pack_weights
-        HIPCHK(lfamd_launch_q80_rows_to_f16(Btype, d_B, b_row_bytes, n, k, ws8, s), "q80_rows_to_f16");
-        if (lfamd_blaslt_gemm(LFAMD_TYPE_F16, img, k, ws8, k, m, n, k, d_C, ldc, ws8 + align_up((size_t)n * (size_t)k * 2, 256),
+        HIPCHK(lfamd_launch_q80_rows_to_f16(Btype, d_B, b_row_bytes, n, k, ws, s), "q80_rows_to_f16");
+        if (lfamd_blaslt_gemm(LFAMD_TYPE_F16, img, k, ws, k, m, n, k, d_C, ldc, ws + align_up((size_t)n * (size_t)k * 2, 256),
                               lfamd_blaslt_workspace(), s) == hipSuccess)
             return LFAMD_OK;
         // the library declined this shape or this device: the bit-exact kernel on the resident P80 image (the workspace is sized for
-        // either, mul_mat_workspace_base)
+        // either, lfamd_mul_mat_workspace)
         (void)hipGetLastError();
         if (ws_bytes < align_up(lfamd_gemm_q80_workspace(k, n), 256))
             return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
         HIPCHK(lfamd_launch_gemm_q80(d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, vregs32, precise, s), "gemm_q80 (library declined)");
         return LFAMD_OK;
     }
-    if (use_gemm_q80_lf(Atype, n, flags, k) && (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_0)) {
-        if (ws_bytes < lfamd_gemm_lf_workspace(k, n) || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        const void *A1 = d_A;
-        HIPCHK(lfamd_launch_gemm_lf_q80(1, &A1, &m, k, Btype, d_B, b_row_bytes, n, &d_C, &ldc, d_ws, s), "gemm_lf (Q8_0)");
+    case mm_body::q80_lf:
+        HIPCHK(lfamd_launch_gemm_lf_q80(1, &d_A, &m, k, Btype, d_B, b_row_bytes, n, &d_C, &ldc, d_ws, s), "gemm_lf (Q8_0)");
         return LFAMD_OK;
-    }
-    if (use_gemm_q80(Atype, n, flags, k)) {
-        size_t need = align_up(lfamd_gemm_q80_workspace(k, n), 256);
-        if (ws_bytes < need || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
+    case mm_body::q80_exact:
         HIPCHK(lfamd_launch_gemm_q80(d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, vregs32, precise, s), "gemm_q80");
         return LFAMD_OK;
-    }
-    if (use_gemv(Atype, n, flags, k)) {
-        if (Btype == LFAMD_TYPE_F32 && gemv_quantise_separately(Atype, m)) {
-            // very tall matrices (output.weight): thousands of work-groups would each re-quantise the same
-            // activation vector; quantise it once into the workspace instead
-            size_t qrow = lfamd_row_size(vdt, k), need = align_up((size_t)n * qrow, 256);
-            if (ws_bytes < need || !d_ws)
-                return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-            HIPCHK(lfamd_launch_quantize(vdt, (const float *)d_B, n, k, b_row_bytes, d_ws, qrow, s), "quantize_rows");
-            HIPCHK(lfamd_launch_gemv(Atype, d_A, m, k, vdt, d_ws, qrow, n, d_C, ldc, vregs32, precise, s), "gemv");
-            return LFAMD_OK;
-        }
+    case mm_body::gemv:
         HIPCHK(lfamd_launch_gemv(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, vregs32, precise, s), "gemv");
         return LFAMD_OK;
+    case mm_body::gemv_float: // decode on float weights (16-byte loads)
+        if (aligned16(d_A) && aligned16(d_B) && !(b_row_bytes & 15)) {
+            HIPCHK(lfamd_launch_gemv_float(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, s), "gemv_float");
+            return LFAMD_OK;
+        }
+        [[fallthrough]];
+    case mm_body::generic:
+        if (!float_type(Atype) && Btype == LFAMD_TYPE_F32) {
+            const size_t qrow = lfamd_row_size(vdt, k);
+            HIPCHK(lfamd_launch_quantize(vdt, (const float *)d_B, n, k, b_row_bytes, d_ws, qrow, s), "quantize_rows");
+            HIPCHK(lfamd_launch_generic(Atype, d_A, m, k, vdt, d_ws, qrow, n, d_C, ldc, s), "generic");
+            return LFAMD_OK;
+        }
+        HIPCHK(lfamd_launch_generic(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, s), "generic");
+        return LFAMD_OK;
+    default: // (refused: check_mul_mat returned the error)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: no body for this call%s", "");
     }
-    if (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K || Atype == LFAMD_TYPE_Q8_0 ||
-        Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K || Atype == LFAMD_TYPE_IQ4_XS || packed40(Atype, k) || packed_pcl(Atype, k))
-        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: FORCE_GENERIC needs RAW-layout weights; this type is packed%s", "");
-    if (!float_a && Btype == LFAMD_TYPE_F32) {
-        size_t qrow = lfamd_row_size(vdt, k), need = align_up((size_t)n * qrow, 256);
-        if (ws_bytes < need || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
-        HIPCHK(lfamd_launch_quantize(vdt, (const float *)d_B, n, k, b_row_bytes, d_ws, qrow, s), "quantize_rows");
-        HIPCHK(lfamd_launch_generic(Atype, d_A, m, k, vdt, d_ws, qrow, n, d_C, ldc, s), "generic");
+}
+
+int lfamd_mul_mat(int Atype, const void *d_A, long m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n, float *d_C, long ldc,
+                  void *d_ws, size_t ws_bytes, unsigned flags, void *stream) {
+    (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
+    mm_plan p = {};
+    const int r = check_mul_mat(Atype, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags, p);
+    if (r != LFAMD_OK || m == 0 || n == 0)
+        return r;
+    return launch_mul_mat(p, Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sibling matrices of one type on the same activations (lfamd_mul_mat_multi): one group-level route, decided and checked by
+// check_multi before anything is launched.
+enum class mm_route {
+    none,         // nothing to launch
+    each,         // one lfamd_mul_mat per matrix (every one of them checked first)
+    staged_i8,    // LFAMD_TYPE_STAGED_Q8K: the int8 body over up to four matrices per launch
+    staged_wide,  // LFAMD_TYPE_STAGED_SCALED: the scaled wide body over the concatenated row blocks
+    sb_shared,    // gemm_sb per matrix on activations staged once
+    gemv_multi,   // one fused decode GEMV launch
+    i8_multi,     // the int8 body over the concatenated row blocks
+    wide_multi,   // one staging, the wide body over the concatenated row blocks
+    q80_lf_multi, // one staging, gemm_lf_q80 over the concatenated row blocks
+};
+
+// sibling matrices of one type on one launch of the int8 body: their row blocks together must make a grid it takes
+static bool multi_i8_ok(int Atype, int count, const long *m, const long *ldc, long k, long n, unsigned flags) {
+    long rbs = 0;
+    for (int j = 0; j < count; j++) {
+        if (m[j] < 0 || ldc[j] < m[j])
+            return false;
+        rbs += (m[j] + 127) / 128;
+    }
+    return rbs > 0 && i8_takes(Atype, k, n, flags, rbs);
+}
+
+// 2 .. 4 K-quant siblings whose concatenated row blocks fill the chip with 128 x 128 tiles (or LFAMD_FLAG_GEMM_WIDE asks for it)
+static bool wide_group_ok(int Atype, int count, const long *m, const long *ldc, long k, long n, unsigned flags) {
+    if (count < 2 || count > 4 || n <= 8 || !kquant(Atype) || k <= 0 || k % 256 || (flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_GEMM_NARROW)))
+        return false;
+    long rbs = 0;
+    for (int j = 0; j < count; j++) {
+        if (m[j] < 0 || ldc[j] < m[j])
+            return false;
+        rbs += (m[j] + 127) / 128;
+    }
+    return rbs * (long)(align_up((size_t)n, 128) / 128) >= 192 || (flags & LFAMD_FLAG_GEMM_WIDE);
+}
+
+static bool scaled_ok(int Atype, unsigned flags) { // may the wide body run on scaled operands?
+    return !(flags & LFAMD_FLAG_PRECISE) && lfamd_gemm_wide_scaled_ok(Atype, (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0);
+}
+
+static int check_multi(int Atype, int count, const long *m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n, const long *ldc,
+                       const void *d_ws, size_t ws_bytes, unsigned flags, mm_route &route) {
+    route = mm_route::none;
+    if (count <= 0 || ((Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED) && n == 0))
+        return LFAMD_OK;
+    if (Btype == LFAMD_TYPE_STAGED_Q8K) { // every matrix must take the image
+        if (!(count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))) // (else: each matrix by itself)
+            for (int j = 0; j < count; j++)
+                if (m[j] > 0 && (ldc[j] < m[j] || !lfamd_mul_mat_takes_staged(Atype, m[j], k, n, flags)))
+                    return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: a matrix of this call does not run the int8 batch body%s", "");
+        route = mm_route::staged_i8;
         return LFAMD_OK;
     }
-    HIPCHK(lfamd_launch_generic(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, s), "generic");
+    route = mm_route::each;
+    if (Btype == LFAMD_TYPE_STAGED_SCALED) { // the route the same call takes on f32 rows
+        if (!d_B || !aligned16(d_B))
+            return fail(LFAMD_ERR_INVALID, "mul_mat_multi: the staged image must be 16-byte aligned%s", "");
+        if (count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))
+            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: these matrices run the int8 batch body together (LFAMD_TYPE_STAGED_Q8K)%s", "");
+        if (wide_group_ok(Atype, count, m, ldc, k, n, flags) && scaled_ok(Atype, flags))
+            route = mm_route::staged_wide;
+    } else if (!(count == 1 && sb_takes(Atype, m[0], k, n, flags))) { // (a handful of tokens on one matrix, attn_output / ffn_down: gemm_sb by itself)
+        const bool rows_ok = (Btype == LFAMD_TYPE_F32 || Btype == lfamd_vec_dot_type(Atype)) && b_row_bytes >= lfamd_row_size(Btype, k);
+        // several tokens (6 and more) on sibling matrices that all take the small-batch MFMA kernel (ffn_gate + ffn_up): the
+        // activations are staged once, then one launch per matrix — 14336 x 4096 x 2 at 8 tokens: 39.8 us on the multi-column GEMV,
+        // 32.7 us as two separate calls, less with the shared staging
+        const bool i8_body = Atype == LFAMD_TYPE_Q4_K && n <= 8;
+        bool all_sb = count > 1 && n >= (i8_body ? 4 : 6) && rows_ok;
+        for (int j = 0; j < count && all_sb; j++) // (small siblings — attn_k / attn_v — are faster on the fused GEMV below 8 tokens)
+            all_sb = (m[j] > 8192 || (i8_body && n >= 8)) && ldc[j] >= m[j] && sb_takes(Atype, m[j], k, n, flags);
+        // one fused launch when the GEMV path applies to every matrix
+        bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && packed(Atype, k) && rows_ok && k > 0 &&
+                    k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || k % 256 == 0);
+        for (int j = 0; j < count && gemv; j++)
+            gemv = m[j] >= 0 && ldc[j] >= m[j];
+        bool q80_lf = count > 1 && count <= 4 && Atype == LFAMD_TYPE_Q8_0 && k > 0 && rows_ok &&
+                      plan_mul_mat(Atype, m[0], k, n, flags).body == mm_body::q80_lf;
+        for (int j = 0; j < count && q80_lf; j++)
+            q80_lf = m[j] >= 0 && ldc[j] >= m[j];
+        size_t need = 0;
+        if (all_sb)
+            route = mm_route::sb_shared, need = align_up(lfamd_gemm_sb_workspace(k), 256);
+        else if (gemv)
+            route = n == 0 ? mm_route::none : mm_route::gemv_multi;
+        // Q4_K siblings whose tiles TOGETHER make a grid the int8 body takes (attn_q/k/v of an all-Q4_K layer: 48 row blocks at 512
+        // tokens): one staging, one launch over the concatenated row blocks, exact integer dots (6144 x 4096 x 512: 47.5 us against 56.8)
+        else if (count > 1 && count <= 4 && rows_ok && k > 0 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))
+            route = mm_route::i8_multi, need = lfamd_gemm_i8_workspace(k, n);
+        // K-quant batches: ONE activation prep for all the matrices, and one launch of the 128 x 128 body over their concatenated
+        // row blocks when that grid fills the chip (attn_q/k/v: 48 + 8 + 8 row blocks instead of three launches of which two fill a
+        // quarter of the CUs)
+        else if (rows_ok && wide_group_ok(Atype, count, m, ldc, k, n, flags))
+            route = mm_route::wide_multi, need = gemm_act_ws(k, n);
+        // Q8_0 batches on sibling matrices: one staging of the activations, one launch over the concatenated row blocks
+        else if (q80_lf)
+            route = mm_route::q80_lf_multi, need = lfamd_gemm_lf_workspace(k, n);
+        const bool uses_ws = route == mm_route::sb_shared || route == mm_route::i8_multi || route == mm_route::wide_multi ||
+                             route == mm_route::q80_lf_multi;
+        if (uses_ws && (ws_bytes < need || !d_ws))
+            return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
+    }
+    if (route == mm_route::each) // one call per matrix: each must pass lfamd_mul_mat's checks before the first is launched
+        for (int j = 0; j < count; j++) {
+            mm_plan p = {};
+            const int r = check_mul_mat(Atype, m[j], k, Btype, d_B, b_row_bytes, n, ldc[j], d_ws, ws_bytes, flags, p);
+            if (r != LFAMD_OK)
+                return r;
+        }
+    return LFAMD_OK;
+}
+
+int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long *m, long k, int Btype, const void *d_B,
+                        size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
+                        unsigned flags, void *stream) {
+    (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
+    mm_route route;
+    const int r = check_multi(Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags, route);
+    if (r != LFAMD_OK)
+        return r;
+    hipStream_t s = (hipStream_t)stream;
+    const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
+    const size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
+    switch (route) {
+    case mm_route::none:
+        return LFAMD_OK;
+    case mm_route::each:
+        for (int j = 0; j < count; j++) {
+            const int rj = lfamd_mul_mat(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, ws_bytes, flags, stream);
+            if (rj != LFAMD_OK)
+                return rj;
+        }
+        return LFAMD_OK;
+    case mm_route::staged_i8:
+        for (int j0 = 0; j0 < count; j0 += 4) {
+            const int c = count - j0 < 4 ? count - j0 : 4;
+            HIPCHK(lfamd_launch_gemm_i8_staged(c, d_A + j0, m + j0, k, d_B, n, d_C + j0, ldc + j0, s), "gemm_i8 (staged input, multi)");
+        }
+        return LFAMD_OK;
+    case mm_route::staged_wide: {
+        const scaled_image_ptrs im = scaled_image_of(d_B, k, n);
+        HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, im.Xh, im.d8T, im.Xm, n, (long)im.n_pad, d_C, ldc, plain | 2, nullptr, 0, s),
+               "gemm_wide_multi (staged input)");
+        return LFAMD_OK;
+    }
+    case mm_route::sb_shared:
+        for (int j = 0; j < count; j++)
+            HIPCHK(lfamd_launch_gemm_sb(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, j > 0, s), "gemm_sb (multi)");
+        return LFAMD_OK;
+    case mm_route::gemv_multi:
+        HIPCHK(lfamd_launch_gemv_multi(Atype, count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0,
+                                       (flags & LFAMD_FLAG_PRECISE) ? 1 : 0, s),
+               "gemv_multi");
+        return LFAMD_OK;
+    case mm_route::i8_multi:
+        HIPCHK(lfamd_launch_gemm_i8(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, nullptr, s), "gemm_i8 (multi)");
+        return LFAMD_OK;
+    case mm_route::wide_multi: {
+        uint8_t *ws = (uint8_t *)d_ws;
+        void *Xh = ws, *d8T = ws + align_up(n_pad * (size_t)k * 2, 256), *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
+        const int mode = scaled_ok(Atype, flags) ? 2 : 0;
+        if (Btype == LFAMD_TYPE_F32)
+            HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_f32");
+        else
+            HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_q8k");
+        HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain | mode, nullptr, 0, s),
+               "gemm_wide_multi");
+        return LFAMD_OK;
+    }
+    case mm_route::q80_lf_multi:
+        HIPCHK(lfamd_launch_gemm_lf_q80(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, s), "gemm_lf (Q8_0, multi)");
+        return LFAMD_OK;
+    }
     return LFAMD_OK;
 }
 
@@ -931,162 +1077,20 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
             return LFAMD_OK;
         }
     }
-    for (int j0 = 0; j0 < count;) { // runs of equal types
-        int j1 = j0 + 1;
-        while (j1 < count && Atype[j1] == Atype[j0] && j1 - j0 < 4)
-            j1++;
-        int r = lfamd_mul_mat_multi(Atype[j0], j1 - j0, d_A + j0, m + j0, k, Btype, d_B, b_row_bytes, n, d_C + j0, ldc + j0, d_ws,
-                                    ws_bytes, flags, stream);
-        if (r != LFAMD_OK)
-            return r;
-        j0 = j1;
-    }
-    return LFAMD_OK;
-}
-
-int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long *m, long k, int Btype, const void *d_B,
-                        size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
-                        unsigned flags, void *stream) {
-    (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
-    const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
-    if (count <= 0)
-        return LFAMD_OK;
-    if (Btype == LFAMD_TYPE_STAGED_Q8K) { // sibling matrices on one staged image: every one of them must take it
-        if (n == 0)
-            return LFAMD_OK;
-        if (!(count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))) // (else: each matrix by itself)
-            for (int j = 0; j < count; j++)
-                if (m[j] > 0 && (ldc[j] < m[j] || !lfamd_mul_mat_takes_staged(Atype, m[j], k, n, flags)))
-                    return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: a matrix of this call does not run the int8 batch body%s", "");
-        for (int j0 = 0; j0 < count; j0 += 4) {
-            const int c = count - j0 < 4 ? count - j0 : 4;
-            HIPCHK(lfamd_launch_gemm_i8_staged(c, d_A + j0, m + j0, k, d_B, n, d_C + j0, ldc + j0, (hipStream_t)stream), "gemm_i8 (staged input, multi)");
-        }
-        return LFAMD_OK;
-    }
-    if (Btype == LFAMD_TYPE_STAGED_SCALED) { // sibling matrices on one scaled image: the route the same call takes on f32 rows
-        if (n == 0)
-            return LFAMD_OK;
-        if (!d_B || ((uintptr_t)d_B & 15))
-            return fail(LFAMD_ERR_INVALID, "mul_mat_multi: the staged image must be 16-byte aligned%s", "");
-        if (count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))
-            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: these matrices run the int8 batch body together (LFAMD_TYPE_STAGED_Q8K)%s", "");
-        bool fuse = count > 1 && count <= 4 && use_gemm(Atype, n, flags, k) && Atype != LFAMD_TYPE_Q4_0 && k > 0 && k % 256 == 0 &&
-                    !(flags & (LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_PRECISE | LFAMD_FLAG_FORCE_GENERIC)) && lfamd_gemm_wide_scaled_ok(Atype, plain);
-        long rbs = 0;
-        for (int j = 0; j < count && fuse; j++) {
-            fuse = m[j] >= 0 && ldc[j] >= m[j];
-            rbs += (m[j] + 127) / 128;
-        }
-        const scaled_image_ptrs im = scaled_image_of(d_B, k, n);
-        if (fuse && (rbs * (long)(im.n_pad / 128) >= 192 || (flags & LFAMD_FLAG_GEMM_WIDE))) { // (one launch over the concatenated row blocks)
-            HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, im.Xh, im.d8T, im.Xm, n, (long)im.n_pad, d_C, ldc, plain | 2, nullptr, 0,
-                                                (hipStream_t)stream),
-                   "gemm_wide_multi (staged input)");
-            return LFAMD_OK;
-        }
-        for (int j = 0; j < count; j++) { // one call per matrix: each must take the image itself
-            const int r = lfamd_mul_mat(Atype, d_A[j], m[j], k, Btype, d_B, 0, n, d_C[j], ldc[j], d_ws, ws_bytes, flags, stream);
+    // runs of equal types (up to four matrices each): every run is checked before the first one is launched
+    for (int launch = 0; launch < 2; launch++)
+        for (int j0 = 0; j0 < count;) {
+            int j1 = j0 + 1;
+            while (j1 < count && Atype[j1] == Atype[j0] && j1 - j0 < 4)
+                j1++;
+            mm_route route;
+            const int r = launch ? lfamd_mul_mat_multi(Atype[j0], j1 - j0, d_A + j0, m + j0, k, Btype, d_B, b_row_bytes, n, d_C + j0, ldc + j0,
+                                                       d_ws, ws_bytes, flags, stream)
+                                 : check_multi(Atype[j0], j1 - j0, m + j0, k, Btype, d_B, b_row_bytes, n, ldc + j0, d_ws, ws_bytes, flags, route);
             if (r != LFAMD_OK)
                 return r;
+            j0 = j1;
         }
-        return LFAMD_OK;
-    }
-    if (count == 1 && use_gemm_sb(Atype, n, flags, k, m[0])) // a handful of tokens on one matrix (attn_output, ffn_down): gemm_sb.hip
-        return lfamd_mul_mat(Atype, d_A[0], m[0], k, Btype, d_B, b_row_bytes, n, d_C[0], ldc[0], d_ws, ws_bytes, flags, stream);
-    // several tokens (6 and more) on sibling matrices that all take the small-batch MFMA kernel (ffn_gate + ffn_up): the activations
-    // are staged once, then one launch per matrix — 14336 x 4096 x 2 at 8 tokens: 39.8 us on the multi-column GEMV, 32.7 us as two
-    // separate calls, less with the shared staging
-    const bool i8_body = Atype == LFAMD_TYPE_Q4_K && n <= 8;
-    if (count > 1 && n >= (i8_body ? 4 : 6) && (Btype == LFAMD_TYPE_F32 || Btype == lfamd_vec_dot_type(Atype)) &&
-        b_row_bytes >= lfamd_row_size(Btype, k)) {
-        bool all_sb = true;
-        for (int j = 0; j < count && all_sb; j++) // (small siblings — attn_k / attn_v — are faster on the fused GEMV below 8 tokens)
-            all_sb = (m[j] > 8192 || (i8_body && n >= 8)) && ldc[j] >= m[j] && use_gemm_sb(Atype, n, flags, k, m[j]);
-        if (all_sb) {
-            if (ws_bytes < align_up(lfamd_gemm_sb_workspace(k), 256) || !d_ws)
-                return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
-            for (int j = 0; j < count; j++)
-                HIPCHK(lfamd_launch_gemm_sb(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, j > 0, (hipStream_t)stream),
-                       "gemm_sb (multi)");
-            return LFAMD_OK;
-        }
-    }
-    // one fused launch when the GEMV path applies to every matrix; otherwise one mul_mat per matrix
-    bool fuse = count <= 4 && use_gemv(Atype, n, flags, k) && (Btype == LFAMD_TYPE_F32 || Btype == lfamd_vec_dot_type(Atype)) &&
-                k > 0 && k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || k % 256 == 0) &&
-                b_row_bytes >= lfamd_row_size(Btype, k);
-    for (int j = 0; j < count && fuse; j++)
-        fuse = m[j] >= 0 && ldc[j] >= m[j];
-    if (fuse) {
-        if (n == 0)
-            return LFAMD_OK;
-        HIPCHK(lfamd_launch_gemv_multi(Atype, count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc,
-                                       (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0, (flags & LFAMD_FLAG_PRECISE) ? 1 : 0,
-                                       (hipStream_t)stream),
-               "gemv_multi");
-        return LFAMD_OK;
-    }
-    // Q4_K siblings whose tiles TOGETHER make a grid the int8 body takes (attn_q/k/v of an all-Q4_K layer: 48 row blocks at 512
-    // tokens): one staging, one launch over the concatenated row blocks, exact integer dots (6144 x 4096 x 512: 47.5 us against 56.8)
-    if (count > 1 && count <= 4 && (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && k > 0 && b_row_bytes >= lfamd_row_size(Btype, k) &&
-        multi_i8_ok(Atype, count, m, ldc, k, n, flags)) {
-        if (ws_bytes < lfamd_gemm_i8_workspace(k, n) || !d_ws)
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
-        HIPCHK(lfamd_launch_gemm_i8(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, nullptr, (hipStream_t)stream), "gemm_i8 (multi)");
-        return LFAMD_OK;
-    }
-    // K-quant batches: ONE activation prep for all the matrices, and one launch of the 128 x 128 body over their
-    // concatenated row blocks when that grid fills the chip (attn_q/k/v: 48 + 8 + 8 row blocks instead of three
-    // launches of which two fill a quarter of the CUs)
-    bool gfuse = count > 1 && count <= 4 && use_gemm(Atype, n, flags, k) && Atype != LFAMD_TYPE_Q4_0 && k > 0 && k % 256 == 0 &&
-                 (Btype == LFAMD_TYPE_F32 || Btype == lfamd_vec_dot_type(Atype)) && b_row_bytes >= lfamd_row_size(Btype, k) &&
-                 !(flags & LFAMD_FLAG_GEMM_NARROW);
-    long rbs = 0;
-    for (int j = 0; j < count && gfuse; j++) {
-        gfuse = m[j] >= 0 && ldc[j] >= m[j];
-        rbs += (m[j] + 127) / 128;
-    }
-    if (gfuse) {
-        hipStream_t s = (hipStream_t)stream;
-        size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-        gfuse = rbs * (long)(n_pad / 128) >= 192 || (flags & LFAMD_FLAG_GEMM_WIDE);
-        if (gfuse) {
-            size_t need = align_up(n_pad * (size_t)k * 2, 256) + align_up(nb * n_pad * 4, 256) + align_up(n_pad * nb * 32, 256);
-            if (ws_bytes < need || !d_ws)
-                return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
-            uint8_t *ws = (uint8_t *)d_ws;
-            void *Xh = ws;
-            void *d8T = ws + align_up(n_pad * (size_t)k * 2, 256);
-            void *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
-            const int scaled = (flags & LFAMD_FLAG_PRECISE) ? 0 : lfamd_gemm_wide_scaled_ok(Atype, plain);
-                if (Btype == LFAMD_TYPE_F32)
-                HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, scaled ? 2 : 0, nullptr, s), "prep_f32");
-            else
-                HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, scaled ? 2 : 0, nullptr, s), "prep_q8k");
-            HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain | (scaled << 1), nullptr, 0, s),
-                   "gemm_wide_multi");
-            return LFAMD_OK;
-        }
-    }
-    // Q8_0 batches on sibling matrices: one staging of the activations, one launch over the concatenated row blocks
-    if (count > 1 && count <= 4 && use_gemm_q80_lf(Atype, n, flags, k) && (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_0) && k > 0 &&
-        b_row_bytes >= lfamd_row_size(Btype, k)) {
-        bool ok = true;
-        for (int j = 0; j < count && ok; j++)
-            ok = m[j] >= 0 && ldc[j] >= m[j];
-        if (ok) {
-            if (ws_bytes < lfamd_gemm_lf_workspace(k, n) || !d_ws)
-                return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
-            HIPCHK(lfamd_launch_gemm_lf_q80(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, (hipStream_t)stream), "gemm_lf (Q8_0, multi)");
-            return LFAMD_OK;
-        }
-    }
-    for (int j = 0; j < count; j++) {
-        int r = lfamd_mul_mat(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, ws_bytes, flags, stream);
-        if (r != LFAMD_OK)
-            return r;
-    }
     return LFAMD_OK;
 }
 

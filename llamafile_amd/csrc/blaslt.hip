@@ -62,7 +62,7 @@ void load() {
     // opt-in (round 4): the module's own kernels are the default for every type; LFAMD_USE_BLASLT=1 selects the vendor GEMM for
     // plain 16-bit float weights and Q8_0 batches (a yardstick, and a second resident image for Q8_0: lfamd_packed_size)
     const char *use = getenv("LFAMD_USE_BLASLT");
-    if (!use || atoi(use) == 0 || getenv("LFAMD_NO_BLASLT"))
+    if (!use || atoi(use) == 0)
         return;
     int devices = 0; // (hipblasLtCreate ends the process when there is no device)
     if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) {

@@ -538,12 +538,6 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
     }
 }
 
-// may the 256 x 128 body run this launch?  (LFAMD_GEMM_NO_KR: the loader-wave body's 128 x 128 tile instead — A/B runs)
-bool lfamd_kr_ok(int Atype) {
-    static const bool off = getenv("LFAMD_GEMM_NO_KR") != nullptr;
-    return !off && Atype == LFAMD_TYPE_Q4_K;
-}
-
 // mats as the other launchers fill it (rb_end in 128-row blocks); n_ct = token tiles of 128
 hipError_t lfamd_kr_go(int Atype, const gemm_mats &mats128, int nb, const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
                        int n_ct, hipStream_t s) {

@@ -552,12 +552,6 @@ __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int 
 #endif
 }
 
-// may the K-split-waves body run this launch?  (LFAMD_GEMM_NO_KS: the loader-wave body's 128 x 64 tile instead — A/B runs)
-bool lfamd_ks_ok(int Atype) {
-    static const bool off = getenv("LFAMD_GEMM_NO_KS") != nullptr;
-    return !off && Atype == LFAMD_TYPE_Q4_K;
-}
-
 hipError_t lfamd_ks_go(int Atype, const gemm_mats &mats, int nb, const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
                        int n_rb, int n_ct, hipStream_t s) {
     if (Atype != LFAMD_TYPE_Q4_K || nb < 1)

@@ -545,17 +545,16 @@ __global__ __launch_bounds__(256) void prep_lf_kernel(const uint8_t *__restrict_
 // pieces each measured 3-9 % slower), four computing waves, fragments one K-step ahead.  f32 accumulate on the matrix cores like the reference's fmaf chains.
 #define LFF_X 32768
 #define LFF_SLOT (32768 + 16384)
-template <bool BF, bool M16>
+template <bool BF>
 __global__ __launch_bounds__(512) void gemm_lf_float_kernel(const gemm_mats mats, int nq, size_t a_row_bytes, const uint16_t *__restrict__ Xh,
                                                                       long n, long n_pad, int n_rb, int n_ct) {
 #ifdef LF_CHECK_NQ
     nq = LF_CHECK_NQ;
 #endif
-    constexpr int NT = 2, RING = 3;
+    constexpr int RING = 3;
     constexpr int WP = 8, XP = 4, PIECES = WP + XP; // of a loader and stage
     __shared__ __attribute__((aligned(16))) uint8_t lds[RING * LFF_SLOT];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = lane & 31, h = lane >> 5;
     int rb, ct;
     {
         const int n_wg = n_rb * n_ct;
@@ -635,104 +634,34 @@ __global__ __launch_bounds__(512) void gemm_lf_float_kernel(const gemm_mats mats
 
     const int rw = wave;
     const int rt = rb * 4 + rw;
-    if constexpr (M16) {
-        // The same tile on v_mfma_f32_16x16x32: a K-step is 32 weights, the wave's 32 rows x 64 tokens are 2 x 4 tiles of 16 x 16 —
-        // the same operand bytes, accumulators and MFMA cycles as the 32 x 32 x 16 form; what differs is the clock the chip holds
-        // under it (MI355X_MICROARCH.md, DVFS give-back item 7).  Lane (r16, kq): 16-byte chunk 4 s + kq of row / token r16.
-        const int r16 = lane & 15, kq = lane >> 4;
-        uint32_t aW[4], aX[4]; // K-step s: row tile 0 / token tile 0 (the others: + 4096 per tile of 16)
+    // The same tile on v_mfma_f32_16x16x32: a K-step is 32 weights, the wave's 32 rows x 64 tokens are 2 x 4 tiles of 16 x 16 —
+    // the same operand bytes, accumulators and MFMA cycles as the 32 x 32 x 16 form; what differs is the clock the chip holds
+    // under it (MI355X_MICROARCH.md, DVFS give-back item 7).  Lane (r16, kq): 16-byte chunk 4 s + kq of row / token r16.
+    const int r16 = lane & 15, kq = lane >> 4;
+    uint32_t aW[4], aX[4]; // K-step s: row tile 0 / token tile 0 (the others: + 4096 per tile of 16)
 #pragma unroll
-        for (int sx = 0; sx < 4; sx++) {
-            aW[sx] = lds0 + (uint32_t)((rw * 32 + r16) * 256 + (((4 * sx + kq) ^ r16) << 4));
-            aX[sx] = lds0 + (uint32_t)(LFF_X + r16 * 256 + (((4 * sx + kq) ^ r16) << 4));
-        }
-        float4_t_ ac[4][2];
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int u = 0; u < 2; u++)
-                ac[t][u] = float4_t_{0.0f, 0.0f, 0.0f, 0.0f};
-        asm volatile("s_barrier" ::: "memory"); // stage 0 has landed for everybody
-        u32x4 W2[2][2], X2[2][4];
-#define LFF_READ(BUF, SX, BASE)                                                                                               \
-    do {                                                                                                                      \
-        lf_dsr16<0>(W2[BUF][0], aW[SX] + (BASE));                                                                              \
-        lf_dsr16<4096>(W2[BUF][1], aW[SX] + (BASE));                                                                           \
-        lf_dsr16<0>(X2[BUF][0], aX[SX] + (BASE));                                                                              \
-        lf_dsr16<4096>(X2[BUF][1], aX[SX] + (BASE));                                                                           \
-        lf_dsr16<8192>(X2[BUF][2], aX[SX] + (BASE));                                                                           \
-        lf_dsr16<12288>(X2[BUF][3], aX[SX] + (BASE));                                                                          \
-    } while (0)
-        LFF_READ(0, 0, 0u);
-        typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-        int slot_c = 0;
-        for (int b = 0; b < nq; b++) {
-            const uint32_t so = (uint32_t)(slot_c * LFF_SLOT);
-            slot_c = slot_c + 1 == RING ? 0 : slot_c + 1;
-            const uint32_t so_n = (uint32_t)(slot_c * LFF_SLOT);
-            asm volatile("s_barrier" ::: "memory"); // B1: everybody is done with stage b - 1
-#define LFF_STEP16(S)                                                                                                         \
-    do {                                                                                                                      \
-        if ((S) == 3)                                                                                                         \
-            asm volatile("s_barrier" ::: "memory"); /* B2: stage b + 1 has landed for everybody */                            \
-        LFF_READ(((S) + 1) & 1, ((S) + 1) & 3, (S) == 3 ? so_n : so);                                                          \
-        asm volatile("s_waitcnt lgkmcnt(6)"                                                                                   \
-                     : "+v"(W2[(S)&1][0]), "+v"(W2[(S)&1][1]), "+v"(X2[(S)&1][0]), "+v"(X2[(S)&1][1]), "+v"(X2[(S)&1][2]),      \
-                       "+v"(X2[(S)&1][3]));                                                                                    \
-        _Pragma("unroll") for (int t = 0; t < 4; t++) _Pragma("unroll") for (int u = 0; u < 2; u++) {                            \
-            if constexpr (BF)                                                                                                 \
-                ac[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, X2[(S)&1][t]),                  \
-                                                                   __builtin_bit_cast(bf16x8_t, W2[(S)&1][u]), ac[t][u], 0, 0, 0); \
-            else                                                                                                              \
-                ac[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, X2[(S)&1][t]),                    \
-                                                                  __builtin_bit_cast(half8_t, W2[(S)&1][u]), ac[t][u], 0, 0, 0);  \
-        }                                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                    \
-    } while (0)
-            LFF_STEP16(0);
-            LFF_STEP16(1);
-            LFF_STEP16(2);
-            LFF_STEP16(3);
-#undef LFF_STEP16
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(W2[0][0]), "+v"(W2[0][1]), "+v"(X2[0][0]), "+v"(X2[0][1]), "+v"(X2[0][2]), "+v"(X2[0][3])); // (a stage that does not exist)
-#undef LFF_READ
-        // lane (r16, kq) holds weight row 32 rt + 16 u + r16, register j = token n0 + 16 t + 4 kq + j
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const long row = (long)rt * 32 + 16 * u + r16;
-            if (row < m)
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const long tk = n0 + 16 * t + 4 * kq + j;
-                        if (tk < n)
-                            C[tk * ldc + row] = ac[t][u][j];
-                    }
-        }
-        return;
+    for (int sx = 0; sx < 4; sx++) {
+        aW[sx] = lds0 + (uint32_t)((rw * 32 + r16) * 256 + (((4 * sx + kq) ^ r16) << 4));
+        aX[sx] = lds0 + (uint32_t)(LFF_X + r16 * 256 + (((4 * sx + kq) ^ r16) << 4));
     }
-    uint32_t adW[8], adX[8];
+    float4_t_ ac[4][2];
 #pragma unroll
-    for (int s = 0; s < 8; s++) {
-        adW[s] = lds0 + (uint32_t)((rw * 32 + i) * 256 + (((2 * s + h) ^ (i & 15)) << 4));
-        adX[s] = lds0 + (uint32_t)(LFF_X + i * 256 + (((2 * s + h) ^ (i & 15)) << 4));
-    }
-    float16_t_ acc[NT];
+    for (int t = 0; t < 4; t++)
 #pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int e = 0; e < 16; e++)
-            acc[t][e] = 0.0f;
+        for (int u = 0; u < 2; u++)
+            ac[t][u] = float4_t_{0.0f, 0.0f, 0.0f, 0.0f};
     asm volatile("s_barrier" ::: "memory"); // stage 0 has landed for everybody
-    // fragments ONE K-step ahead: in step s the wave issues W(s + 1), X(s + 1) [from the NEXT slot once s = 7: landed, the barrier at
-    // the top of this stage said so] and waits for step s's: younger are exactly this step's three reads
-    u32x4 WF[2], XF[2][NT];
-    lf_dsr16<0>(WF[0], adW[0]);
-    lf_dsr16<0>(XF[0][0], adX[0]);
-    lf_dsr16<8192>(XF[0][1], adX[0]);
+    u32x4 W2[2][2], X2[2][4];
+#define LFF_READ(BUF, SX, BASE)                                                                                               \
+do {                                                                                                                          \
+    lf_dsr16<0>(W2[BUF][0], aW[SX] + (BASE));                                                                                 \
+    lf_dsr16<4096>(W2[BUF][1], aW[SX] + (BASE));                                                                              \
+    lf_dsr16<0>(X2[BUF][0], aX[SX] + (BASE));                                                                                 \
+    lf_dsr16<4096>(X2[BUF][1], aX[SX] + (BASE));                                                                              \
+    lf_dsr16<8192>(X2[BUF][2], aX[SX] + (BASE));                                                                              \
+    lf_dsr16<12288>(X2[BUF][3], aX[SX] + (BASE));                                                                             \
+} while (0)
+    LFF_READ(0, 0, 0u);
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
     int slot_c = 0;
     for (int b = 0; b < nq; b++) {
@@ -740,45 +669,46 @@ __global__ __launch_bounds__(512) void gemm_lf_float_kernel(const gemm_mats mats
         slot_c = slot_c + 1 == RING ? 0 : slot_c + 1;
         const uint32_t so_n = (uint32_t)(slot_c * LFF_SLOT);
         asm volatile("s_barrier" ::: "memory"); // B1: everybody is done with stage b - 1
-#define LFF_STEP(S)                                                                                                           \
-    do {                                                                                                                      \
-        if ((S) == 7)                                                                                                         \
-            asm volatile("s_barrier" ::: "memory"); /* B2: stage b + 1 has landed for everybody */                            \
-        lf_dsr16<0>(WF[((S) + 1) & 1], adW[((S) + 1) & 7] + ((S) == 7 ? so_n : so));                                            \
-        lf_dsr16<0>(XF[((S) + 1) & 1][0], adX[((S) + 1) & 7] + ((S) == 7 ? so_n : so));                                         \
-        lf_dsr16<8192>(XF[((S) + 1) & 1][1], adX[((S) + 1) & 7] + ((S) == 7 ? so_n : so));                                      \
-        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(WF[(S)&1]), "+v"(XF[(S)&1][0]), "+v"(XF[(S)&1][1]));                          \
-        _Pragma("unroll") for (int t = 0; t < NT; t++) {                                                                       \
-            if constexpr (BF)                                                                                                 \
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, XF[(S)&1][t]),                    \
-                                                                 __builtin_bit_cast(bf16x8_t, WF[(S)&1]), acc[t], 0, 0, 0);     \
-            else                                                                                                              \
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, XF[(S)&1][t]),                      \
-                                                                __builtin_bit_cast(half8_t, WF[(S)&1]), acc[t], 0, 0, 0);       \
-        }                                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                    \
-    } while (0)
-        LFF_STEP(0);
-        LFF_STEP(1);
-        LFF_STEP(2);
-        LFF_STEP(3);
-        LFF_STEP(4);
-        LFF_STEP(5);
-        LFF_STEP(6);
-        LFF_STEP(7);
-#undef LFF_STEP
+#define LFF_STEP16(S)                                                                                                         \
+do {                                                                                                                          \
+    if ((S) == 3)                                                                                                             \
+        asm volatile("s_barrier" ::: "memory"); /* B2: stage b + 1 has landed for everybody */                                \
+    LFF_READ(((S) + 1) & 1, ((S) + 1) & 3, (S) == 3 ? so_n : so);                                                             \
+    asm volatile("s_waitcnt lgkmcnt(6)"                                                                                       \
+                 : "+v"(W2[(S)&1][0]), "+v"(W2[(S)&1][1]), "+v"(X2[(S)&1][0]), "+v"(X2[(S)&1][1]), "+v"(X2[(S)&1][2]),        \
+                   "+v"(X2[(S)&1][3]));                                                                                       \
+    _Pragma("unroll") for (int t = 0; t < 4; t++) _Pragma("unroll") for (int u = 0; u < 2; u++) {                             \
+        if constexpr (BF)                                                                                                     \
+            ac[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, X2[(S)&1][t]),                    \
+                                                               __builtin_bit_cast(bf16x8_t, W2[(S)&1][u]), ac[t][u], 0, 0, 0); \
+        else                                                                                                                  \
+            ac[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, X2[(S)&1][t]),                      \
+                                                              __builtin_bit_cast(half8_t, W2[(S)&1][u]), ac[t][u], 0, 0, 0);  \
+    }                                                                                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                                        \
+} while (0)
+        LFF_STEP16(0);
+        LFF_STEP16(1);
+        LFF_STEP16(2);
+        LFF_STEP16(3);
+#undef LFF_STEP16
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(WF[0]), "+v"(XF[0][0]), "+v"(XF[0][1])); // (reads of a stage that does not exist)
-    if ((long)rt * 32 + i < m) {
-        const long row = (long)rt * 32 + i;
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(W2[0][0]), "+v"(W2[0][1]), "+v"(X2[0][0]), "+v"(X2[0][1]), "+v"(X2[0][2]), "+v"(X2[0][3])); // (a stage that does not exist)
+#undef LFF_READ
+    // lane (r16, kq) holds weight row 32 rt + 16 u + r16, register j = token n0 + 16 t + 4 kq + j
 #pragma unroll
-        for (int t = 0; t < NT; t++)
+    for (int u = 0; u < 2; u++) {
+        const long row = (long)rt * 32 + 16 * u + r16;
+        if (row < m)
 #pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const long tk = n0 + 32 * t + 8 * (e >> 2) + 4 * h + (e & 3);
-                if (tk < n)
-                    C[tk * ldc + row] = acc[t][e];
-            }
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const long tk = n0 + 16 * t + 4 * kq + j;
+                    if (tk < n)
+                        C[tk * ldc + row] = ac[t][u][j];
+                }
     }
 }
 
@@ -797,18 +727,10 @@ extern "C" hipError_t lfamd_launch_gemm_lf_float(int Atype, const void *A, size_
         mats.A[q] = (const uint8_t *)A, mats.C[q] = C, mats.m[q] = q ? 0 : m, mats.ldc[q] = q ? 0 : ldc, mats.rb_end[q] = n_rb;
     const int nq = (int)(k / 128);
     const unsigned grid = (unsigned)(n_rb * n_ct);
-    static const bool m16 = !(getenv("LFAMD_LFF_M16") && atoi(getenv("LFAMD_LFF_M16")) == 0); // (A/B runs: 0 = the 32 x 32 x 16 form)
-    if (Atype == LFAMD_TYPE_BF16) {
-        if (m16)
-            gemm_lf_float_kernel<true, true><<<grid, 512, 0, s>>>(mats, nq, a_row_bytes, (const uint16_t *)Xh, n, n_pad, n_rb, n_ct);
-        else
-            gemm_lf_float_kernel<true, false><<<grid, 512, 0, s>>>(mats, nq, a_row_bytes, (const uint16_t *)Xh, n, n_pad, n_rb, n_ct);
-    } else {
-        if (m16)
-            gemm_lf_float_kernel<false, true><<<grid, 512, 0, s>>>(mats, nq, a_row_bytes, (const uint16_t *)Xh, n, n_pad, n_rb, n_ct);
-        else
-            gemm_lf_float_kernel<false, false><<<grid, 512, 0, s>>>(mats, nq, a_row_bytes, (const uint16_t *)Xh, n, n_pad, n_rb, n_ct);
-    }
+    if (Atype == LFAMD_TYPE_BF16)
+        gemm_lf_float_kernel<true><<<grid, 512, 0, s>>>(mats, nq, a_row_bytes, (const uint16_t *)Xh, n, n_pad, n_rb, n_ct);
+    else
+        gemm_lf_float_kernel<false><<<grid, 512, 0, s>>>(mats, nq, a_row_bytes, (const uint16_t *)Xh, n, n_pad, n_rb, n_ct);
     return hipGetLastError();
 }
 

@@ -839,8 +839,7 @@ size_t lfamd_gemm_sb_workspace(long k) { // Xh, d8T, Xm
 }
 
 bool lfamd_gemm_sb_ok(int Atype, long k, long n) {
-    static const bool off = getenv("LFAMD_NO_SMALL_BATCH") != nullptr;
-    return !off && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K) && k > 0 && k % 256 == 0 && n >= 2 &&
+    return (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K) && k > 0 && k % 256 == 0 && n >= 2 &&
            n <= SB_COLS;
 }
 
@@ -857,18 +856,16 @@ hipError_t lfamd_launch_gemm_sb(int Atype, const void *A, long m, long k, int Bt
     const bool mins = Atype != LFAMD_TYPE_Q6_K;
     // up to 16 tokens of Q4_K / Q5_K: the 16-wave body with the codes in LDS; K halves when one work-group's codes would not fit
     // beside the reduction buffer, and on deep rows (twice the work-groups for the 128 row tiles of a 4096-row matrix)
-    static const bool no16 = getenv("LFAMD_SB_NO16") != nullptr;
     const int rl = n <= 8 ? 4 : 8;
     const size_t red_bytes = 16 * (size_t)rl * 64 * 4;
     int ksplit = 0;
     // (measured, profiles/r03_small_batch16.txt: a gain only where a work-group walks several tiles — 14336 x 4096 n = 8: 20.5 -> 16.4 us;
     //  with one tile per work-group the two-launch latency chain dominates and the 8-wave bodies are as fast)
-    static const bool no_i8 = getenv("LFAMD_SB_NO_I8") != nullptr; // development: A/B against the f16 bodies
     // Q4_K up to 8 tokens: the int8 form of the 16-wave body, on every shape (14336 x 4096: 16.6 -> 13.2 us, 4096 x 14336: 16.4 -> 13.4,
     // 8192 x 4096: 15.1 -> 10.6, 4096 x 4096: 9.1 -> 8.5); the f16 form (Q5_K, 9 .. 16 tokens) only where a work-group walks several
     // tiles (profiles/r03_small_batch16.txt)
-    const bool i8_ok = Atype == LFAMD_TYPE_Q4_K && n <= 8 && !no_i8;
-    if (mins && n <= 16 && !no16 && ((m + 31) / 32 > lfamd_num_cus() || i8_ok)) {
+    const bool i8_ok = Atype == LFAMD_TYPE_Q4_K && n <= 8;
+    if (mins && n <= 16 && ((m + 31) / 32 > lfamd_num_cus() || i8_ok)) {
         if ((size_t)nb * n * 512 + red_bytes <= 150 * 1024 && nb <= 16)
             ksplit = 1;
         else if ((size_t)((nb + 1) / 2) * n * 512 + red_bytes <= 150 * 1024)
@@ -945,8 +942,7 @@ staged:
     }
     const unsigned grid = 2u * (unsigned)(n_rt < lfamd_num_cus() ? n_rt : lfamd_num_cus()); // one 8-wave work-group per CU, K halves adjacent
     constexpr int NW = 8;
-    static const bool no_shallow = getenv("LFAMD_SB_ROLLING") != nullptr; // development: A/B of the two bodies
-    if ((nb + 1) / 2 <= NW && !no_shallow && Atype != LFAMD_TYPE_Q6_K) { // (Q6_K: more weight registers than the second set leaves room for) // one super-block per wave and K half: token fragments held in registers across the tiles
+    if ((nb + 1) / 2 <= NW && Atype != LFAMD_TYPE_Q6_K) { // (Q6_K: more weight registers than the second set leaves room for) // one super-block per wave and K half: token fragments held in registers across the tiles
         switch (Atype) {
         case LFAMD_TYPE_Q4_K:
             gemm_sb_shallow_kernel<LFAMD_TYPE_Q4_K, NW><<<grid, NW * 64, 0, s>>>((const uint8_t *)A, m, nb, Xh, d8T, Xm, (int)n, C, ldc, n_rt);

@@ -1,6 +1,5 @@
 // gemm_wide.hip — launchers of the 128 x 128 MFMA body (kernel: gemm_wide_impl.h; instantiations: gemm_wide_*.hip)
 #include "gemm_wide_impl.h"
-#include <stdlib.h>
 
 hipError_t lfamd_wide_go_q4k(WIDE_ARGS);
 hipError_t lfamd_wide_go_q5k(WIDE_ARGS);
@@ -17,8 +16,6 @@ hipError_t lfamd_wide_go_bf16(WIDE_ARGS);
 
 hipError_t lfamd_lw_go(int Atype, const gemm_mats &mats, int nb, const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
                        int n_rb, int n_ct, unsigned n_wg, int moe, int fast, int nt, int ks, float *P, hipStream_t s);
-bool lfamd_ks_ok(int Atype);
-bool lfamd_kr_ok(int Atype);
 hipError_t lfamd_kr_go(int Atype, const gemm_mats &mats128, int nb, const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
                        int n_ct, hipStream_t s);
 hipError_t lfamd_kr_moe_go(int Atype, const gemm_mats &mats, int nb, const void *Xh, const void *d8T, const void *Xm, long n_pad, int experts,
@@ -52,8 +49,7 @@ static int lw_ksplit(int tiles2, int nb) {
 // small ones on 256 CUs) lose against one partial round of the big tile; up to 128 big tiles the small tile's single round wins.
 #define LW_FULL_GRID 129
 static bool lw_allowed(int mode) {
-    static const bool env_plain = getenv("LFAMD_GEMM_NO_LW") != nullptr;
-    return !(mode & 1) && !env_plain;
+    return !(mode & 1);
 }
 
 // The first rb_cut row blocks of `mats` / the rest (a matrix straddling the cut is split: weights by row tiles, C by rows).
@@ -93,15 +89,13 @@ static hipError_t wide_go(int Atype, int mode, float *P, size_t P_bytes, WIDE_AR
     if ((q45 || (Atype == LFAMD_TYPE_Q6_K && g_scaled)) && lw_allowed(mode)) {
         if (g_scaled && !moe) {
             // scaled operands: 128 x 128 tiles when they fill the chip, else 128 x 64 (twice the work-groups, no K split)
-            static const int full_grid = getenv("LFAMD_LW_FULL_GRID") ? atoi(getenv("LFAMD_LW_FULL_GRID")) : LW_FULL_GRID; // (tuning)
-            if (n_rb * n_ct >= full_grid && lfamd_kr_ok(Atype)) // 256 x 128 tiles on the row-split body (gemm_kr.hip)
+            if (n_rb * n_ct >= LW_FULL_GRID && Atype == LFAMD_TYPE_Q4_K) // 256 x 128 tiles on the row-split body (gemm_kr.hip)
                 return lfamd_kr_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_ct, s);
-            if (n_rb * n_ct >= full_grid) {
+            if (n_rb * n_ct >= LW_FULL_GRID) {
                 // full rounds of 128 x 128 tiles; a last round of at most 128 of them (half the CUs idle) runs as one round of
                 // 128 x 64 tiles instead (0.73 of the time): ffn_gate + ffn_up at 512 tokens = 896 tiles = 3 rounds + 128
-                static const bool no_tail = getenv("LFAMD_LW_NO_TAIL_SPLIT") != nullptr; // (tests compare the two)
                 const int tiles = n_rb * n_ct, rem = tiles % 256;
-                if (!no_tail && tiles > 256 && rem > 0 && rem <= 128 && rem % n_ct == 0) {
+                if (tiles > 256 && rem > 0 && rem <= 128 && rem % n_ct == 0) {
                     const int rb_cut = (tiles - rem) / n_ct;
                     const size_t tile_bytes = (size_t)nb * (Atype == LFAMD_TYPE_Q5_K ? P5K_TILE : Atype == LFAMD_TYPE_Q6_K ? P6K_TILE : P4K_TILE);
                     gemm_mats lo, hi;
@@ -111,7 +105,7 @@ static hipError_t wide_go(int Atype, int mode, float *P, size_t P_bytes, WIDE_AR
                     if (e != hipSuccess)
                         return e;
                     const int n_ct2 = (int)((n + 63) / 64), rb_hi = n_rb - rb_cut;
-                    if (lfamd_ks_ok(Atype))
+                    if (Atype == LFAMD_TYPE_Q4_K) // (the K-split-waves body, gemm_ks.hip)
                         return lfamd_ks_go(Atype, hi, nb, Xh, d8T, Xm, n, n_pad, rb_hi, n_ct2, s);
                     return lfamd_lw_go(Atype, hi, nb, Xh, d8T, Xm, n, n_pad, rb_hi, n_ct2, (unsigned)(rb_hi * n_ct2), 0, 1, 2, 1, nullptr, s);
                 }
@@ -127,7 +121,7 @@ static hipError_t wide_go(int Atype, int mode, float *P, size_t P_bytes, WIDE_AR
                 return lfamd_lw_ksplit_reduce(P, ksp, n, n_pad, (long)n_rb * 128, mats.m[0], mats.C[0], mats.ldc[0],
                                               (const float *)d8T, s);
             }
-            if (lfamd_ks_ok(Atype)) // 128 x 64 tiles on the K-split-waves body (gemm_ks.hip)
+            if (Atype == LFAMD_TYPE_Q4_K) // 128 x 64 tiles on the K-split-waves body (gemm_ks.hip)
                 return lfamd_ks_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, s);
             return lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, (unsigned)(n_rb * n_ct2), 0, 1, 2, 1, nullptr, s);
         }
@@ -190,9 +184,7 @@ extern "C" int lfamd_gemm_wide_ksplit(long m, long k, long n_pad) {
 
 // Will a wide launch of these (fused) matrices run the loader-wave body, i.e. may the caller stage scaled activations?
 extern "C" int lfamd_gemm_wide_scaled_ok(int Atype, int plain) {
-    static const bool env_off = getenv("LFAMD_GEMM_NO_SCALED") != nullptr, env_plain = getenv("LFAMD_GEMM_NO_LW") != nullptr;
-    return !(env_off || env_plain || plain ||
-             (Atype != LFAMD_TYPE_Q4_K && Atype != LFAMD_TYPE_Q5_K && Atype != LFAMD_TYPE_Q6_K));
+    return !plain && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K);
 }
 
 extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const void *const *A, const long *m, long k,
@@ -264,8 +256,7 @@ extern "C" hipError_t lfamd_launch_gemm_wide_dual(int type_a, int count_a, const
                                                   const void *const *A_b, const long *m_b, float *const *C_b, const long *ldc_b,
                                                   long k, const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
                                                   int mode, hipStream_t s) {
-    static const bool off = getenv("LFAMD_GEMM_NO_DUAL") != nullptr;
-    if (off || !(mode & 2) || !lw_allowed(mode) || type_b != LFAMD_TYPE_Q6_K || (type_a != LFAMD_TYPE_Q4_K && type_a != LFAMD_TYPE_Q5_K) ||
+    if (!(mode & 2) || !lw_allowed(mode) || type_b != LFAMD_TYPE_Q6_K || (type_a != LFAMD_TYPE_Q4_K && type_a != LFAMD_TYPE_Q5_K) ||
         count_a <= 0 || count_b <= 0 || count_a > GEMM_MAX_MATS || count_b > GEMM_MAX_MATS || n_pad % WD_COLS)
         return hipErrorNotSupported;
     gemm_mats ma, mb;
@@ -300,9 +291,8 @@ extern "C" hipError_t lfamd_launch_gemm_wide_moe(int Atype, const void *W, long 
     const unsigned n_wg = (unsigned)experts * n_rb * ct_max;
     if (Atype != LFAMD_TYPE_Q4_K && Atype != LFAMD_TYPE_Q5_K && Atype != LFAMD_TYPE_Q6_K)
         return hipErrorInvalidValue;
-    // scaled operands, Q4_K experts: the 256 x 128 row-split body (gemm_kr.hip) — LFAMD_MOE_NO_KR: the loader-wave body (A/B runs)
-    static const bool no_kr = getenv("LFAMD_MOE_NO_KR") != nullptr;
-    if ((mode & 2) && lw_allowed(mode) && !no_kr && lfamd_kr_ok(Atype))
+    // scaled operands, Q4_K experts: the 256 x 128 row-split body (gemm_kr.hip)
+    if ((mode & 2) && lw_allowed(mode) && Atype == LFAMD_TYPE_Q4_K)
         return lfamd_kr_moe_go(Atype, mats, nb, Xh, d8T, Xm, n_pad, experts, ct_max, s);
     return wide_go(Atype, mode, nullptr, 0, mats, nb, Xh, d8T, Xm, n_pad, n_pad, n_rb, ct_max, 1, nb, n_wg, 1, s);
 }

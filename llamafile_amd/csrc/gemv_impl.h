@@ -1922,9 +1922,8 @@ static hipError_t launch_kq_ids(const gemv_mats &mats, int n_ht, long k, const v
     // gate + up experts in one launch (4 x 896 half-tiles of 16 super-blocks, 14 per 16-wave work-group): every item ends in a
     // work-group barrier, and two independent 8-wave work-groups per CU hide each other's — Mixtral decode pass 1.823 ->
     // 1.706 ms (548 -> 586 tokens/s).  Shorter walks keep the 16-wave form (see launch_kq_pick).
-    static const bool no_nw8 = getenv("LFAMD_IDS_NO_NW8") && atoi(getenv("LFAMD_IDS_NO_NW8"));
     // (the 16-wave form with 32-row items, seven per work-group, was measured too: 1.748 ms per pass against 1.702 for this one)
-    if (nb <= 16 && !no_nw8 && n_ht >= 8 * num_cus()) {
+    if (nb <= 16 && n_ht >= 8 * num_cus()) {
         constexpr int NW8 = 8;
         const size_t smem8 = (size_t)nb * XBLK + 2 * NW8 * 16 * sizeof(float) + (size_t)NW8 * XBLK;
         const int max8 = 2 * num_cus(), per8 = (n_ht + max8 - 1) / max8, grid8 = (n_ht + per8 - 1) / per8;

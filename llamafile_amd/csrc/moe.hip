@@ -201,11 +201,10 @@ extern "C" hipError_t lfamd_launch_moe(int type, const void *W, long rows, long 
     if (tokens <= 4 && (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K) &&
         !(flags & LFAMD_FLAG_FORCE_GENERIC) &&
         (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && (size_t)(cols / 256) * 384 <= 150 * 1024) {
-        static const bool no_pair = getenv("LFAMD_MOE_NO_PAIR") != nullptr; // development: A/B
         for (long t = 0; t < tokens; t++) {
             int th = 0;
             while (th < thinkers) {
-                if (tasks > 1 && th + 1 < thinkers && (th + 1) % tasks != th % tasks && !no_pair) {
+                if (tasks > 1 && th + 1 < thinkers && (th + 1) % tasks != th % tasks) {
                     // two thinkers with their own activation rows (ffn_down_exps): one launch, half of the work-groups each
                     const uint8_t *Ba = (const uint8_t *)thought + (size_t)(t * tasks + th % tasks) * b_row_bytes;
                     const uint8_t *Bb = (const uint8_t *)thought + (size_t)(t * tasks + (th + 1) % tasks) * b_row_bytes;

@@ -143,7 +143,7 @@ def test_gate_up_fused_launch_tail_split(gpu):
     128 x 128 tiles only (448 tiles each: no such tail): the rows that keep their tile shape are bit-identical; the Q4_K
     128 x 64 tail runs the K-split-waves body (gemm_ks.hip) since round 3, whose two wave groups sum their K halves
     separately — the same products in another f32 order (<= 4e-6 of the output scale; it was bit-identical on the
-    loader-wave body, which LFAMD_GEMM_NO_KS=1 still selects)."""
+    loader-wave body, which the Q5_K / Q6_K tails still run)."""
     from llamafile_amd import synth
     t, m, k = T.Q4_K, 14336, 4096
     Ws = [gpu.upload_weights(t, synth.random_weights_torch(t, m, k, 31 + i), m, k) for i in range(2)]

@@ -236,3 +236,45 @@ def test_producers_write_the_scaled_image_of_the_f16_bodies(gpu, producer, k, n)
     # a call that runs another body declines the image
     assert L.lfamd_mul_mat_takes_staged_scaled(T.Q4_K, 4096, k, n, flags | _hip.FLAG_PRECISE) == 0
     assert L.lfamd_mul_mat_takes_staged_scaled(T.Q8_0, 4096, k, n, flags) == 0
+
+
+def test_staged_image_declined_before_any_launch(gpu):
+    """A multi-matrix call on a staged image that one of its matrices does not take returns LFAMD_ERR_UNSUPPORTED with nothing
+    enqueued: lfamd_mul_mat_multi on the scaled image (five Q4_K matrices, one call each; the last one runs the int8 body), and
+    lfamd_mul_mat_multi_types on the int8 body's image (a Q4_K run that takes it, then a Q6_K run that does not).  Every output
+    still holds its sentinel."""
+    L = _hip.lib()
+    flags = gpu.host_variant_flags()
+    k, n = 512, 256
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sentinel = 12345.0
+
+    def call(types, rows, Btype, image):
+        cnt = len(rows)
+        Ws = [gpu.upload_weights(t, synth.random_weights(t, m, k, 40 + j), m, k) for j, (t, m) in enumerate(zip(types, rows))]
+        outs = [torch.full((n, m), sentinel, dtype=torch.float32, device="cuda") for m in rows]
+        ws = torch.zeros(max(L.lfamd_mul_mat_workspace(t, m, k, n) for t, m in zip(types, rows)) + 16, dtype=torch.uint8, device="cuda")
+        A = (C.c_void_p * cnt)(*[w.data.data_ptr() for w in Ws])
+        Cs = (C.c_void_p * cnt)(*[o.data_ptr() for o in outs])
+        ms = (C.c_long * cnt)(*rows)
+        args = (A, ms, k, Btype, C.c_void_p(image.data_ptr()), 0, n, Cs, ms, C.c_void_p(ws.data_ptr()), ws.numel(), flags, st)
+        if len(set(types)) == 1:
+            rc = L.lfamd_mul_mat_multi(types[0], cnt, *args)
+        else:
+            rc = L.lfamd_mul_mat_multi_types(cnt, (C.c_int * cnt)(*types), *args)
+        torch.cuda.synchronize()
+        return rc, outs
+
+    rows = [1024, 1024, 1024, 1024, 4096]
+    assert [L.lfamd_mul_mat_takes_staged_scaled(T.Q4_K, m, k, n, flags) for m in rows] == [1, 1, 1, 1, 0]
+    image = torch.zeros(L.lfamd_staged_scaled_size(k, n), dtype=torch.uint8, device="cuda")
+    rc, outs = call([T.Q4_K] * 5, rows, _hip.TYPE_STAGED_SCALED, image)
+    assert rc == -1
+    assert all(torch.all(o == sentinel) for o in outs)
+
+    types, rows = [T.Q4_K, T.Q6_K], [4096, 1024]
+    assert [L.lfamd_mul_mat_takes_staged(t, m, k, n, flags) for t, m in zip(types, rows)] == [1, 0]
+    image = torch.zeros(L.lfamd_staged_q8k_size(k, n), dtype=torch.uint8, device="cuda")
+    rc, outs = call(types, rows, _hip.TYPE_STAGED_Q8K, image)
+    assert rc == -1
+    assert all(torch.all(o == sentinel) for o in outs)
