@@ -98,6 +98,36 @@ int lfamd_vendor_gemm_available(void);
 int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t raw_row_bytes,
                        void *d_packed, void *stream);
 
+/* Reading a resident image back (csrc/dequant.hip).  The packed image is not write-only: a host that freed the GGUF rows after
+ * lfamd_pack_weights can still look rows up, dequantise the tensor and get the file's bytes again, so no tensor has to be held twice
+ * (token_embd.weight of a tied-embedding model IS output.weight: one image serves the row lookup and the mat-mul).
+ *
+ * lfamd_get_rows: rows d_ids[0 .. n_ids) of the packed rows x cols matrix as out_type (LFAMD_TYPE_F32 or LFAMD_TYPE_F16) rows,
+ * out_row_bytes apart.  d_ids == NULL: rows row0 .. row0 + n_ids (whole-tensor dequantisation: row0 = 0, n_ids = rows).  Stands for
+ * GGML_OP_GET_ROWS (k_get_rows / ggml_cuda_op_get_rows, ggml-cuda.cu.patch:10687-10860) and for the to_fp16 / to_fp32 converters
+ * (ggml_get_to_fp16_cuda / ggml_get_to_fp32_cuda, :3929-4040), for every type and shape lfamd_packed_size answers non-zero for.
+ *   EXACT: every value is the f32 ((d * sc) * q) - (dmin * mn) (K-quants, IQ4_XS) or (d * q) + m (32-blocks) of the block's own
+ *   fields, in that order, uncontracted — the same bits as dequantising the GGUF row on the CPU (oracle.c: ora_dequantize_row),
+ *   the sign of zero included; F16 output is that value rounded to nearest-even (subnormals kept, overflow to inf); F32 / F16 /
+ *   BF16 tensors convert exactly.
+ *   An index outside [0, rows) leaves its output row untouched (the rule lfamd_mul_mat_id has for expert ids); bytes of an output
+ *   row beyond `cols` elements are never written; n_ids == 0 is LFAMD_OK with nothing launched.  d_out aligned to 16 bytes with
+ *   out_row_bytes a multiple of 16 gets whole 16 / 8-byte stores; any element-aligned buffer works.
+ *   Asynchronous on `stream`: no workspace, no allocation, no host read-back — capturable in a graph like lfamd_mul_mat.
+ *   Errors, before any launch: unknown type or out_type -> LFAMD_ERR_UNSUPPORTED; cols not a block multiple, out_row_bytes smaller
+ *   than cols elements or not a multiple of the element, a null pointer, row0 + n_ids > rows with d_ids == NULL -> LFAMD_ERR_INVALID.
+ *   An expert stack needs nothing new: expert e is (const char *)d_packed + e * lfamd_packed_size(type, rows, cols).
+ *
+ * lfamd_unpack_weights: the inverse of lfamd_pack_weights (ggml_backend_cuda_buffer_get_tensor, ggml-cuda.cu.patch:16890-17027):
+ * the image back to GGUF rows, raw_row_bytes apart, BYTE FOR BYTE, for every type.  Every image is a permutation of the file's bits
+ * plus derived fields; where a header field is kept re-coded (the sixteen int8 scales of PK3 for Q3_K's scales[12], the eight of the
+ * compact IQ4_XS image for scales_l / scales_h) the re-coding is a bijection and is inverted.  No type answers LFAMD_ERR_UNSUPPORTED.
+ * One caveat, inherited from packing: the Q2_K / Q3_K images hold d and dmin after an f16 -> f32 -> f16 round trip, which is the
+ * identity on every value except a signalling NaN (it comes back quiet).  Same stream and error rules as lfamd_pack_weights. */
+int lfamd_get_rows(int type, const void *d_packed, long rows, long cols, const int32_t *d_ids, long row0, long n_ids, int out_type,
+                   void *d_out, size_t out_row_bytes, void *stream);
+int lfamd_unpack_weights(int type, long rows, long cols, const void *d_packed, void *d_raw, size_t raw_row_bytes, void *stream);
+
 /* Batches (n > 8) of Q4_K / Q5_K / Q6_K run the scaled-operand MFMA body by default: weights as f16(d * sc * q), activations as
  * f16(d8 * code), f32 accumulate — one f16 rounding per operand, relative error ~1e-4 (north star: 1e-3), no scaling per
  * super-block.  Its constants need f16(|d| * 63) * 1024 <= 65504 and |dmin| * 63 <= 65504 for every block, which every ggml-quantised

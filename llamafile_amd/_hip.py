@@ -47,6 +47,8 @@ _SIGS = {
     "lfamd_packed_size": (_sz, [_i, _l, _l]),
     "lfamd_pack_weights": (_i, [_i, _l, _l, _vp, _sz, _vp, _vp]),
     "lfamd_scaled_gemm_ok": (_i, [_i, _l, _l, _vp, _vp]),
+    "lfamd_get_rows": (_i, [_i, _vp, _l, _l, _vp, _l, _l, _i, _vp, _sz, _vp]),
+    "lfamd_unpack_weights": (_i, [_i, _l, _l, _vp, _vp, _sz, _vp]),
     "lfamd_mul_mat_is_exact": (_i, [_i, _l, _l, _l, _u]),
     "lfamd_mul_mat_takes_staged": (_i, [_i, _l, _l, _l, _u]),
     "lfamd_staged_q8k_size": (_sz, [_l, _l]),

@@ -87,6 +87,9 @@ hipError_t lfamd_launch_gemm_i8_staged(int count, const void *const *A, const lo
                                        const long *ldc, hipStream_t s);
 hipError_t lfamd_launch_gemm_i8(int count, const void *const *A, const long *m, long k, int Btype, const void *B, size_t b_row_bytes, long n,
                                 float *const *C, const long *ldc, void *ws, const int32_t *src_idx, hipStream_t s);
+hipError_t lfamd_launch_get_rows(int type, const void *img, long rows, long cols, const int32_t *ids, long row0, long n_ids, int out_type,
+                                 void *out, size_t out_row_bytes, hipStream_t s);
+hipError_t lfamd_launch_unpack(int type, const void *img, long rows, long cols, void *raw, size_t raw_row_bytes, hipStream_t s);
 }
 
 static thread_local char g_err[512] = "";
@@ -304,6 +307,47 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
     default:
         HIPCHK(lfamd_launch_pack_raw(d_raw, raw_row_bytes, rows, lfamd_row_size(type, cols), d_packed, s), "pack_raw");
     }
+    return LFAMD_OK;
+}
+
+// Reading a resident image back (dequant.hip).  Neither call enters plan_mul_mat: no dispatch decision depends on them, they take no
+// workspace, allocate nothing and read nothing back, so both are capturable like lfamd_mul_mat.
+int lfamd_get_rows(int type, const void *d_packed, long rows, long cols, const int32_t *d_ids, long row0, long n_ids, int out_type,
+                   void *d_out, size_t out_row_bytes, void *stream) {
+    (void)hipGetLastError(); // (as lfamd_pack_weights)
+    if (!type_known(type))
+        return fail(LFAMD_ERR_UNSUPPORTED, "get_rows: unsupported ggml type%s", "");
+    if (out_type != LFAMD_TYPE_F32 && out_type != LFAMD_TYPE_F16)
+        return fail(LFAMD_ERR_UNSUPPORTED, "get_rows: out_type must be F32 or F16%s", "");
+    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || n_ids < 0)
+        return fail(LFAMD_ERR_INVALID, "get_rows: bad shape%s", "");
+    const size_t esz = out_type == LFAMD_TYPE_F32 ? 4 : 2;
+    if (out_row_bytes < (size_t)cols * esz || out_row_bytes % esz)
+        return fail(LFAMD_ERR_INVALID, "get_rows: out_row_bytes %s", "smaller than a row or not a multiple of the element");
+    if (!d_ids && (row0 < 0 || row0 > rows || n_ids > rows - row0))
+        return fail(LFAMD_ERR_INVALID, "get_rows: rows row0 .. row0 + n_ids %s", "outside the matrix");
+    if (n_ids == 0 || cols == 0)
+        return LFAMD_OK;
+    if (!d_packed || !d_out)
+        return fail(LFAMD_ERR_INVALID, "get_rows: null pointer%s", "");
+    if ((uintptr_t)d_out % esz)
+        return fail(LFAMD_ERR_INVALID, "get_rows: d_out %s", "not aligned to the element");
+    HIPCHK(lfamd_launch_get_rows(type, d_packed, rows, cols, d_ids, d_ids ? 0 : row0, n_ids, out_type, d_out, out_row_bytes, (hipStream_t)stream),
+           "get_rows");
+    return LFAMD_OK;
+}
+
+int lfamd_unpack_weights(int type, long rows, long cols, const void *d_packed, void *d_raw, size_t raw_row_bytes, void *stream) {
+    (void)hipGetLastError();
+    if (!type_known(type))
+        return fail(LFAMD_ERR_UNSUPPORTED, "unpack_weights: unsupported ggml type%s", "");
+    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || raw_row_bytes < lfamd_row_size(type, cols))
+        return fail(LFAMD_ERR_INVALID, "unpack_weights: bad shape%s", "");
+    if (rows == 0 || cols == 0)
+        return LFAMD_OK;
+    if (!d_packed || !d_raw)
+        return fail(LFAMD_ERR_INVALID, "unpack_weights: null pointer%s", "");
+    HIPCHK(lfamd_launch_unpack(type, d_packed, rows, cols, d_raw, raw_row_bytes, (hipStream_t)stream), "unpack_weights");
     return LFAMD_OK;
 }
 

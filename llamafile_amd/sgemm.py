@@ -103,6 +103,44 @@ def upload_weights(t: int, raw, rows: int, cols: int, device="cuda") -> PackedWe
     return W
 
 
+_OUT_TYPES = {torch.float32: T.F32, torch.float16: T.F16}
+
+
+def get_rows(W: PackedWeights, ids: torch.Tensor | None, out_dtype: torch.dtype = torch.float32, row0: int = 0, n: int | None = None,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """GGML_OP_GET_ROWS on a resident image (lfamd_get_rows): rows ids[0 .. n) of W, dequantised to out_dtype (float32 or
+    float16) with the oracle's arithmetic, bit for bit.  ids: int32 cuda vector, or None for rows row0 .. row0 + n.  An index
+    outside [0, rows) leaves its row of `out` untouched; `out` may be wider than W.cols (the padding is never written)."""
+    if out_dtype not in _OUT_TYPES:
+        raise _hip.LfamdError(f"get_rows: out_dtype {out_dtype} is neither float32 nor float16")
+    if ids is not None:
+        assert ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
+        n = ids.numel() if n is None else n
+        assert n <= ids.numel()
+    elif n is None:
+        n = W.rows - row0
+    if out is None:
+        out = torch.empty((n, W.cols), dtype=out_dtype, device=W.data.device)
+    assert out.is_cuda and out.dtype == out_dtype and out.dim() == 2 and out.shape[0] >= n and (out.shape[1] == 0 or out.stride(1) == 1)
+    rc = _hip.lib().lfamd_get_rows(W.type, _ptr(W.data), W.rows, W.cols, _ptr(ids) if ids is not None else C.c_void_p(0), row0, n,
+                                   _OUT_TYPES[out_dtype], _ptr(out), out.stride(0) * out.element_size(), _stream())
+    _hip.check(rc, "lfamd_get_rows")
+    return out
+
+
+def dequantize(W: PackedWeights, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The whole matrix as out_dtype [rows, cols] (the reference's to_fp32 / to_fp16 converters)."""
+    return get_rows(W, None, out_dtype, 0, W.rows)
+
+
+def unpack_weights(W: PackedWeights) -> torch.Tensor:
+    """The inverse of upload_weights: uint8 [rows, row_bytes], the tensor's GGUF bytes (lfamd_unpack_weights)."""
+    rb = T.row_size(W.type, W.cols)
+    raw = torch.empty((W.rows, rb), dtype=torch.uint8, device=W.data.device)
+    _hip.check(_hip.lib().lfamd_unpack_weights(W.type, W.rows, W.cols, _ptr(W.data), _ptr(raw), rb, _stream()), "lfamd_unpack_weights")
+    return raw
+
+
 def quantize_rows(vec_dot_type: int, x: torch.Tensor) -> torch.Tensor:
     """f32 [n, k] cuda -> activation blocks uint8 [n, row_size]."""
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
