@@ -5,92 +5,10 @@
 // run the generic kernel.  There is no CPU fallback anywhere in this module.
 #include "lfamd_device.h"
 #include "../../include/lfamd_hip.h"
+#include "lfamd_internal.h"
 
 #include <stdio.h>
 #include <string.h>
-
-extern "C" {
-hipError_t lfamd_launch_pack_q4k(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q40(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_prep80(int, const void *, size_t, long, long, long, void *, void *, void *, hipStream_t);
-hipError_t lfamd_launch_wprep32(int, const void *, size_t, long, long, void *, hipStream_t);
-size_t lfamd_wprep32_bytes(long, long);
-hipError_t lfamd_launch_prep_float(int, int, const void *, size_t, long, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_wprep8(int, const void *, size_t, long, long, void *, hipStream_t);
-size_t lfamd_wprep8_bytes(long, long);
-hipError_t lfamd_launch_pack_q5k(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q6k(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q80(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_raw(const void *, size_t, long, size_t, void *, hipStream_t);
-hipError_t lfamd_launch_prep_q8k(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);
-hipError_t lfamd_launch_prep_f32(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);
-bool lfamd_moe_decode_multi_ok(int type, long cols, int Btype, int tasks, long tokens, unsigned flags);
-hipError_t lfamd_launch_moe_decode_multi(int type, int count, const void *const *W, long rows, long cols, int experts, size_t expert_bytes,
-                                         int Btype, const void *thought, size_t b_row_bytes, long tokens, const int32_t *plan, int thinkers,
-                                         float *const *result, hipStream_t s);
-bool lfamd_blaslt_ok();
-size_t lfamd_blaslt_workspace();
-hipError_t lfamd_blaslt_gemm(int dtype, const void *W, long ldw, const void *X, long ldx, long m, long n, long k, float *C, long ldc, void *ws,
-                             size_t ws_bytes, hipStream_t s);
-hipError_t lfamd_launch_rows_to_16(int dtype, const void *X, size_t x_row_bytes, long n, long k, void *out, hipStream_t s);
-hipError_t lfamd_launch_q80_rows_to_f16(int Btype, const void *X, size_t x_row_bytes, long n, long k, void *out, hipStream_t s);
-hipError_t lfamd_launch_q80_image(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s);
-size_t lfamd_pk_bytes(int type, long rows, long cols);
-hipError_t lfamd_launch_pk4x_pack(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s);
-hipError_t lfamd_launch_pk4x_expand(const void *packed, long rows, long cols, void *out, hipStream_t s);
-hipError_t lfamd_launch_pk_pack(int type, const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s);
-hipError_t lfamd_launch_pk_expand(int type, const void *packed, long rows, long cols, void *out, hipStream_t s);
-size_t lfamd_gemm_sb_workspace(long k);
-bool lfamd_gemm_sb_ok(int Atype, long k, long n);
-hipError_t lfamd_launch_gemm_sb(int Atype, const void *A, long m, long k, int Btype, const void *B, size_t b_row_bytes, long n, float *C,
-                                long ldc, void *ws, int reuse_stage, hipStream_t s);
-hipError_t lfamd_launch_wprep16(int, const void *, size_t, long, long, void *, hipStream_t);
-size_t lfamd_wprep16_bytes(long, long);
-hipError_t lfamd_launch_generic(int, const void *, long, long, int, const void *, size_t, long, float *, long, hipStream_t);
-hipError_t lfamd_launch_gemv_float(int, const void *, long, long, int, const void *, size_t, long, float *, long, hipStream_t);
-int lfamd_gemv_float_ok(int, long, long);
-hipError_t lfamd_launch_gemv(int, const void *, long, long, int, const void *, size_t, long, float *, long, int, int,
-                             hipStream_t);
-hipError_t lfamd_launch_gemv_multi(int, int, const void *const *, const long *, long, int, const void *, size_t, long,
-                                   float *const *, const long *, int, int, hipStream_t);
-hipError_t lfamd_launch_gemm_q80(const void *, long, long, int, const void *, size_t, long, float *, long, void *, int, int,
-                                 hipStream_t);
-size_t lfamd_gemm_q80_workspace(long, long);
-hipError_t lfamd_launch_gemv_dual(int, int, const void *const *, const long *, float *const *, const long *, int, int,
-                                  const void *const *, const long *, float *const *, const long *, long, int, const void *, size_t,
-                                  hipStream_t);
-hipError_t lfamd_launch_scaled_ok(int, long, long, const void *, int *, hipStream_t);
-int lfamd_gemm_wide_scaled_ok(int, int);
-// (the wide launchers take `mode`: bit 0 plain body, bit 1 activations staged scaled — gemm_wide.hip)
-hipError_t lfamd_launch_gemm_wide_multi(int, int, const void *const *, const long *, long, const void *, const void *,
-                                        const void *, long, long, float *const *, const long *, int, void *, size_t, hipStream_t);
-hipError_t lfamd_launch_gemm_wide(int, const void *, long, long, const void *, const void *, const void *, long, long,
-                                  float *, long, int, void *, size_t, hipStream_t);
-size_t lfamd_gemm_lw_ksplit_bytes(long, long);
-hipError_t lfamd_launch_gemm_wide_dual(int, int, const void *const *, const long *, float *const *, const long *, int, int,
-                                       const void *const *, const long *, float *const *, const long *, long, const void *,
-                                       const void *, const void *, long, long, int, hipStream_t);
-hipError_t lfamd_launch_gemm_kq(int, const void *, long, long, const void *, const void *, const void *, long, long,
-                                float *, long, hipStream_t);
-hipError_t lfamd_launch_quantize(int, const float *, long, long, size_t, void *, size_t, hipStream_t);
-hipError_t lfamd_launch_moe(int, const void *, long, long, int, size_t, int, const void *, size_t, int, long,
-                            const int32_t *, int, float *, void *, size_t, unsigned, hipStream_t);
-size_t lfamd_moe_workspace(int, long, long, int, long, int);
-int lfamd_gemm_i8_ok(int Atype, long row_blocks128, long n);
-size_t lfamd_gemm_i8_workspace(long k, long n);
-hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, const long *m, long k, int Btype, const void *B, size_t b_row_bytes, long n,
-                                    float *const *C, const long *ldc, void *ws, hipStream_t s);
-size_t lfamd_gemm_lf_workspace(long k, long n);
-hipError_t lfamd_launch_gemm_lf_float(int Atype, const void *A, size_t a_row_bytes, long m, long k, const void *Xh, long n, long n_pad, float *C,
-                                      long ldc, hipStream_t s);
-hipError_t lfamd_launch_gemm_i8_staged(int count, const void *const *A, const long *m, long k, const void *image, long n, float *const *C,
-                                       const long *ldc, hipStream_t s);
-hipError_t lfamd_launch_gemm_i8(int count, const void *const *A, const long *m, long k, int Btype, const void *B, size_t b_row_bytes, long n,
-                                float *const *C, const long *ldc, void *ws, const int32_t *src_idx, hipStream_t s);
-hipError_t lfamd_launch_get_rows(int type, const void *img, long rows, long cols, const int32_t *ids, long row0, long n_ids, int out_type,
-                                 void *out, size_t out_row_bytes, hipStream_t s);
-hipError_t lfamd_launch_unpack(int type, const void *img, long rows, long cols, void *raw, size_t raw_row_bytes, hipStream_t s);
-}
 
 static thread_local char g_err[512] = "";
 
@@ -415,10 +333,6 @@ static bool float_lf_fits(int Atype, long m, long k) {
     return (size_t)m * lfamd_row_size(Atype, k) < ((size_t)1 << 32);
 }
 
-static size_t gemm_act_ws(long k, long n) { // Xh + d8T + Xm of the K-quant GEMM
-    size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-    return align_up(n_pad * (size_t)k * 2, 256) + align_up(nb * n_pad * 4, 256) + align_up(n_pad * nb * 32, 256);
-}
 static size_t gemm_lt_ws(long k, long n) { // the 16-bit activation rows, then the library's workspace
     return align_up((size_t)n * (size_t)k * 2, 256) + lfamd_blaslt_workspace();
 }
@@ -529,7 +443,7 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
     } else if (n <= 8 && packed(Atype, k))
         p.body = mm_body::gemv;
 
-    const size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
+    const size_t n_pad = align_up((size_t)n, 128), act = lfamd_kq_image_of(k, n).parts; // (the staged K-quant image, lfamd_internal.h)
     switch (p.body) {
     case mm_body::sb:
         p.workspace = align_up(lfamd_gemm_sb_workspace(k), 256);
@@ -537,16 +451,16 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
     case mm_body::i8: // (the staging layout every K-quant batch body shares, then partial tiles of a K-split launch)
     case mm_body::kq_narrow:
     case mm_body::wide:
-        p.workspace = gemm_act_ws(k, n) + lfamd_gemm_lw_ksplit_bytes(m, n);
+        p.workspace = act + lfamd_gemm_lw_ksplit_bytes(m, n);
         break;
     case mm_body::q40_wide:
-        p.workspace = gemm_act_ws(k, n);
+        p.workspace = act;
         break;
     case mm_body::canon: // (+ the canonical image of the matrix, rebuilt from the compact one per call)
-        p.workspace = gemm_act_ws(k, n) + align_up(Atype == LFAMD_TYPE_IQ4_XS ? lfamd_wprep8_bytes(m, k) : lfamd_wprep16_bytes(m, k), 256);
+        p.workspace = act + align_up(Atype == LFAMD_TYPE_IQ4_XS ? lfamd_wprep8_bytes(m, k) : lfamd_wprep16_bytes(m, k), 256);
         break;
-    case mm_body::canon32: // Xh, d8T [nb*8][n_pad], sT [nb*8][n_pad]
-        p.workspace = align_up(n_pad * (size_t)k * 2, 256) + 2 * align_up(nb * 8 * n_pad * 4, 256);
+    case mm_body::canon32:
+        p.workspace = lfamd_b32_image_of(k, n).bytes;
         break;
     case mm_body::float_lt: // (each one may fall back on the others)
     case mm_body::float_lf:
@@ -627,20 +541,6 @@ size_t lfamd_mul_mat_workspace_upto(int Atype, long m, long k, long n) {
     return best;
 }
 
-struct scaled_image_ptrs {
-    const void *Xh, *d8T, *Xm;
-    size_t n_pad;
-};
-static scaled_image_ptrs scaled_image_of(const void *image, long k, long n) {
-    scaled_image_ptrs p;
-    p.n_pad = align_up((size_t)n, 128);
-    const size_t nb = (size_t)(k / 256);
-    p.Xh = image;
-    p.d8T = (const uint8_t *)image + align_up(p.n_pad * (size_t)k * 2, 256);
-    p.Xm = (const uint8_t *)p.d8T + align_up(nb * p.n_pad * 4, 256);
-    return p;
-}
-
 static bool aligned16(const void *p) {
     return ((uintptr_t)p & 15) == 0;
 }
@@ -687,21 +587,32 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
     return LFAMD_OK;
 }
 
+// f32 or Q8_K activation rows -> the K-quant image at img (mode: prep mode 2 stages scaled operands; the canonical bodies pass mins16)
+static int prep_kq(int Btype, const void *d_B, size_t b_row_bytes, long n, long k, uint8_t *img, int mode, hipStream_t s) {
+    const lfamd_kq_image im = lfamd_kq_image_of(k, n);
+    if (Btype == LFAMD_TYPE_F32)
+        HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)im.n_pad, k, img, img + im.d8T, img + im.Xm, mode, nullptr, s), "prep_f32");
+    else
+        HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)im.n_pad, k, img, img + im.d8T, img + im.Xm, mode, nullptr, s), "prep_q8k");
+    return LFAMD_OK;
+}
+
 static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, long k, int Btype, const void *d_B, size_t b_row_bytes,
                           long n, float *d_C, long ldc, void *d_ws, size_t ws_bytes, unsigned flags, hipStream_t s) {
     const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
     const int vregs32 = (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0, precise = (flags & LFAMD_FLAG_PRECISE) ? 1 : 0;
     const int vdt = lfamd_vec_dot_type(Atype);
-    const size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
+    const lfamd_kq_image im = lfamd_kq_image_of(k, n);
+    const size_t n_pad = im.n_pad;
     uint8_t *ws = (uint8_t *)d_ws; // the staging layout of the K-quant batch bodies: Xh, d8T, Xm
-    void *Xh = ws, *d8T = ws + align_up(n_pad * (size_t)k * 2, 256), *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
+    void *Xh = ws, *d8T = ws + im.d8T, *Xm = ws + im.Xm;
     if (Btype == LFAMD_TYPE_STAGED_Q8K) { // the GEMM alone, no staging launch
         HIPCHK(lfamd_launch_gemm_i8_staged(1, &d_A, &m, k, d_B, n, &d_C, &ldc, s), "gemm_i8 (staged input)");
         return LFAMD_OK;
     }
     if (Btype == LFAMD_TYPE_STAGED_SCALED) {
-        const scaled_image_ptrs im = scaled_image_of(d_B, k, n);
-        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, im.Xh, im.d8T, im.Xm, n, (long)im.n_pad, d_C, ldc, plain | 2, d_ws, ws_bytes, s),
+        const uint8_t *img = (const uint8_t *)d_B;
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, img, img + im.d8T, img + im.Xm, n, (long)n_pad, d_C, ldc, plain | 2, d_ws, ws_bytes, s),
                "gemm_wide (staged input)");
         return LFAMD_OK;
     }
@@ -719,34 +630,29 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
     case mm_body::kq_narrow:
     case mm_body::wide: {
         const int mode = p.scaled ? 2 : 0;
-        if (Btype == LFAMD_TYPE_F32)
-            HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_f32");
-        else
-            HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_q8k");
+        if (const int r = prep_kq(Btype, d_B, b_row_bytes, n, k, ws, mode, s))
+            return r;
         if (p.body == mm_body::kq_narrow) {
             HIPCHK(lfamd_launch_gemm_kq(Atype, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, s), "gemm_kq");
         } else {
-            uint8_t *Pp = (uint8_t *)Xm + align_up(n_pad * nb * 32, 256); // after Xh, d8T, Xm
+            uint8_t *Pp = ws + im.parts; // after Xh, d8T, Xm
             HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain | mode, Pp, (size_t)(ws + ws_bytes - Pp), s),
                    "gemm_wide");
         }
         return LFAMD_OK;
     }
     case mm_body::canon32: {
-        void *sT = (uint8_t *)d8T + align_up(nb * 8 * n_pad * 4, 256);
-        const bool q81 = vdt == LFAMD_TYPE_Q8_1;
-        HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, q81 ? sT : nullptr, s), "prep80");
-        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, q81 ? sT : nullptr, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
+        const lfamd_b32_image b32 = lfamd_b32_image_of(k, n);
+        void *sT = vdt == LFAMD_TYPE_Q8_1 ? ws + b32.sT : nullptr;
+        HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, ws + b32.d8T, sT, s), "prep80");
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, ws + b32.d8T, sT, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
         return LFAMD_OK;
     }
     case mm_body::canon: {
-        const int mins16 = Atype == LFAMD_TYPE_Q2_K;
-        if (Btype == LFAMD_TYPE_F32)
-            HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mins16, nullptr, s), "prep_f32");
-        else
-            HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mins16, nullptr, s), "prep_q8k");
+        if (const int r = prep_kq(Btype, d_B, b_row_bytes, n, k, ws, Atype == LFAMD_TYPE_Q2_K, s)) // (mins16)
+            return r;
         // the resident image is the compact one; the MFMA body reads the canonical form, rebuilt here per call
-        void *img = ws + gemm_act_ws(k, n);
+        void *img = ws + im.parts;
         if (Atype == LFAMD_TYPE_IQ4_XS)
             HIPCHK(lfamd_launch_pk4x_expand(d_A, m, k, img, s), "pk4x_expand");
         else
@@ -831,8 +737,9 @@ int lfamd_mul_mat(int Atype, const void *d_A, long m, long k, int Btype, const v
 }
 
 // ---------------------------------------------------------------------------------------------
-// Sibling matrices of one type on the same activations (lfamd_mul_mat_multi): one group-level route, decided and checked by
-// check_multi before anything is launched.
+// Sibling matrices on the same activations: lfamd_mul_mat_multi (one weight type) and lfamd_mul_mat_multi_types (a type per matrix).
+// plan_group / plan_types decide the route of a call and the workspace it needs before anything is launched; check_group checks
+// every matrix against that route, and one switch launches it.  DESIGN.md section 14 lists the routes in this order.
 enum class mm_route {
     none,         // nothing to launch
     each,         // one lfamd_mul_mat per matrix (every one of them checked first)
@@ -843,16 +750,26 @@ enum class mm_route {
     i8_multi,     // the int8 body over the concatenated row blocks
     wide_multi,   // one staging, the wide body over the concatenated row blocks
     q80_lf_multi, // one staging, gemm_lf_q80 over the concatenated row blocks
+    gemv_dual,    // (multi_types) decode, a {Q4_K | Q5_K} group and a Q6_K group: one launch of the dual GEMV
+    wide_dual,    // (multi_types) K-quants of mixed types on one scaled staging: both groups in one loader-wave launch
+    wide_runs,    // (multi_types) K-quants of mixed types on one scaled staging: one wide launch per run of equal types
+    runs,         // (multi_types) a lfamd_mul_mat_multi route per run of equal types (every run checked first)
 };
 
-// sibling matrices of one type on one launch of the int8 body: their row blocks together must make a grid it takes
-static bool multi_i8_ok(int Atype, int count, const long *m, const long *ldc, long k, long n, unsigned flags) {
+// 128-row blocks of a group of matrices, or -1 when one of them has a negative height or a short ldc
+static long group_row_blocks(int count, const long *m, const long *ldc) {
     long rbs = 0;
     for (int j = 0; j < count; j++) {
         if (m[j] < 0 || ldc[j] < m[j])
-            return false;
+            return -1;
         rbs += (m[j] + 127) / 128;
     }
+    return rbs;
+}
+
+// sibling matrices of one type on one launch of the int8 body: their row blocks together must make a grid it takes
+static bool multi_i8_ok(int Atype, int count, const long *m, const long *ldc, long k, long n, unsigned flags) {
+    const long rbs = group_row_blocks(count, m, ldc);
     return rbs > 0 && i8_takes(Atype, k, n, flags, rbs);
 }
 
@@ -860,40 +777,39 @@ static bool multi_i8_ok(int Atype, int count, const long *m, const long *ldc, lo
 static bool wide_group_ok(int Atype, int count, const long *m, const long *ldc, long k, long n, unsigned flags) {
     if (count < 2 || count > 4 || n <= 8 || !kquant(Atype) || k <= 0 || k % 256 || (flags & (LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_GEMM_NARROW)))
         return false;
-    long rbs = 0;
-    for (int j = 0; j < count; j++) {
-        if (m[j] < 0 || ldc[j] < m[j])
-            return false;
-        rbs += (m[j] + 127) / 128;
-    }
-    return rbs * (long)(align_up((size_t)n, 128) / 128) >= 192 || (flags & LFAMD_FLAG_GEMM_WIDE);
+    const long rbs = group_row_blocks(count, m, ldc);
+    return rbs >= 0 && (rbs * (long)(align_up((size_t)n, 128) / 128) >= 192 || (flags & LFAMD_FLAG_GEMM_WIDE));
 }
 
 static bool scaled_ok(int Atype, unsigned flags) { // may the wide body run on scaled operands?
     return !(flags & LFAMD_FLAG_PRECISE) && lfamd_gemm_wide_scaled_ok(Atype, (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0);
 }
 
-static int check_multi(int Atype, int count, const long *m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n, const long *ldc,
-                       const void *d_ws, size_t ws_bytes, unsigned flags, mm_route &route) {
-    route = mm_route::none;
+// One side of a two-type launch: a {Q4_K | Q5_K} group (one of the two types) or a Q6_K group, at most four matrices.
+struct mm_side {
+    int type, count;
+    long m[4], ldc[4];
+    const void *A[4];
+    float *C[4];
+};
+struct mm_group_plan {
+    mm_route route;
+    bool i8_group;    // 2 .. 4 matrices whose row blocks together make a grid the int8 body takes
+    size_t workspace; // bytes the route stages into (0: it takes none)
+    mm_side a, b;     // (plan_types) gemv_dual / wide_dual: the two groups
+};
+
+// The route of sibling matrices of one type (a lfamd_mul_mat_multi call, or one run of a lfamd_mul_mat_multi_types call).
+static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int Btype, size_t b_row_bytes, long n, const long *ldc,
+                                unsigned flags) {
+    mm_group_plan g = {mm_route::each, count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags), 0, {}, {}};
     if (count <= 0 || ((Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED) && n == 0))
-        return LFAMD_OK;
-    if (Btype == LFAMD_TYPE_STAGED_Q8K) { // every matrix must take the image
-        if (!(count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))) // (else: each matrix by itself)
-            for (int j = 0; j < count; j++)
-                if (m[j] > 0 && (ldc[j] < m[j] || !lfamd_mul_mat_takes_staged(Atype, m[j], k, n, flags)))
-                    return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: a matrix of this call does not run the int8 batch body%s", "");
-        route = mm_route::staged_i8;
-        return LFAMD_OK;
-    }
-    route = mm_route::each;
-    if (Btype == LFAMD_TYPE_STAGED_SCALED) { // the route the same call takes on f32 rows
-        if (!d_B || !aligned16(d_B))
-            return fail(LFAMD_ERR_INVALID, "mul_mat_multi: the staged image must be 16-byte aligned%s", "");
-        if (count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))
-            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: these matrices run the int8 batch body together (LFAMD_TYPE_STAGED_Q8K)%s", "");
+        g.route = mm_route::none;
+    else if (Btype == LFAMD_TYPE_STAGED_Q8K) // (check_group: every matrix must take the image, unless the group takes it together)
+        g.route = mm_route::staged_i8;
+    else if (Btype == LFAMD_TYPE_STAGED_SCALED) { // the route the same call takes on f32 rows
         if (wide_group_ok(Atype, count, m, ldc, k, n, flags) && scaled_ok(Atype, flags))
-            route = mm_route::staged_wide;
+            g.route = mm_route::staged_wide;
     } else if (!(count == 1 && sb_takes(Atype, m[0], k, n, flags))) { // (a handful of tokens on one matrix, attn_output / ffn_down: gemm_sb by itself)
         const bool rows_ok = (Btype == LFAMD_TYPE_F32 || Btype == lfamd_vec_dot_type(Atype)) && b_row_bytes >= lfamd_row_size(Btype, k);
         // several tokens (6 and more) on sibling matrices that all take the small-batch MFMA kernel (ffn_gate + ffn_up): the
@@ -904,66 +820,64 @@ static int check_multi(int Atype, int count, const long *m, long k, int Btype, c
         for (int j = 0; j < count && all_sb; j++) // (small siblings — attn_k / attn_v — are faster on the fused GEMV below 8 tokens)
             all_sb = (m[j] > 8192 || (i8_body && n >= 8)) && ldc[j] >= m[j] && sb_takes(Atype, m[j], k, n, flags);
         // one fused launch when the GEMV path applies to every matrix
-        bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && packed(Atype, k) && rows_ok && k > 0 &&
-                    k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || k % 256 == 0);
-        for (int j = 0; j < count && gemv; j++)
-            gemv = m[j] >= 0 && ldc[j] >= m[j];
-        bool q80_lf = count > 1 && count <= 4 && Atype == LFAMD_TYPE_Q8_0 && k > 0 && rows_ok &&
-                      plan_mul_mat(Atype, m[0], k, n, flags).body == mm_body::q80_lf;
-        for (int j = 0; j < count && q80_lf; j++)
-            q80_lf = m[j] >= 0 && ldc[j] >= m[j];
-        size_t need = 0;
+        const bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && packed(Atype, k) && rows_ok && k > 0 &&
+                          k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || k % 256 == 0) && group_row_blocks(count, m, ldc) >= 0;
+        const bool q80_lf = count > 1 && count <= 4 && Atype == LFAMD_TYPE_Q8_0 && k > 0 && rows_ok &&
+                            plan_mul_mat(Atype, m[0], k, n, flags).body == mm_body::q80_lf && group_row_blocks(count, m, ldc) >= 0;
         if (all_sb)
-            route = mm_route::sb_shared, need = align_up(lfamd_gemm_sb_workspace(k), 256);
+            g.route = mm_route::sb_shared, g.workspace = align_up(lfamd_gemm_sb_workspace(k), 256);
         else if (gemv)
-            route = n == 0 ? mm_route::none : mm_route::gemv_multi;
+            g.route = n == 0 ? mm_route::none : mm_route::gemv_multi;
         // Q4_K siblings whose tiles TOGETHER make a grid the int8 body takes (attn_q/k/v of an all-Q4_K layer: 48 row blocks at 512
         // tokens): one staging, one launch over the concatenated row blocks, exact integer dots (6144 x 4096 x 512: 47.5 us against 56.8)
-        else if (count > 1 && count <= 4 && rows_ok && k > 0 && multi_i8_ok(Atype, count, m, ldc, k, n, flags))
-            route = mm_route::i8_multi, need = lfamd_gemm_i8_workspace(k, n);
+        else if (rows_ok && g.i8_group)
+            g.route = mm_route::i8_multi, g.workspace = lfamd_i8_image_of(k, n).bytes;
         // K-quant batches: ONE activation prep for all the matrices, and one launch of the 128 x 128 body over their concatenated
         // row blocks when that grid fills the chip (attn_q/k/v: 48 + 8 + 8 row blocks instead of three launches of which two fill a
         // quarter of the CUs)
         else if (rows_ok && wide_group_ok(Atype, count, m, ldc, k, n, flags))
-            route = mm_route::wide_multi, need = gemm_act_ws(k, n);
+            g.route = mm_route::wide_multi, g.workspace = lfamd_kq_image_of(k, n).parts;
         // Q8_0 batches on sibling matrices: one staging of the activations, one launch over the concatenated row blocks
         else if (q80_lf)
-            route = mm_route::q80_lf_multi, need = lfamd_gemm_lf_workspace(k, n);
-        const bool uses_ws = route == mm_route::sb_shared || route == mm_route::i8_multi || route == mm_route::wide_multi ||
-                             route == mm_route::q80_lf_multi;
-        if (uses_ws && (ws_bytes < need || !d_ws))
-            return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
+            g.route = mm_route::q80_lf_multi, g.workspace = lfamd_gemm_lf_workspace(k, n);
     }
-    if (route == mm_route::each) // one call per matrix: each must pass lfamd_mul_mat's checks before the first is launched
+    return g;
+}
+
+// Everything a group's route needs before its first launch: LFAMD_OK, or the error the call returns.
+static int check_group(const mm_group_plan &g, int Atype, int count, const long *m, long k, int Btype, const void *d_B, size_t b_row_bytes,
+                       long n, const long *ldc, const void *d_ws, size_t ws_bytes, unsigned flags) {
+    if (g.route == mm_route::none)
+        return LFAMD_OK;
+    if (Btype == LFAMD_TYPE_STAGED_Q8K && !g.i8_group) // every matrix must take the image (each one by itself)
+        for (int j = 0; j < count; j++)
+            if (m[j] > 0 && (ldc[j] < m[j] || !lfamd_mul_mat_takes_staged(Atype, m[j], k, n, flags)))
+                return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: a matrix of this call does not run the int8 batch body%s", "");
+    if (Btype == LFAMD_TYPE_STAGED_SCALED && (!d_B || !aligned16(d_B)))
+        return fail(LFAMD_ERR_INVALID, "mul_mat_multi: the staged image must be 16-byte aligned%s", "");
+    if (Btype == LFAMD_TYPE_STAGED_SCALED && g.i8_group)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: these matrices run the int8 batch body together (LFAMD_TYPE_STAGED_Q8K)%s", "");
+    if (g.workspace && (ws_bytes < g.workspace || !d_ws))
+        return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace too small%s", "");
+    if (g.route == mm_route::each) // one call per matrix: each must pass lfamd_mul_mat's checks before the first is launched
         for (int j = 0; j < count; j++) {
             mm_plan p = {};
-            const int r = check_mul_mat(Atype, m[j], k, Btype, d_B, b_row_bytes, n, ldc[j], d_ws, ws_bytes, flags, p);
-            if (r != LFAMD_OK)
+            if (const int r = check_mul_mat(Atype, m[j], k, Btype, d_B, b_row_bytes, n, ldc[j], d_ws, ws_bytes, flags, p))
                 return r;
         }
     return LFAMD_OK;
 }
 
-int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long *m, long k, int Btype, const void *d_B,
-                        size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
+static int launch_group(const mm_group_plan &g, int Atype, int count, const void *const *d_A, const long *m, long k, int Btype,
+                        const void *d_B, size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
                         unsigned flags, void *stream) {
-    (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
-    mm_route route;
-    const int r = check_multi(Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags, route);
-    if (r != LFAMD_OK)
-        return r;
     hipStream_t s = (hipStream_t)stream;
-    const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
-    const size_t n_pad = align_up((size_t)n, 128), nb = (size_t)(k / 256);
-    switch (route) {
-    case mm_route::none:
-        return LFAMD_OK;
+    const lfamd_kq_image im = lfamd_kq_image_of(k, n);
+    switch (g.route) {
     case mm_route::each:
-        for (int j = 0; j < count; j++) {
-            const int rj = lfamd_mul_mat(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, ws_bytes, flags, stream);
-            if (rj != LFAMD_OK)
-                return rj;
-        }
+        for (int j = 0; j < count; j++)
+            if (const int r = lfamd_mul_mat(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, ws_bytes, flags, stream))
+                return r;
         return LFAMD_OK;
     case mm_route::staged_i8:
         for (int j0 = 0; j0 < count; j0 += 4) {
@@ -971,12 +885,6 @@ int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long
             HIPCHK(lfamd_launch_gemm_i8_staged(c, d_A + j0, m + j0, k, d_B, n, d_C + j0, ldc + j0, s), "gemm_i8 (staged input, multi)");
         }
         return LFAMD_OK;
-    case mm_route::staged_wide: {
-        const scaled_image_ptrs im = scaled_image_of(d_B, k, n);
-        HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, im.Xh, im.d8T, im.Xm, n, (long)im.n_pad, d_C, ldc, plain | 2, nullptr, 0, s),
-               "gemm_wide_multi (staged input)");
-        return LFAMD_OK;
-    }
     case mm_route::sb_shared:
         for (int j = 0; j < count; j++)
             HIPCHK(lfamd_launch_gemm_sb(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, j > 0, s), "gemm_sb (multi)");
@@ -989,29 +897,98 @@ int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long
     case mm_route::i8_multi:
         HIPCHK(lfamd_launch_gemm_i8(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, nullptr, s), "gemm_i8 (multi)");
         return LFAMD_OK;
-    case mm_route::wide_multi: {
-        uint8_t *ws = (uint8_t *)d_ws;
-        void *Xh = ws, *d8T = ws + align_up(n_pad * (size_t)k * 2, 256), *Xm = (uint8_t *)d8T + align_up(nb * n_pad * 4, 256);
-        const int mode = scaled_ok(Atype, flags) ? 2 : 0;
-        if (Btype == LFAMD_TYPE_F32)
-            HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_f32");
-        else
-            HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, mode, nullptr, s), "prep_q8k");
-        HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, Xh, d8T, Xm, n, (long)n_pad, d_C, ldc, plain | mode, nullptr, 0, s),
-               "gemm_wide_multi");
+    case mm_route::wide_multi:
+        if (const int r = prep_kq(Btype, d_B, b_row_bytes, n, k, (uint8_t *)d_ws, scaled_ok(Atype, flags) ? 2 : 0, s))
+            return r;
+        [[fallthrough]];
+    case mm_route::staged_wide: { // (staged_wide: the plan asked scaled_ok)
+        const bool staged = g.route == mm_route::staged_wide;
+        const uint8_t *img = (const uint8_t *)(staged ? d_B : d_ws);
+        HIPCHK(lfamd_launch_gemm_wide_multi(Atype, count, d_A, m, k, img, img + im.d8T, img + im.Xm, n, (long)im.n_pad, d_C, ldc,
+                                            ((flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0) | (scaled_ok(Atype, flags) ? 2 : 0), nullptr, 0, s),
+               staged ? "gemm_wide_multi (staged input)" : "gemm_wide_multi");
         return LFAMD_OK;
     }
     case mm_route::q80_lf_multi:
         HIPCHK(lfamd_launch_gemm_lf_q80(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, s), "gemm_lf (Q8_0, multi)");
         return LFAMD_OK;
+    default: // (none)
+        return LFAMD_OK;
+    }
+}
+
+int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long *m, long k, int Btype, const void *d_B,
+                        size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
+                        unsigned flags, void *stream) {
+    (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
+    const mm_group_plan g = plan_group(Atype, count, m, k, Btype, b_row_bytes, n, ldc, flags);
+    const int r = check_group(g, Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags);
+    return r != LFAMD_OK ? r : launch_group(g, Atype, count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags, stream);
+}
+
+// The matrices of a call as the two sides of a two-type launch; false when they do not split so.
+static bool split_pair(int count, const int *Atype, const void *const *d_A, const long *m, float *const *d_C, const long *ldc, mm_side &a,
+                       mm_side &b) {
+    a.type = -1, b.type = LFAMD_TYPE_Q6_K, a.count = b.count = 0;
+    for (int j = 0; j < count; j++) {
+        const int t = Atype[j];
+        if (t != LFAMD_TYPE_Q6_K && ((t != LFAMD_TYPE_Q4_K && t != LFAMD_TYPE_Q5_K) || (a.count && a.type != t)))
+            return false;
+        mm_side &g = t == LFAMD_TYPE_Q6_K ? b : a;
+        if (g.count == 4)
+            return false;
+        g.type = t, g.A[g.count] = d_A[j], g.m[g.count] = m[j], g.ldc[g.count] = ldc[j], g.C[g.count] = d_C[j], g.count++;
+    }
+    return a.count > 0 && b.count > 0;
+}
+
+// Runs of up to four consecutive matrices of one type: fn(j0, j1) for each, until one answers other than LFAMD_OK.
+extern "C++" {
+template <class F> static int each_run(int count, const int *Atype, F fn) {
+    for (int j0 = 0, j1; j0 < count; j0 = j1) {
+        for (j1 = j0 + 1; j1 < count && Atype[j1] == Atype[j0] && j1 - j0 < 4;)
+            j1++;
+        const int r = fn(j0, j1);
+        if (r != LFAMD_OK)
+            return r;
     }
     return LFAMD_OK;
 }
+}
 
-// Sibling mat-muls on the same activations whose weight types may differ (a backend's graph_compute sees attn_q/k/v as
-// three MUL_MAT nodes with one src1; in a Q4_K_M file q and k are Q4_K, v is Q6_K).  Decode (n = 1) with exactly two
-// K-quant types {Q4_K | Q5_K, Q6_K}: ONE launch (gemv_kq_dual_kernel).  Everything else: one lfamd_mul_mat_multi per
-// run of equal types.
+// The route of a lfamd_mul_mat_multi_types call: gemv_dual, wide_dual, wide_runs or runs (a backend's graph_compute sees attn_q/k/v
+// as three MUL_MAT nodes with one src1; in a Q4_K_M file q and k are Q4_K, v is Q6_K).
+static mm_group_plan plan_types(int count, const int *Atype, const void *const *d_A, const long *m, long k, int Btype, const void *d_B,
+                                size_t b_row_bytes, long n, float *const *d_C, const long *ldc, const void *d_ws, size_t ws_bytes,
+                                unsigned flags) {
+    mm_group_plan p = {mm_route::runs, false, 0, {}, {}};
+    const bool paired = split_pair(count, Atype, d_A, m, d_C, ldc, p.a, p.b);
+    const bool rows_ok = (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && b_row_bytes >= lfamd_row_size(Btype, k);
+    // decode (n = 1) with exactly two K-quant types {Q4_K | Q5_K, Q6_K}: ONE launch (gemv_kq_dual_kernel)
+    bool dual = paired && n == 1 && k > 0 && k % 256 == 0 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && rows_ok;
+    for (int j = 0; j < count && dual; j++)
+        dual = m[j] > 0 && ldc[j] >= m[j];
+    if (dual) // (n = 1: none of the routes below applies)
+        p.route = mm_route::gemv_dual;
+    // K-quant batches of mixed types (attn_q/k = Q4_K with attn_v = Q6_K at prefill): the scaled-operand GEMM of every type reads the
+    // SAME staged activations, prepared once (or written by a fused producer: d_B); a workspace too small for them leaves `runs`
+    const bool staged_in = Btype == LFAMD_TYPE_STAGED_SCALED;
+    bool share = n > 8 && count > 1 && k > 0 && k % 256 == 0 &&
+                 !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_FORCE_GENERIC | LFAMD_FLAG_GEMM_NARROW)) && (staged_in ? d_B && aligned16(d_B) : rows_ok);
+    bool mixed = false;
+    for (int j = 0; j < count && share; j++) {
+        share = kquant(Atype[j]) && scaled_ok(Atype[j], flags) && m[j] >= 0 && ldc[j] >= m[j];
+        mixed = mixed || Atype[j] != Atype[0];
+    }
+    const lfamd_kq_image im = lfamd_kq_image_of(k, n);
+    if (share && mixed && (staged_in || (d_ws && ws_bytes >= im.parts))) {
+        const long rb_a = group_row_blocks(p.a.count, p.a.m, p.a.ldc), rb_b = group_row_blocks(p.b.count, p.b.m, p.b.ldc);
+        p.route = paired && lfamd_gemm_wide_dual_ok(rb_a, rb_b, (long)im.n_pad) ? mm_route::wide_dual : mm_route::wide_runs;
+        p.workspace = staged_in ? 0 : im.parts;
+    }
+    return p;
+}
+
 int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_A, const long *m, long k, int Btype,
                               const void *d_B, size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws,
                               size_t ws_bytes, unsigned flags, void *stream) {
@@ -1020,122 +997,46 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
         return LFAMD_OK;
     if (!Atype || !d_A || !m || !d_C || !ldc)
         return fail(LFAMD_ERR_INVALID, "mul_mat_multi_types: null argument%s", "");
-    int ta = -1, tb = -1, na = 0, nb_ = 0;
-    const void *Aa[4], *Ab[4];
-    long ma[4], mb[4], la[4], lb[4];
-    float *Ca[4], *Cb[4];
-    bool dual = n == 1 && count <= 8 && k > 0 && k % 256 == 0 && !(flags & LFAMD_FLAG_FORCE_GENERIC) &&
-                (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && b_row_bytes >= lfamd_row_size(Btype, k);
-    for (int j = 0; j < count && dual; j++) {
-        const int t = Atype[j];
-        if (m[j] <= 0 || ldc[j] < m[j]) {
-            dual = false;
-        } else if (t == LFAMD_TYPE_Q6_K) {
-            if (nb_ == 4)
-                dual = false;
-            else
-                Ab[nb_] = d_A[j], mb[nb_] = m[j], lb[nb_] = ldc[j], Cb[nb_] = d_C[j], nb_++, tb = t;
-        } else if ((t == LFAMD_TYPE_Q4_K || t == LFAMD_TYPE_Q5_K) && (ta < 0 || ta == t)) {
-            if (na == 4)
-                dual = false;
-            else
-                Aa[na] = d_A[j], ma[na] = m[j], la[na] = ldc[j], Ca[na] = d_C[j], na++, ta = t;
-        } else {
-            dual = false;
-        }
+    const mm_group_plan p = plan_types(count, Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags);
+    auto run_plan = [&](int j0, int j1) { return plan_group(Atype[j0], j1 - j0, m + j0, k, Btype, b_row_bytes, n, ldc + j0, flags); };
+    if (p.route == mm_route::runs) { // every run is checked before the first one is launched
+        const int r = each_run(count, Atype, [&](int j0, int j1) {
+            return check_group(run_plan(j0, j1), Atype[j0], j1 - j0, m + j0, k, Btype, d_B, b_row_bytes, n, ldc + j0, d_ws, ws_bytes, flags);
+        });
+        if (r != LFAMD_OK)
+            return r;
     }
-    if (dual && na > 0 && nb_ > 0) {
-        HIPCHK(lfamd_launch_gemv_dual(ta, na, Aa, ma, Ca, la, tb, nb_, Ab, mb, Cb, lb, k, Btype, d_B, b_row_bytes,
-                                      (hipStream_t)stream),
+    hipStream_t s = (hipStream_t)stream;
+    const lfamd_kq_image im = lfamd_kq_image_of(k, n);
+    uint8_t *img = p.workspace ? (uint8_t *)d_ws : (uint8_t *)const_cast<void *>(d_B); // (a staged image has the workspace's layout)
+    switch (p.route) {
+    case mm_route::gemv_dual:
+        HIPCHK(lfamd_launch_gemv_dual(p.a.type, p.a.count, p.a.A, p.a.m, p.a.C, p.a.ldc, p.b.type, p.b.count, p.b.A, p.b.m, p.b.C, p.b.ldc, k,
+                                      Btype, d_B, b_row_bytes, s),
                "gemv_dual");
         return LFAMD_OK;
-    }
-    // Batches whose nodes are all K-quants with a resident layout (attn_q/k = Q4_K with attn_v = Q6_K at prefill): the
-    // scaled-operand GEMM of every type reads the SAME staged activations, so they are prepared once; then one launch of
-    // the loader-wave body per run of equal types.
-    {
-        const bool staged_in = Btype == LFAMD_TYPE_STAGED_SCALED; // (a fused producer wrote the scaled image: d_B, 16-byte aligned)
-        bool share = n > 8 && count > 1 && k > 0 && k % 256 == 0 && !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_FORCE_GENERIC |
-                                                                                LFAMD_FLAG_GEMM_NARROW)) &&
-                     (staged_in ? d_B && ((uintptr_t)d_B & 15) == 0
-                                : (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && b_row_bytes >= lfamd_row_size(Btype, k));
-        const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
-        bool mixed = false;
-        for (int j = 0; j < count && share; j++) {
-            const int t = Atype[j];
-            share = (t == LFAMD_TYPE_Q4_K || t == LFAMD_TYPE_Q5_K || t == LFAMD_TYPE_Q6_K) && lfamd_gemm_wide_scaled_ok(t, plain) &&
-                    m[j] >= 0 && ldc[j] >= m[j];
-            mixed = mixed || t != Atype[0];
-        }
-        const size_t n_pad = align_up((size_t)n, 128), nbk = (size_t)(k / 256);
-        const size_t need = align_up(n_pad * (size_t)k * 2, 256) + align_up(nbk * n_pad * 4, 256) + align_up(n_pad * nbk * 32, 256);
-        if (share && mixed && (staged_in || (d_ws && ws_bytes >= need))) {
-            hipStream_t s = (hipStream_t)stream;
-            uint8_t *ws = staged_in ? (uint8_t *)const_cast<void *>(d_B) : (uint8_t *)d_ws; // (the image has the workspace's layout)
-            void *Xh = ws;
-            void *d8T = ws + align_up(n_pad * (size_t)k * 2, 256);
-            void *Xm = (uint8_t *)d8T + align_up(nbk * n_pad * 4, 256);
-            if (staged_in)
-                ; // nothing to stage
-            else if (Btype == LFAMD_TYPE_F32)
-                HIPCHK(lfamd_launch_prep_f32(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, 2, nullptr, s), "prep_f32");
-            else
-                HIPCHK(lfamd_launch_prep_q8k(d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, Xm, 2, nullptr, s), "prep_q8k");
-            { // {Q4_K | Q5_K, Q6_K} whose tiles fill more than half the chip in one round: one launch for both types
-                const void *Aa[4], *Ab[4];
-                long ma_[4], mb_[4], la[4], lb[4];
-                float *Ca[4], *Cb[4];
-                int ta = -1, na = 0, nbq = 0;
-                bool two = true;
-                for (int j = 0; j < count && two; j++) {
-                    if (Atype[j] == LFAMD_TYPE_Q6_K) {
-                        two = nbq < 4;
-                        if (two)
-                            Ab[nbq] = d_A[j], mb_[nbq] = m[j], lb[nbq] = ldc[j], Cb[nbq] = d_C[j], nbq++;
-                    } else if (ta < 0 || ta == Atype[j]) {
-                        two = na < 4;
-                        if (two)
-                            Aa[na] = d_A[j], ma_[na] = m[j], la[na] = ldc[j], Ca[na] = d_C[j], na++, ta = Atype[j];
-                    } else {
-                        two = false;
-                    }
-                }
-                if (two && na > 0 && nbq > 0) {
-                    hipError_t e = lfamd_launch_gemm_wide_dual(ta, na, Aa, ma_, Ca, la, LFAMD_TYPE_Q6_K, nbq, Ab, mb_, Cb, lb, k, Xh, d8T,
-                                                               Xm, n, (long)n_pad, plain | 2, s);
-                    if (e == hipSuccess)
-                        return LFAMD_OK;
-                    if (e != hipErrorNotSupported)
-                        HIPCHK(e, "gemm_wide_dual");
-                }
-            }
-            for (int j0 = 0; j0 < count;) {
-                int j1 = j0 + 1;
-                while (j1 < count && Atype[j1] == Atype[j0] && j1 - j0 < 4)
-                    j1++;
-                HIPCHK(lfamd_launch_gemm_wide_multi(Atype[j0], j1 - j0, d_A + j0, m + j0, k, Xh, d8T, Xm, n, (long)n_pad, d_C + j0,
-                                                    ldc + j0, plain | 2, nullptr, 0, s),
-                       "gemm_wide_multi");
-                j0 = j1;
-            }
+    case mm_route::wide_dual:
+    case mm_route::wide_runs: // (the plan took scaled operands for every type, so `plain` is 0: mode 2)
+        if (const int r = p.workspace ? prep_kq(Btype, d_B, b_row_bytes, n, k, img, 2, s) : LFAMD_OK)
+            return r;
+        if (p.route == mm_route::wide_dual) {
+            HIPCHK(lfamd_launch_gemm_wide_dual(p.a.type, p.a.count, p.a.A, p.a.m, p.a.C, p.a.ldc, p.b.type, p.b.count, p.b.A, p.b.m, p.b.C,
+                                               p.b.ldc, k, img, img + im.d8T, img + im.Xm, n, (long)im.n_pad, 2, s),
+                   "gemm_wide_dual");
             return LFAMD_OK;
         }
+        return each_run(count, Atype, [&](int j0, int j1) -> int {
+            HIPCHK(lfamd_launch_gemm_wide_multi(Atype[j0], j1 - j0, d_A + j0, m + j0, k, img, img + im.d8T, img + im.Xm, n, (long)im.n_pad,
+                                                d_C + j0, ldc + j0, 2, nullptr, 0, s),
+                   "gemm_wide_multi");
+            return LFAMD_OK;
+        });
+    default: // (runs)
+        return each_run(count, Atype, [&](int j0, int j1) {
+            return launch_group(run_plan(j0, j1), Atype[j0], j1 - j0, d_A + j0, m + j0, k, Btype, d_B, b_row_bytes, n, d_C + j0, ldc + j0,
+                                d_ws, ws_bytes, flags, stream);
+        });
     }
-    // runs of equal types (up to four matrices each): every run is checked before the first one is launched
-    for (int launch = 0; launch < 2; launch++)
-        for (int j0 = 0; j0 < count;) {
-            int j1 = j0 + 1;
-            while (j1 < count && Atype[j1] == Atype[j0] && j1 - j0 < 4)
-                j1++;
-            mm_route route;
-            const int r = launch ? lfamd_mul_mat_multi(Atype[j0], j1 - j0, d_A + j0, m + j0, k, Btype, d_B, b_row_bytes, n, d_C + j0, ldc + j0,
-                                                       d_ws, ws_bytes, flags, stream)
-                                 : check_multi(Atype[j0], j1 - j0, m + j0, k, Btype, d_B, b_row_bytes, n, ldc + j0, d_ws, ws_bytes, flags, route);
-            if (r != LFAMD_OK)
-                return r;
-            j0 = j1;
-        }
-    return LFAMD_OK;
 }
 
 size_t lfamd_mul_mat_id_workspace(int type, long rows, long cols, int experts, long tokens, int thinkers) {

@@ -15,8 +15,7 @@
 // LDS-tiled bodies of the weight GEMMs would not pay here.
 #include "lfamd_device.h"
 #include "../../include/lfamd_hip.h"
-
-extern "C" void lfamd_set_error(const char *msg);
+#include "lfamd_internal.h"
 
 namespace {
 

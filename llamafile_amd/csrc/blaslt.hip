@@ -8,6 +8,7 @@
 //   lfamd_blaslt_gemm(dtype, W, ldw, X, ldx, m, n, k, C, ldc, ws, ws_bytes, stream)
 //   lfamd_launch_rows_to_f16 / _q80_rows_to_f16 / _q80_image     the row-major 16-bit operands
 #include "lfamd_device.h"
+#include "lfamd_internal.h"
 
 #include <dlfcn.h>
 #include <stdlib.h>

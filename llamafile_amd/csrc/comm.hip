@@ -13,6 +13,7 @@
 //     14 latency-bound hops at world 8.  Every spin is bounded (a lost peer sets an error flag instead of hanging).
 #include "lfamd_device.h"
 #include "../../include/lfamd_hip.h"
+#include "lfamd_internal.h"
 #include "oneshot_impl.h"
 
 #include <dlfcn.h>
@@ -23,7 +24,6 @@
 #include <mutex>
 #include <unordered_map>
 
-extern "C" void lfamd_set_error(const char *msg);
 hipError_t lfamd_launch_add_f32(float *y, const float *r, long n, hipStream_t s);
 namespace {
 
@@ -177,13 +177,6 @@ __global__ __launch_bounds__(ONESHOT_THREADS) void oneshot_allreduce_kernel(cons
 }
 
 extern "C" {
-
-int lfamd_oneshot_alloc(void **d_block, size_t bytes);
-int lfamd_oneshot_free(void *d_block);
-int lfamd_comm_allreduce_add_f32(lfamd_comm *c, const float *d_partial, const float *d_residual, float *d_out, long count,
-                                 void *stream);
-size_t lfamd_oneshot_bytes(size_t max_message_bytes);
-int lfamd_comm_destroy(lfamd_comm *c);
 
 int lfamd_comm_unique_id(void *id128) {
     if (!load_rccl())

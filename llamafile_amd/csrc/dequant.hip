@@ -22,6 +22,7 @@
 // and the 31 later rows hit the caches; 4 (one per wave) for index lists, so that a handful of indices still spreads over the chip.
 #include "lfamd_device.h"
 #include "../../include/lfamd_hip.h"
+#include "lfamd_internal.h"
 
 #pragma clang fp contract(off)
 

@@ -24,6 +24,7 @@
 // barrier per super-block, placed so that the NEXT stage has landed before the current one is computed — its first operands
 // are read before the barrier they would otherwise wait behind.
 #include "gemm_wide_impl.h"
+#include "lfamd_internal.h"
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v16i_t __attribute__((ext_vector_type(16)));
@@ -474,8 +475,7 @@ extern "C" int lfamd_gemm_i8_ok(int Atype, long row_blocks128, long n) {
 }
 
 extern "C" size_t lfamd_gemm_i8_workspace(long k, long n) { // Xq, d8T, Xs
-    const size_t n_pad = ((size_t)n + 127) / 128 * 128, nb = (size_t)(k / 256);
-    return n_pad * nb * 256 + n_pad * nb * 4 + n_pad * nb * 32;
+    return lfamd_i8_image_of(k, n).bytes;
 }
 
 // The staged activation image the body reads (what prep_i8_kernel writes, and what the fused producers of norm_quant.hip write
@@ -484,10 +484,8 @@ extern "C" size_t lfamd_gemm_i8_workspace(long k, long n) { // Xq, d8T, Xs
 static hipError_t gemm_i8_go(int count, const void *const *A, const long *m, long k, const void *image, long n, float *const *C, const long *ldc,
                              hipStream_t s) {
     const int nb = (int)(k / 256);
-    const long n_pad = (n + 127) / 128 * 128;
-    const int8_t *Xq = (const int8_t *)image;
-    const float *d8T = (const float *)((const uint8_t *)image + (size_t)n_pad * nb * 256);
-    const _Float16 *Xs = (const _Float16 *)((const uint8_t *)d8T + (size_t)n_pad * nb * 4);
+    const lfamd_i8_image l = lfamd_i8_image_of(k, n);
+    const uint8_t *img = (const uint8_t *)image;
     gemm_mats mats;
     int n_rb = 0;
     mats.count = 0;
@@ -505,7 +503,8 @@ static hipError_t gemm_i8_go(int count, const void *const *A, const long *m, lon
     for (int q = mats.count; q < GEMM_MAX_MATS; q++)
         mats.A[q] = mats.A[0], mats.C[q] = mats.C[0], mats.m[q] = 0, mats.ldc[q] = 0, mats.rb_end[q] = n_rb;
     const int n_ct = (int)((n + I8_COLS - 1) / I8_COLS);
-    gemm_i8_kernel<<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nb, Xq, d8T, Xs, n, n_pad, n_rb, n_ct);
+    gemm_i8_kernel<<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nb, (const int8_t *)img, (const float *)(img + l.d8T),
+                                                           (const _Float16 *)(img + l.Xs), n, (long)l.n_pad, n_rb, n_ct);
     return hipGetLastError();
 }
 
@@ -517,10 +516,11 @@ extern "C" hipError_t lfamd_launch_gemm_i8(int count, const void *const *A, cons
     if (count > GEMM_MAX_MATS || k % 256 || (Btype != LFAMD_TYPE_F32 && Btype != LFAMD_TYPE_Q8_K))
         return hipErrorInvalidValue;
     const int nb = (int)(k / 256);
-    const long n_pad = (n + 127) / 128 * 128;
+    const lfamd_i8_image l = lfamd_i8_image_of(k, n);
+    const long n_pad = (long)l.n_pad;
     int8_t *Xq = (int8_t *)ws;
-    float *d8T = (float *)((uint8_t *)ws + (size_t)n_pad * nb * 256);
-    _Float16 *Xs = (_Float16 *)((uint8_t *)d8T + (size_t)n_pad * nb * 4);
+    float *d8T = (float *)((uint8_t *)ws + l.d8T);
+    _Float16 *Xs = (_Float16 *)((uint8_t *)ws + l.Xs);
     const dim3 pg((unsigned)n_pad, (unsigned)((nb + 15) / 16));
     if (Btype == LFAMD_TYPE_F32)
         prep_i8_kernel<true><<<pg, 512, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nb, Xq, d8T, Xs, src_idx);

@@ -26,6 +26,7 @@
 //   activations : f16(d8 * q8) (quantize_row_q8_0 arithmetic, or the caller's Q8_0 blocks), [quad][token][256 B] in the K order
 //                 above, 16-byte chunks XOR-swizzled by token on the source address.
 #include "gemm_wide_impl.h"
+#include "lfamd_internal.h"
 
 #include <stdlib.h>
 

@@ -23,6 +23,7 @@
 // barrier per super-block; the two partial accumulators meet in LDS at the end.  Tiles are assigned to
 // work-groups XCD-aware so an XCD's work-groups share a token tile.
 #include "gemm_common.h"
+#include "lfamd_internal.h"
 #ifndef GEMM_DIAG
 #define GEMM_DIAG 0
 #endif

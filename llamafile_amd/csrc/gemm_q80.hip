@@ -19,6 +19,7 @@
 //   summation mode per output from the mnpack geometry (q0_is_kahan): wave-uniform fast paths for all-plain and
 //   all-Kahan patches, per-output select otherwise.
 #include "lfamd_device.h"
+#include "lfamd_internal.h"
 
 #define GQ_QUAD 144 // bytes per (token, quad) in the activation image
 #define GQ_QD 128

@@ -20,6 +20,7 @@
 //                              element of the zeroed result, and a + b == b + a: the outcome does not depend on their order
 //                              (bit-identical from run to run), while 4096 x 4096 offers 256 work-groups instead of 128.
 #include "gemm_common.h"
+#include "lfamd_internal.h"
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 

@@ -1,5 +1,6 @@
 // gemm_wide.hip — launchers of the 128 x 128 MFMA body (kernel: gemm_wide_impl.h; instantiations: gemm_wide_*.hip)
 #include "gemm_wide_impl.h"
+#include "lfamd_internal.h"
 
 hipError_t lfamd_wide_go_q4k(WIDE_ARGS);
 hipError_t lfamd_wide_go_q5k(WIDE_ARGS);
@@ -187,16 +188,8 @@ extern "C" int lfamd_gemm_wide_scaled_ok(int Atype, int plain) {
     return !plain && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K);
 }
 
-extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const void *const *A, const long *m, long k,
-                                                   const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
-                                                   float *const *C, const long *ldc, int mode, void *P, size_t P_bytes,
-                                                   hipStream_t s) {
-    if (n <= 0 || count <= 0)
-        return hipSuccess;
-    if (n_pad % WD_COLS || count > GEMM_MAX_MATS)
-        return hipErrorInvalidValue;
-    const int nb = (int)(k / 256);
-    gemm_mats mats;
+// The matrices of a launch with m > 0, padded to GEMM_MAX_MATS with empty ones; returns their row blocks of 128.
+static int fill_gemm_mats(gemm_mats &mats, int count, const void *const *A, const long *m, float *const *C, const long *ldc) {
     int n_rb = 0;
     mats.count = 0;
     mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
@@ -208,10 +201,24 @@ extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const v
         n_rb += (int)((m[j] + 127) / 128);
         mats.rb_end[i] = n_rb;
     }
+    for (int i = mats.count; i < GEMM_MAX_MATS && mats.count > 0; i++)
+        mats.A[i] = mats.A[0], mats.C[i] = mats.C[0], mats.m[i] = 0, mats.ldc[i] = 0, mats.rb_end[i] = n_rb;
+    return n_rb;
+}
+
+extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const void *const *A, const long *m, long k,
+                                                   const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
+                                                   float *const *C, const long *ldc, int mode, void *P, size_t P_bytes,
+                                                   hipStream_t s) {
+    if (n <= 0 || count <= 0)
+        return hipSuccess;
+    if (n_pad % WD_COLS || count > GEMM_MAX_MATS)
+        return hipErrorInvalidValue;
+    const int nb = (int)(k / 256);
+    gemm_mats mats;
+    const int n_rb = fill_gemm_mats(mats, count, A, m, C, ldc);
     if (mats.count == 0)
         return hipSuccess;
-    for (int i = mats.count; i < GEMM_MAX_MATS; i++)
-        mats.A[i] = mats.A[0], mats.C[i] = mats.C[0], mats.m[i] = 0, mats.ldc[i] = 0, mats.rb_end[i] = n_rb;
     const int n_ct = (int)(n_pad / WD_COLS);
     const bool scaled_lw = (mode & 2) && lw_allowed(mode) &&
                            (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K);
@@ -231,26 +238,16 @@ extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const v
 hipError_t lfamd_lw_dual_go(int type_a, const gemm_mats &ma, int n_rb_a, int type_b, const gemm_mats &mb, int n_rb_b, int nb,
                             const void *Xh, const void *d8T, const void *Xm, long n, long n_pad, int n_ct, hipStream_t s);
 
-static int fill_gemm_mats(gemm_mats &mats, int count, const void *const *A, const long *m, float *const *C, const long *ldc) {
-    int n_rb = 0;
-    mats.count = 0;
-    mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
-    for (int j = 0; j < count; j++) {
-        if (m[j] <= 0)
-            continue;
-        const int i = mats.count++;
-        mats.A[i] = (const uint8_t *)A[j], mats.C[i] = C[j], mats.m[i] = m[j], mats.ldc[i] = ldc[j];
-        n_rb += (int)((m[j] + 127) / 128);
-        mats.rb_end[i] = n_rb;
-    }
-    for (int i = mats.count; i < GEMM_MAX_MATS; i++)
-        mats.A[i] = mats.A[0], mats.C[i] = mats.C[0], mats.m[i] = 0, mats.ldc[i] = 0, mats.rb_end[i] = n_rb;
-    return n_rb;
+// Does ONE launch of the 128 x 128 loader-wave body take two groups of matrices (row blocks of 128 rows each; n_pad staged token
+// rows)?  When the combined grid fills more than half the chip in one round; beyond one round the separate launches with their tail
+// handling do as well.
+extern "C" int lfamd_gemm_wide_dual_ok(long row_blocks_a, long row_blocks_b, long n_pad) {
+    const long tiles = (row_blocks_a + row_blocks_b) * (n_pad / WD_COLS);
+    return row_blocks_a > 0 && row_blocks_b > 0 && tiles >= LW_FULL_GRID && tiles <= 256;
 }
 
-// Scaled staged activations, two groups of matrices of two K-quant types (type_b = Q6_K, type_a = Q4_K | Q5_K): ONE launch of
-// the 128 x 128 loader-wave body when the combined grid fills more than half the chip.  Returns hipErrorNotSupported when
-// that launch does not apply (the caller then launches the groups one after the other).
+// Scaled staged activations, two groups of matrices of two K-quant types (type_b = Q6_K, type_a = Q4_K | Q5_K) in that one launch.
+// Precondition: lfamd_gemm_wide_dual_ok (else hipErrorInvalidValue).
 extern "C" hipError_t lfamd_launch_gemm_wide_dual(int type_a, int count_a, const void *const *A_a, const long *m_a,
                                                   float *const *C_a, const long *ldc_a, int type_b, int count_b,
                                                   const void *const *A_b, const long *m_b, float *const *C_b, const long *ldc_b,
@@ -258,13 +255,12 @@ extern "C" hipError_t lfamd_launch_gemm_wide_dual(int type_a, int count_a, const
                                                   int mode, hipStream_t s) {
     if (!(mode & 2) || !lw_allowed(mode) || type_b != LFAMD_TYPE_Q6_K || (type_a != LFAMD_TYPE_Q4_K && type_a != LFAMD_TYPE_Q5_K) ||
         count_a <= 0 || count_b <= 0 || count_a > GEMM_MAX_MATS || count_b > GEMM_MAX_MATS || n_pad % WD_COLS)
-        return hipErrorNotSupported;
+        return hipErrorInvalidValue;
     gemm_mats ma, mb;
     const int n_rb_a = fill_gemm_mats(ma, count_a, A_a, m_a, C_a, ldc_a), n_rb_b = fill_gemm_mats(mb, count_b, A_b, m_b, C_b, ldc_b);
-    const int n_ct = (int)(n_pad / WD_COLS), tiles = (n_rb_a + n_rb_b) * n_ct;
-    if (ma.count == 0 || mb.count == 0 || tiles < LW_FULL_GRID || tiles > 256)
-        return hipErrorNotSupported; // (beyond one round the separate launches with their tail handling do as well)
-    return lfamd_lw_dual_go(type_a, ma, n_rb_a, type_b, mb, n_rb_b, (int)(k / 256), Xh, d8T, Xm, n, n_pad, n_ct, s);
+    if (!lfamd_gemm_wide_dual_ok(n_rb_a, n_rb_b, n_pad))
+        return hipErrorInvalidValue;
+    return lfamd_lw_dual_go(type_a, ma, n_rb_a, type_b, mb, n_rb_b, (int)(k / 256), Xh, d8T, Xm, n, n_pad, (int)(n_pad / WD_COLS), s);
 }
 
 extern "C" hipError_t lfamd_launch_gemm_wide(int Atype, const void *A, long m, long k, const void *Xh, const void *d8T,

@@ -1,5 +1,6 @@
 // gemv.hip — dispatch of the decode GEMVs (kernels: gemv_impl.h; instantiations: gemv_q4k / q5k / q6k / q40 / q41 / q50 / q51 / q2k / q3k / iq4xs / q80.hip)
 #include "gemv_impl.h"
+#include "lfamd_internal.h"
 
 hipError_t lfamd_gemv_go_q4k(GEMV_GO_ARGS);
 hipError_t lfamd_gemv_go_q5k(GEMV_GO_ARGS);

@@ -13,6 +13,7 @@
 // LDS image of one activation column: kpad f32.  For 2-byte weights a lane needs 8 consecutive activations per chunk;
 // they are stored as two 16-byte halves at ((2 chunk + half) * 64 + lane) * 16 so both ds_read_b128 are conflict-free.
 #include "lfamd_device.h"
+#include "lfamd_internal.h"
 
 #define GF_WAVES 8
 #define GF_GROUP 8

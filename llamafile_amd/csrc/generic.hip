@@ -9,6 +9,7 @@
 // units (32 for the legacy 32-blocks), each lane unpacks its unit once and dots it against up to 8
 // activation rows, then the wave reduces with DPP/shuffles.
 #include "lfamd_device.h"
+#include "lfamd_internal.h"
 
 __device__ static const int8_t kvalues_iq4nl_dev[16] = {-127, -104, -83, -65, -49, -35, -22, -10,
                                                         1,    13,   25,  38,  53,  69,  89,  113};

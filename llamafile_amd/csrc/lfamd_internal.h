@@ -1,0 +1,133 @@
+// lfamd_internal.h — what the module's translation units share on the host side: every extern "C" function that one csrc unit
+// defines and another calls (declared once here, so that the defining unit's compiler checks each prototype against its definition;
+// the definitions name the parameters), and the byte layouts of the staged activation images.  Public functions: include/lfamd_hip.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+extern "C" {
+void lfamd_set_error(const char *); // (api.hip: sets lfamd_last_error)
+size_t lfamd_mul_mat_workspace_upto(int, long, long, long);
+// weight images (pack.hip, generic.hip, blaslt.hip)
+hipError_t lfamd_launch_pack_q4k(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pack_q40(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pack_q5k(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pack_q6k(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pack_q80(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pack_raw(const void *, size_t, long, size_t, void *, hipStream_t);
+hipError_t lfamd_launch_scaled_ok(int, long, long, const void *, int *, hipStream_t);
+size_t lfamd_wprep32_bytes(long, long);
+hipError_t lfamd_launch_wprep32(int, const void *, size_t, long, long, void *, hipStream_t);
+size_t lfamd_wprep16_bytes(long, long);
+hipError_t lfamd_launch_wprep16(int, const void *, size_t, long, long, void *, hipStream_t);
+size_t lfamd_wprep8_bytes(long, long);
+hipError_t lfamd_launch_wprep8(int, const void *, size_t, long, long, void *, hipStream_t);
+size_t lfamd_pk_bytes(int, long, long);
+hipError_t lfamd_launch_pk_pack(int, const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pk_expand(int, const void *, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pk4x_pack(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_pk4x_expand(const void *, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_q80_image(const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_get_rows(int, const void *, long, long, const int32_t *, long, long, int, void *, size_t, hipStream_t);
+hipError_t lfamd_launch_unpack(int, const void *, long, long, void *, size_t, hipStream_t);
+// activation staging (pack.hip, quantize.hip, blaslt.hip)
+hipError_t lfamd_launch_quantize(int, const float *, long, long, size_t, void *, size_t, hipStream_t);
+hipError_t lfamd_launch_prep_q8k(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);
+hipError_t lfamd_launch_prep_f32(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);
+hipError_t lfamd_launch_prep80(int, const void *, size_t, long, long, long, void *, void *, void *, hipStream_t);
+hipError_t lfamd_launch_prep_float(int, int, const void *, size_t, long, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_rows_to_16(int, const void *, size_t, long, long, void *, hipStream_t);
+hipError_t lfamd_launch_q80_rows_to_f16(int, const void *, size_t, long, long, void *, hipStream_t);
+// decode GEMVs (gemv.hip, gemv_float.hip)
+hipError_t lfamd_launch_gemv(int, const void *, long, long, int, const void *, size_t, long, float *, long, int, int, hipStream_t);
+hipError_t lfamd_launch_gemv_multi(int, int, const void *const *, const long *, long, int, const void *, size_t, long, float *const *, const long *,
+                                   int, int, hipStream_t);
+hipError_t lfamd_launch_gemv_dual(int, int, const void *const *, const long *, float *const *, const long *, int, int, const void *const *,
+                                  const long *, float *const *, const long *, long, int, const void *, size_t, hipStream_t);
+hipError_t lfamd_launch_gemv_ids(int, int, const void *const *, long, int, const int32_t *, const int *, long, long, int, const void *, size_t,
+                                 float *const *, hipStream_t);
+hipError_t lfamd_launch_gemv_ids_pair(int, const void *, long, int, const int32_t *, int, int, long, long, int, const void *, const void *, size_t,
+                                      float *, float *, hipStream_t);
+int lfamd_gemv_float_ok(int, long, long);
+hipError_t lfamd_launch_gemv_float(int, const void *, long, long, int, const void *, size_t, long, float *, long, hipStream_t);
+// batch bodies (gemm_*.hip, generic.hip)
+bool lfamd_gemm_sb_ok(int, long, long);
+size_t lfamd_gemm_sb_workspace(long);
+hipError_t lfamd_launch_gemm_sb(int, const void *, long, long, int, const void *, size_t, long, float *, long, void *, int, hipStream_t);
+int lfamd_gemm_i8_ok(int, long, long);
+size_t lfamd_gemm_i8_workspace(long, long);
+hipError_t lfamd_launch_gemm_i8(int, const void *const *, const long *, long, int, const void *, size_t, long, float *const *, const long *, void *,
+                                const int32_t *, hipStream_t);
+hipError_t lfamd_launch_gemm_i8_staged(int, const void *const *, const long *, long, const void *, long, float *const *, const long *, hipStream_t);
+hipError_t lfamd_launch_gemm_kq(int, const void *, long, long, const void *, const void *, const void *, long, long, float *, long, hipStream_t);
+// (the wide launchers take `mode`: bit 0 plain body, bit 1 activations staged scaled — gemm_wide.hip)
+int lfamd_gemm_wide_scaled_ok(int, int);
+int lfamd_gemm_wide_dual_ok(long, long, long);
+size_t lfamd_gemm_lw_ksplit_bytes(long, long);
+hipError_t lfamd_launch_gemm_wide(int, const void *, long, long, const void *, const void *, const void *, long, long, float *, long, int, void *,
+                                  size_t, hipStream_t);
+hipError_t lfamd_launch_gemm_wide_multi(int, int, const void *const *, const long *, long, const void *, const void *, const void *, long, long,
+                                        float *const *, const long *, int, void *, size_t, hipStream_t);
+hipError_t lfamd_launch_gemm_wide_dual(int, int, const void *const *, const long *, float *const *, const long *, int, int, const void *const *,
+                                       const long *, float *const *, const long *, long, const void *, const void *, const void *, long, long, int,
+                                       hipStream_t);
+hipError_t lfamd_launch_gemm_wide_moe(int, const void *, long, int, long, long, const void *, const void *, const void *, long, const int *,
+                                      const int *, const int *, int, float *, long, int, hipStream_t);
+size_t lfamd_gemm_lf_workspace(long, long);
+hipError_t lfamd_launch_gemm_lf_q80(int, const void *const *, const long *, long, int, const void *, size_t, long, float *const *, const long *,
+                                    void *, hipStream_t);
+hipError_t lfamd_launch_gemm_lf_float(int, const void *, size_t, long, long, const void *, long, long, float *, long, hipStream_t);
+size_t lfamd_gemm_q80_workspace(long, long);
+hipError_t lfamd_launch_gemm_q80(const void *, long, long, int, const void *, size_t, long, float *, long, void *, int, int, hipStream_t);
+hipError_t lfamd_launch_generic(int, const void *, long, long, int, const void *, size_t, long, float *, long, hipStream_t);
+// the vendor GEMM (blaslt.hip; LFAMD_USE_BLASLT=1)
+bool lfamd_blaslt_ok();
+size_t lfamd_blaslt_workspace();
+hipError_t lfamd_blaslt_gemm(int, const void *, long, const void *, long, long, long, long, float *, long, void *, size_t, hipStream_t);
+// MUL_MAT_ID (moe.hip)
+size_t lfamd_moe_workspace(int, long, long, int, long, int);
+bool lfamd_moe_decode_multi_ok(int, long, int, int, long, unsigned);
+hipError_t lfamd_launch_moe(int, const void *, long, long, int, size_t, int, const void *, size_t, int, long, const int32_t *, int, float *, void *,
+                            size_t, unsigned, hipStream_t);
+hipError_t lfamd_launch_moe_decode_multi(int, int, const void *const *, long, long, int, size_t, int, const void *, size_t, long, const int32_t *,
+                                         int, float *const *, hipStream_t);
+}
+
+// ---- staged activation images for k weights per row and n token rows (n_pad: n rounded up to 128): byte offsets and the total.
+// Fused producers (norm_quant.hip) and the activation preps write them, the batch bodies read them: all take the offsets from here.
+static inline size_t lfamd_up256(size_t v) {
+    return (v + 255) / 256 * 256;
+}
+
+// The K-quant image (LFAMD_TYPE_STAGED_SCALED, and the staging of every K-quant batch body): Xh f16 [nb][n_pad][256], then d8T
+// f32 [nb][n_pad], then Xm f16 [nb][n_pad][16], each starting on 256 bytes; a K-split launch keeps its partial tiles at `parts`.
+struct lfamd_kq_image {
+    size_t n_pad, d8T, Xm, parts;
+};
+static inline lfamd_kq_image lfamd_kq_image_of(long k, long n) {
+    const size_t n_pad = ((size_t)n + 127) / 128 * 128, nb = (size_t)(k / 256), d8T = lfamd_up256(n_pad * (size_t)k * 2);
+    const size_t Xm = d8T + lfamd_up256(nb * n_pad * 4);
+    return {n_pad, d8T, Xm, Xm + lfamd_up256(n_pad * nb * 32)};
+}
+
+// The int8 body's image (LFAMD_TYPE_STAGED_Q8K): Xq int8 [nb][n_pad][256], then d8T f32 [nb][n_pad], then Xs f16 [nb][n_pad][16],
+// packed without padding.
+struct lfamd_i8_image {
+    size_t n_pad, d8T, Xs, bytes;
+};
+static inline lfamd_i8_image lfamd_i8_image_of(long k, long n) {
+    const size_t n_pad = ((size_t)n + 127) / 128 * 128, nb = (size_t)(k / 256), d8T = n_pad * nb * 256, Xs = d8T + n_pad * nb * 4;
+    return {n_pad, d8T, Xs, Xs + n_pad * nb * 32};
+}
+
+// The 32-block image (Q8_0 / Q8_1-quantised activations of the PCL bodies): Xh f16 [nb][n_pad][256], then d8T f32 [nb * 8][n_pad],
+// then sT f32 [nb * 8][n_pad], each starting on 256 bytes.
+struct lfamd_b32_image {
+    size_t n_pad, d8T, sT, bytes;
+};
+static inline lfamd_b32_image lfamd_b32_image_of(long k, long n) {
+    const size_t n_pad = ((size_t)n + 127) / 128 * 128, nb = (size_t)(k / 256), d8T = lfamd_up256(n_pad * (size_t)k * 2);
+    const size_t sT = d8T + lfamd_up256(nb * 8 * n_pad * 4);
+    return {n_pad, d8T, sT, sT + lfamd_up256(nb * 8 * n_pad * 4)};
+}

@@ -12,17 +12,9 @@
 // place.
 #include "lfamd_device.h"
 #include "../../include/lfamd_hip.h"
+#include "lfamd_internal.h"
 
 #include <vector>
-
-extern "C" int lfamd_mul_mat(int, const void *, long, long, int, const void *, size_t, long, float *, long, void *, size_t,
-                             unsigned, void *);
-extern "C" size_t lfamd_mul_mat_workspace(int, long, long, long);
-extern "C" size_t lfamd_mul_mat_workspace_upto(int, long, long, long);
-extern "C" hipError_t lfamd_launch_gemv_ids_pair(int, const void *, long, int, const int32_t *, int, int, long, long, int, const void *,
-                                                 const void *, size_t, float *, float *, hipStream_t);
-extern "C" hipError_t lfamd_launch_gemv_ids(int, int, const void *const *, long, int, const int32_t *, const int *, long, long, int,
-                                            const void *, size_t, float *const *, hipStream_t);
 
 __global__ void moe_gather_kernel(const uint8_t *__restrict__ src, size_t src_stride, size_t row_bytes,
                                   const int32_t *__restrict__ src_idx, uint8_t *__restrict__ dst, long nrows) {
@@ -129,18 +121,12 @@ static size_t moe_grouped_slots(long tokens, int thinkers, int experts) {
     return align_up_((size_t)tokens * thinkers, 128) + (size_t)experts * 128;
 }
 
-extern "C" hipError_t lfamd_launch_prep_q8k(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *,
-                                            hipStream_t);
-extern "C" hipError_t lfamd_launch_prep_f32(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *,
-                                            hipStream_t);
-extern "C" int lfamd_gemm_wide_scaled_ok(int, int);
-extern "C" hipError_t lfamd_launch_gemm_wide_moe(int, const void *, long, int, long, long, const void *, const void *, const void *,
-                                                 long, const int *, const int *, const int *, int, float *, long, int, hipStream_t);
-
+// the routing tables (cnt, poff, slot_row, src_row), then the K-quant image of every slot
+static size_t moe_grouped_tables(long tokens, int thinkers, int experts) {
+    return align_up_((2 * (size_t)experts + 2 * moe_grouped_slots(tokens, thinkers, experts)) * 4, 256);
+}
 static size_t moe_grouped_ws(long cols, long tokens, int thinkers, int experts) {
-    const size_t n_pad = moe_grouped_slots(tokens, thinkers, experts), nb = (size_t)(cols / 256);
-    return align_up_((2 * (size_t)experts + 2 * n_pad) * 4, 256) + align_up_(n_pad * (size_t)cols * 2, 256) +
-           align_up_(nb * n_pad * 4, 256) + align_up_(n_pad * nb * 32, 256);
+    return moe_grouped_tables(tokens, thinkers, experts) + lfamd_kq_image_of(cols, (long)moe_grouped_slots(tokens, thinkers, experts)).parts;
 }
 
 extern "C" size_t lfamd_moe_workspace(int type, long rows, long cols, int experts, long tokens, int thinkers) {
@@ -242,15 +228,11 @@ extern "C" hipError_t lfamd_launch_moe(int type, const void *W, long rows, long 
     if (tokens > 4 && moe_grouped_ok(type, tokens, thinkers, experts) && !(flags & LFAMD_FLAG_FORCE_GENERIC) &&
         (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && cols % 256 == 0 &&
         ws_bytes >= moe_grouped_ws(cols, tokens, thinkers, experts)) {
-        const size_t n_pad = moe_grouped_slots(tokens, thinkers, experts), nbk = (size_t)(cols / 256);
-        uint8_t *p = (uint8_t *)ws;
-        int *cnt = (int *)p, *poff = cnt + experts, *slot_row = poff + experts, *src_row = slot_row + n_pad;
-        p += align_up_((2 * (size_t)experts + 2 * n_pad) * 4, 256);
-        void *Xh = p;
-        p += align_up_(n_pad * (size_t)cols * 2, 256);
-        void *d8T = p;
-        p += align_up_(nbk * n_pad * 4, 256);
-        void *Xm = p;
+        const size_t n_pad = moe_grouped_slots(tokens, thinkers, experts);
+        int *cnt = (int *)ws, *poff = cnt + experts, *slot_row = poff + experts, *src_row = slot_row + n_pad;
+        uint8_t *Xh = (uint8_t *)ws + moe_grouped_tables(tokens, thinkers, experts);
+        const lfamd_kq_image im = lfamd_kq_image_of(cols, (long)n_pad);
+        void *d8T = Xh + im.d8T, *Xm = Xh + im.Xm;
         moe_route_kernel<<<1, 256, align_up_(nr, 16), s>>>(plan, tokens, thinkers, tasks, experts, (int)n_pad, cnt, poff, slot_row,
                                                           src_row);
         hipError_t e2 = hipGetLastError();

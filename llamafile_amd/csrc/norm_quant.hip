@@ -14,8 +14,7 @@
 // (and everything after it) is identical unless the sum sits within 1e-9 relative of a rounding boundary.
 #include "lfamd_device.h"
 #include "../../include/lfamd_hip.h"
-
-extern "C" void lfamd_set_error(const char *msg);
+#include "lfamd_internal.h"
 
 namespace {
 
@@ -355,39 +354,23 @@ __global__ __launch_bounds__(256) void swiglu_scaled_kernel(const float *__restr
 } // namespace
 
 static scaled_image scaled_of(void *image, long k, long nrows) {
-    const size_t nb = (size_t)(k / 256), n_pad = ((size_t)nrows + 127) / 128 * 128;
-    auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
-    scaled_image im;
-    im.Xh = (_Float16 *)image;
-    im.tok_scale = (float *)((uint8_t *)image + up256(n_pad * (size_t)k * 2));
-    im.Xm = (_Float16 *)((uint8_t *)im.tok_scale + up256(nb * n_pad * 4));
-    im.n_pad = (long)n_pad;
-    return im;
+    const lfamd_kq_image l = lfamd_kq_image_of(k, nrows);
+    uint8_t *p = (uint8_t *)image;
+    return {(_Float16 *)p, (float *)(p + l.d8T), (_Float16 *)(p + l.Xm), (long)l.n_pad};
 }
 
 extern "C" size_t lfamd_staged_scaled_size(long k, long nrows) { // = the staging part of lfamd_mul_mat_workspace for these bodies
-    if (k <= 0 || k % 256 || nrows < 0)
-        return 0;
-    const size_t nb = (size_t)(k / 256), n_pad = ((size_t)nrows + 127) / 128 * 128;
-    auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
-    return up256(n_pad * (size_t)k * 2) + up256(nb * n_pad * 4) + up256(n_pad * nb * 32);
+    return k <= 0 || k % 256 || nrows < 0 ? 0 : lfamd_kq_image_of(k, nrows).parts;
 }
 
 static staged_image staged_of(void *image, long k, long nrows) {
-    const long nb = k / 256, n_pad = (nrows + 127) / 128 * 128;
-    staged_image im;
-    im.Xq = (int8_t *)image;
-    im.d8T = (float *)((uint8_t *)image + (size_t)n_pad * nb * 256);
-    im.Xs = (_Float16 *)((uint8_t *)im.d8T + (size_t)n_pad * nb * 4);
-    im.n_pad = n_pad;
-    return im;
+    const lfamd_i8_image l = lfamd_i8_image_of(k, nrows);
+    uint8_t *p = (uint8_t *)image;
+    return {(int8_t *)p, (float *)(p + l.d8T), (_Float16 *)(p + l.Xs), (long)l.n_pad};
 }
 
-extern "C" size_t lfamd_staged_q8k_size(long k, long nrows) {
-    if (k <= 0 || k % 256 || nrows < 0)
-        return 0;
-    const size_t n_pad = ((size_t)nrows + 127) / 128 * 128, nb = (size_t)(k / 256);
-    return n_pad * nb * 256 + n_pad * nb * 4 + n_pad * nb * 32; // = lfamd_gemm_i8_workspace(k, nrows)
+extern "C" size_t lfamd_staged_q8k_size(long k, long nrows) { // = lfamd_gemm_i8_workspace(k, nrows)
+    return k <= 0 || k % 256 || nrows < 0 ? 0 : lfamd_i8_image_of(k, nrows).bytes;
 }
 
 extern "C" int lfamd_rms_norm_quantize(const float *d_x, size_t x_row_bytes, const float *d_weight, float eps, long nrows, long k,

@@ -4,6 +4,7 @@
 // Counterpart of the reference's weight upload, ggml_backend_cuda_buffer_set_tensor
 // (ggml-cuda.cu.patch:16971-16977): the backend owns the device copy, so it may choose its layout.
 #include "lfamd_device.h"
+#include "lfamd_internal.h"
 
 // ---------------------------------------------------------------------------------------------
 // Q4_K -> P4K.  One thread per output dword of the qs part, one per 16-byte header.

@@ -6,6 +6,7 @@
 // bit (same divisions, roundf / nearest-even, first-maximum rule of q8_K), and emit llamafile's
 // Q8_K field order {d, bsums, qs} (ggml-common.h.patch:25-35).
 #include "lfamd_device.h"
+#include "lfamd_internal.h"
 
 // one wave (64 threads) handles two 32-blocks
 template <bool Q81>
