@@ -169,7 +169,9 @@ int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags);
 
 /* ---- activations --------------------------------------------------------------------------
  * f32 rows -> the reference's activation block format (vec_dot_type: Q8_0, Q8_1 or Q8_K in
- * llamafile's field order).  Same rounding as the scalar reference quantisers. */
+ * llamafile's field order).  Same rounding as the scalar reference quantisers.  cols a multiple of the block (32; Q8_K: 256),
+ * y_row_bytes at least the row's size, x rows 4-byte and Q8_K output rows 4-byte (Q8_0 / Q8_1: 2-byte) aligned, at most 65535
+ * rows per call, no NULL pointer: otherwise LFAMD_ERR_INVALID before any launch.  nrows <= 0 is LFAMD_OK with nothing done. */
 int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long cols, size_t x_row_bytes,
                         void *d_y, size_t y_row_bytes, void *stream);
 
@@ -267,12 +269,31 @@ int lfamd_mul_mat_takes_staged_scaled(int Atype, long m, long k, long n, unsigne
  * reference rms_norm_f32, ggml-cuda.cu.patch:14926-14960), written as the reference's Q8_K activation blocks
  * (quantize_row_q8_K, llamafile field order) to d_yq and / or as f32 to d_yf (either may be NULL; d_weight may be NULL = 1).
  * The mat-muls behind the norm then take Btype = Q8_K: no quantisation left in their prologue.  k % 256 == 0;
- * vec_dot_type must be Q8_K (the K-quant and IQ4_XS weights' activation format). */
+ * vec_dot_type must be Q8_K (the K-quant and IQ4_XS weights' activation format) or one of the two staged images above.
+ * Requirements of both producers, checked before any launch (LFAMD_ERR_INVALID, nothing written):
+ *   - f32 operands (d_x, d_gate, d_up, d_weight, d_yf) are 16-byte aligned and their row strides multiples of 16 bytes (rows are
+ *     read and written as float4); input pointers are not NULL; d_weight has k elements;
+ *   - Q8_K rows (d_yq with vec_dot_type Q8_K) are 4-byte aligned, yq_row_bytes a multiple of 4 and at least k / 256 * 292;
+ *   - a staged image (d_yq) is 16-byte aligned and lfamd_staged_q8k_size / lfamd_staged_scaled_size(k, nrows) bytes long: the
+ *     whole image is written, its padding tokens nrows .. roundup(nrows, 128) as zeros; yq_row_bytes is ignored;
+ *   - at least one of d_yq, d_yf is given; d_yq = NULL writes f32 only, whatever vec_dot_type says; the bytes of either output
+ *     do not depend on whether the other is requested;
+ *   - nrows >= 0 (0: LFAMD_OK, nothing launched); lfamd_swiglu_quantize takes at most 65408 rows (one grid row per token of the
+ *     padded image);
+ *   - no output may overlap an input or the other output (the kernels read through __restrict__ pointers and re-read their
+ *     inputs after the first stores).
+ * Domain: finite inputs.  A 256-block whose largest |y| is non-zero and below about 4e-37 has no Q8_K representation (-128 / max overflows, in
+ * the reference quantiser as here).  The scaled image forms 2^(9 - ilogb(max |y| of the row)) in f32: rows whose largest |y| is
+ * non-zero and below 2^-118 (about 3e-36) overflow it, so the "magnitude is not limited" of the scaled bodies above holds from
+ * there up; an all-zero row is exact (scale 1).  eps = 0 on an all-zero row gives NaN, as the reference does. */
 int lfamd_rms_norm_quantize(const float *d_x, size_t x_row_bytes, const float *d_weight, float eps, long nrows, long k,
                             int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes, void *stream);
 
 /* The step in front of ffn_down, fused the same way: y = silu(gate) * up, silu(x) = x / (1 + expf(-x)) (silu_f32,
- * ggml-cuda.cu.patch:16172-16179, + the MUL node), written as Q8_K blocks to d_yq and / or f32 to d_yf.  k % 256 == 0. */
+ * ggml-cuda.cu.patch:16172-16179, + the MUL node), written as Q8_K blocks to d_yq and / or f32 to d_yf.  k % 256 == 0.  The
+ * operations are those three in that order, each rounded to f32 — not (gate * up) / (1 + e) and no reciprocal-multiply; expf is
+ * the device library's (measured within 1 unit in the last place of the exact exponential on the tests' inputs).  Same
+ * requirements and domain as lfamd_rms_norm_quantize; at most 65408 rows. */
 int lfamd_swiglu_quantize(const float *d_gate, size_t gate_row_bytes, const float *d_up, size_t up_row_bytes, long nrows, long k,
                           int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes, void *stream);
 

@@ -299,6 +299,8 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
         return fail(LFAMD_ERR_UNSUPPORTED, "quantize_rows: unsupported activation type%s", "");
     if (cols % lfamd_blck_size(vec_dot_type) || y_row_bytes < lfamd_row_size(vec_dot_type, cols))
         return fail(LFAMD_ERR_INVALID, "quantize_rows: bad shape%s", "");
+    if (nrows > 65535 || (nrows > 0 && cols > 0 && (!d_x || !d_y))) // (one grid row per input row: the launch's y limit)
+        return fail(LFAMD_ERR_INVALID, "quantize_rows: null pointer or more than 65535 rows%s", "");
     HIPCHK(lfamd_launch_quantize(vec_dot_type, d_x, nrows, cols, x_row_bytes, d_y, y_row_bytes, (hipStream_t)stream),
            "quantize_rows");
     return LFAMD_OK;

@@ -378,7 +378,7 @@ extern "C" int lfamd_rms_norm_quantize(const float *d_x, size_t x_row_bytes, con
                                        void *stream) {
     const bool scaled = d_yq && vec_dot_type == LFAMD_TYPE_STAGED_SCALED; // d_yq = an image of lfamd_staged_scaled_size(k, nrows) bytes
     const bool staged = scaled || (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_Q8K); // ... of lfamd_staged_q8k_size(k, nrows) bytes
-    if (nrows < 0 || k <= 0 || k % 256 || (d_yq && vec_dot_type != LFAMD_TYPE_Q8_K && !staged) || (!d_yq && !d_yf) ||
+    if (nrows < 0 || k <= 0 || k % 256 || (d_yq && vec_dot_type != LFAMD_TYPE_Q8_K && !staged) || (!d_yq && !d_yf) || !d_x ||
         ((uintptr_t)d_x & 15) || (x_row_bytes & 15) || ((uintptr_t)d_weight & 15) || ((uintptr_t)d_yf & 15) || (yf_row_bytes & 15) ||
         ((uintptr_t)d_yq & (staged ? 15 : 3)) || (!staged && (yq_row_bytes & 3))) {
         lfamd_set_error("lfamd_rms_norm_quantize: k must be a multiple of 256, output format Q8_K (or the staged image, 16-byte aligned), "
