@@ -819,19 +819,6 @@ __global__ __launch_bounds__(1024) void gemm_sb16i_kernel(const uint8_t *__restr
     }
 }
 
-static int lfamd_num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
-            cus = p.multiProcessorCount;
-        if (cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 extern "C" {
 
 size_t lfamd_gemm_sb_workspace(long k) { // Xh, d8T, Xm

@@ -169,19 +169,6 @@ __global__ __launch_bounds__(GF_WAVES * 64) void gemv_float_kernel(const uint8_t
     }
 }
 
-static int gf_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
-            n = p.multiProcessorCount;
-        if (n <= 0)
-            n = 256;
-    }
-    return n;
-}
-
 // elements per group of chunks; the LDS image of a column is k rounded up to it
 static int gf_group_elems(int Atype) {
     return (Atype == LFAMD_TYPE_F32 ? 256 : 512) * GF_GROUP;
@@ -209,8 +196,8 @@ static hipError_t gf_go(const void *A, long m, long k, const void *B, size_t brb
         const size_t smem = (size_t)nc * kpad * 4;
         const long per_cu = smem <= 72 * 1024 ? 2 : 1;
         long grid = (npairs + GF_WAVES - 1) / GF_WAVES;
-        if (grid > gf_num_cus() * per_cu)
-            grid = gf_num_cus() * per_cu;
+        if (grid > lfamd_num_cus() * per_cu)
+            grid = lfamd_num_cus() * per_cu;
 #define GF_CASE(NC)                                                                                                    \
     case NC: {                                                                                                         \
         auto kernel = gemv_float_kernel<ATYPE, BTYPE, NC>;                                                             \

@@ -1,4 +1,5 @@
-// gemv.hip — wave-reduction GEMV kernels for the batch-1 (decode) case and small batches n <= 8.
+// gemv_impl.h — wave-reduction GEMV kernels of the K-quant and 32-block types for the batch-1 (decode) case and small batches
+// n <= 8: activation staging, per-type traits, kernels.  Launched from gemv.hip (the plan); the Q8_0 kernel: gemv_q80_impl.h.
 //
 // Replaces the reference's mul_mat_vec_q + quantize_q8_1 pair (ggml-cuda.cu.patch:14428-14575,
 // 15259-15293: 32-wide warps, dp4a with a scalar fallback on gfx950) and follows the CPU
@@ -20,21 +21,9 @@
 // weight loads is issued BEFORE the activation staging so HBM latency overlaps it, and the next
 // chunk is always in flight while the current one is consumed.
 #pragma once
-#include "lfamd_device.h"
-#include <stdlib.h>
+#include "gemv_common.h"
 
-// LDS image of one Q8_K activation block for the K-quant GEMVs.  A lane = (gsel, h) reads its 64 code
-// bytes (two groups g = 2gsel+gi, four K-steps dd each) with four ds_read_b128, its 8 half-sums with
-// one more, its 4 sub-block sums with a ds_read_b64.
-//   [0,256)    codes: 8-byte groups at position pos = 16 gsel + 8 h + 4 gi + dd
-//   [256,320)  hb  : int16 sum of each 8-byte group, same position order
-//   [320,352)  ps  : int16 sum of K-step pairs (dd = 2e, 2e+1): position 8 gsel + 4 h + 2 gi + e
-//   [352,384)  d   : f32 block scale (Q8_K: one; Q8_0-quantised activations for the legacy 32-block types: eight;
-//                    Q8_1: eight dwords {f16 d, f16 s = d * sum(q)} like the block_q8_1 header)
-#define XBLK 384
-#define XBLK_HB 256
-#define XBLK_PS 320
-#define XBLK_D 352
+// (the LDS image of one Q8_K activation block, XBLK, and the launch's LDS layout kq_lds_of: gemv_launch.h)
 
 // Within every 8-byte group the codes (y0..y7) are stored as (y0,y4,y1,y5 | y2,y6,y3,y7): the order
 // in which (x & 0x0F0F0F0F) and ((x>>4) & 0x0F0F0F0F) expose the nibbles of a packed K-step dword.
@@ -54,6 +43,16 @@ __device__ static inline int put_group(uint8_t *dst, int grp, uint32_t y0, uint3
 __device__ static inline void put_pair(uint8_t *dst, int grp, int hs_even_plus_odd) {
     const int pp = ((grp & 16) >> 1) | ((grp & 1) << 2) | ((grp & 8) >> 2) | ((grp >> 2) & 1);
     *(int16_t *)(dst + XBLK_PS + 2 * pp) = (int16_t)hs_even_plus_odd;
+}
+
+// a group and, written by the lane of its even K-step, the pair sum with group grp ^ 2, which the lane two on holds (DPP: all
+// lanes of the quad active).  Returns the pair sum.
+__device__ static inline int put_group_pair(uint8_t *dst, int grp, uint32_t y0, uint32_t y1) {
+    const int hs = put_group(dst, grp, y0, y1);
+    const int pair = hs + (int)dpp_u32<DPP_XOR2>((uint32_t)hs);
+    if ((grp & 2) == 0)
+        put_pair(dst, grp, pair);
+    return pair;
 }
 
 // already-quantised Q8_K rows (llamafile field order {d, bsums[16], qs[256]}); blockDim % 32 == 0
@@ -123,15 +122,6 @@ __device__ static inline void quantise_piece_q8k(uint8_t *dst, const float (&v)[
     }
     if (l16 == 0)
         *(float *)(dst + XBLK_D) = d;
-}
-
-__device__ static inline void load_piece(float (&v)[16], const float *x, int p) {
-    const float4 *src = (const float4 *)(x + (size_t)p * 16);
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        float4 f = src[e];
-        v[4 * e + 0] = f.x, v[4 * e + 1] = f.y, v[4 * e + 2] = f.z, v[4 * e + 3] = f.w;
-    }
 }
 
 __device__ static inline void stage_f32_as_q8k(uint8_t *lds, const uint8_t *X, size_t x_row_bytes, long col0, int nc,
@@ -651,67 +641,7 @@ struct iq4c_traits {
     }
 };
 
-// Up to GEMV_MAX_MATS weight matrices of one type and row length that consume the SAME activations
-// (attn_q/k/v, ffn_gate/up) are served by one launch: their half-tiles are concatenated.
-#define GEMV_MAX_MATS 4
-struct gemv_mats {
-    const uint8_t *A[GEMV_MAX_MATS];
-    float *C[GEMV_MAX_MATS];
-    long m[GEMV_MAX_MATS];
-    long ldc[GEMV_MAX_MATS];
-    int ht_end[GEMV_MAX_MATS]; // exclusive prefix of half-tile counts
-    int count;
-    // GGML_OP_MUL_MAT_ID at decode (IDS kernels only): matrix j is expert ids[id_idx[j]] of the stack at A[j]
-    const int32_t *ids;
-    long expert_bytes;
-    int id_idx[GEMV_MAX_MATS];
-    int experts;
-};
-
-#ifndef GEMV_DIAG
-#define GEMV_DIAG 0
-#endif
-#if GEMV_DIAG // development: in-kernel s_memtime stamps of two work-groups (never in the product build)
-static __device__ unsigned long long g_gemv_stamps[4 * 16 * 16];
-extern "C" __attribute__((weak)) int lfamd_debug_gemv_stamps(unsigned long long *dst) { // per TU; dev only
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemv_stamps), sizeof(g_gemv_stamps));
-}
-// entry / exit time and placement (HW_ID, XCC_ID) of wave 0 of every work-group
-static __device__ unsigned long long g_gemv_wg[512 * 4];
-extern "C" __attribute__((weak)) int lfamd_debug_gemv_wgs(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemv_wg), sizeof(g_gemv_wg));
-}
-#define GWG(slot)                                                                                                \
-    do {                                                                                                         \
-        if (blockIdx.x < 512 && threadIdx.x == 0) {                                                              \
-            g_gemv_wg[blockIdx.x * 4 + (slot)] = __builtin_amdgcn_s_memrealtime();                               \
-            if ((slot) == 0) {                                                                                   \
-                g_gemv_wg[blockIdx.x * 4 + 2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |  \
-                                                ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32); \
-                gwg_clk0 = __builtin_amdgcn_s_memtime();                                                         \
-            } else { /* shader-clock cycles of this work-group's life: with the 100 MHz stamps, the clock it ran at */ \
-                g_gemv_wg[blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memtime() - gwg_clk0;                         \
-            }                                                                                                    \
-        }                                                                                                        \
-    } while (0)
-#define GSTAMP()                                                                                                 \
-    do {                                                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if ((blockIdx.x == 0 || blockIdx.x == 100) && lane == 0 && stamp_n < 16)                                  \
-            g_gemv_stamps[((blockIdx.x ? 1 : 0) * 16 + wave) * 16 + stamp_n++] = __builtin_amdgcn_s_memrealtime(); \
-        __builtin_amdgcn_sched_barrier(0);                                                                       \
-    } while (0)
-// (diagnostic only: drain the loads first, so the stamp is the arrival time of the item's weights)
-#define GSTAMP_ARRIVAL()                                                                                         \
-    do {                                                                                                         \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                         \
-        GSTAMP();                                                                                                \
-    } while (0)
-#else
-#define GSTAMP()
-#define GSTAMP_ARRIVAL()
-#define GWG(slot)
-#endif
+// (gemv_mats, the by-value table of a launch's matrices: gemv_launch.h; the GEMV_DIAG stamps: gemv_common.h)
 
 // ---------------------------------------------------------------------------------------------
 // Decode body (ONE activation row).  What the stamps of the body above showed on 4096 x 4096 (tools/gemv_stamps.py):
@@ -840,10 +770,7 @@ __device__ static inline void stage_f32_q8k_wave2(uint8_t *dst, const float4 va,
     const uint32_t y0 = nz ? y[0] : 0u, y1 = nz ? y[1] : 0u;
     const float d = nz ? 1.0f / iscale : 0.0f;
     const int grp = lane & 31;
-    const int hs = put_group(dst, grp, y0, y1);
-    const int other = (int)dpp_u32<DPP_XOR2>((uint32_t)hs); // group grp ^ 2
-    if ((grp & 2) == 0)
-        put_pair(dst, grp, hs + other);
+    put_group_pair(dst, grp, y0, y1);
     if (grp == 0)
         *(float *)(dst + XBLK_D) = d;
 }
@@ -866,11 +793,7 @@ __device__ static inline void stage_f32_q80_wave2(uint8_t *dst, const float4 va,
         y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
     }
     const int grp = lane & 31;
-    const int hs = put_group(dst, grp, y[0], y[1]);
-    const int other = (int)dpp_u32<DPP_XOR2>((uint32_t)hs);
-    if ((grp & 2) == 0)
-        put_pair(dst, grp, hs + other);
-    const int pair = hs + other; // groups grp, grp ^ 2; with the neighbour pair: the four groups of the 32-block
+    const int pair = put_group_pair(dst, grp, y[0], y[1]); // groups grp, grp ^ 2; with the neighbour pair: the four groups of the 32-block
     const int sum = pair + (int)dpp_u32<DPP_XOR1>((uint32_t)pair); // (all lanes active: a DPP source lane must be)
     if ((grp & 3) == 0)
         put_scale_q80<S1>(dst, grp >> 2, d, sum);
@@ -905,12 +828,13 @@ __device__ static inline void stage_quantised_wave(uint8_t *dst, const uint8_t *
                     *(float *)(dst + XBLK_D + 4 * (grp >> 2)) = h2f(hdr[0]);
             }
         }
-        const int hs = put_group(dst, grp, y0, y1);
-        const int other = (int)dpp_u32<DPP_XOR2>((uint32_t)hs); // group grp ^ 2
-        if ((grp & 2) == 0)
-            put_pair(dst, grp, hs + other);
+        put_group_pair(dst, grp, y0, y1);
     }
 }
+
+// a loaded uint4 as the four floats it holds
+#define KQ_F4(u) make_float4(__builtin_bit_cast(float, (u).x), __builtin_bit_cast(float, (u).y), __builtin_bit_cast(float, (u).z), \
+                           __builtin_bit_cast(float, (u).w))
 
 // The body of a GEMV work-group: work-group `bid` of `gdim` over the half-tiles of `mats` (the plain kernel passes its
 // block index and grid size; the two-type kernel gives each type its own sub-grid).
@@ -919,7 +843,8 @@ __device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, cons
                                              long col0, int n_ht, const int bid, const int gdim, uint8_t *lds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i16 = lane & 15, h = (lane >> 4) & 1, gsel = lane >> 5;
-    float *red = (float *)(lds + (size_t)NC * nb * XBLK); // [2][NW][NC][16]
+    const kq_lds lay = kq_lds_of(NC, nb, NW, 16);
+    float *red = (float *)(lds + lay.red); // [2][NW][NC][16]
 #if GEMV_DIAG
     int stamp_n = 0;
 #endif
@@ -936,14 +861,19 @@ __device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, cons
     // returns zeros without touching memory and keeps the counted waits exact.
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const uint32_t rt_bytes = (uint32_t)nb * TR::TILE;
-    auto issue = [&](typename TR::chunk &ch, int f) {
-        const int tile_i = f / cpt, chunk_i = f - tile_i * cpt;
-        long ht = (long)bid + (long)tile_i * gdim;
+    // the matrix that half-tile `ht` of the launch belongs to
+    auto mat_of = [&](long ht) __attribute__((always_inline)) {
         int j = 0;
 #pragma unroll
         for (int jj = 1; jj < GEMV_MAX_MATS; jj++)
             if (jj < mats.count && ht >= mats.ht_end[jj - 1])
                 j = jj;
+        return j;
+    };
+    auto issue = [&](typename TR::chunk &ch, int f) {
+        const int tile_i = f / cpt, chunk_i = f - tile_i * cpt;
+        long ht = (long)bid + (long)tile_i * gdim;
+        const int j = mat_of(ht);
         const uint8_t *A = mats.A[j];
         bool have = f < total;
         if constexpr (IDS) { // expert picked on the device: no routing-table read-back, graph-capturable
@@ -1002,11 +932,7 @@ __device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, cons
                 for (int w = 0; w < NW; w++)
                     v += rb[(w * NC + c) * 16 + i];
                 long ht = (long)bid + (long)tile_i * gdim;
-                int j = 0;
-#pragma unroll
-                for (int jj = 1; jj < GEMV_MAX_MATS; jj++)
-                    if (jj < mats.count && ht >= mats.ht_end[jj - 1])
-                        j = jj;
+                const int j = mat_of(ht);
                 if (j > 0)
                     ht -= mats.ht_end[j - 1];
                 const long row = (ht >> 1) * 32 + (ht & 1) * 16 + i;
@@ -1057,15 +983,16 @@ __device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, cons
         __builtin_amdgcn_sched_barrier(0);
         issue(bufA, 0);
         __builtin_amdgcn_sched_barrier(0);
-        uint8_t *dummy = (uint8_t *)(red + 2 * NW * NC * 16) + (size_t)wave * XBLK;
+        // (= lds + lay.dummy + wave * XBLK, stepped from `red` in floats here and in gemv_kq_body1: with the byte form hipcc moves
+        // the LDS base add of the f32 16 x 2 kernels across a scheduling barrier; this form keeps their code as it was)
+        uint8_t *dummy = (uint8_t *)(red + (lay.dummy - lay.red) / sizeof(float)) + (size_t)wave * XBLK;
 #pragma unroll
         for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int u = 0; u < GEMV_CH; u++) {
                 const int b = wave + NW * u;
                 uint8_t *dst = b < nb ? lds + (size_t)(c * nb + b) * XBLK : dummy;
-                const float4 v = make_float4(__builtin_bit_cast(float, xv[c][u].x), __builtin_bit_cast(float, xv[c][u].y),
-                                             __builtin_bit_cast(float, xv[c][u].z), __builtin_bit_cast(float, xv[c][u].w));
+                const float4 v = KQ_F4(xv[c][u]);
                 if constexpr (TR::ACT == LFAMD_TYPE_Q8_K)
                     stage_f32_q8k_wave(dst, v, lane);
                 else
@@ -1187,7 +1114,8 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i16 = lane & 15, h = (lane >> 4) & 1, gsel = lane >> 5;
     constexpr int RW = PAIR ? 32 : 16; // result rows per item: a half-tile, or (PAIR) both half-tiles of a 32-row tile
-    float *red = (float *)(lds + (size_t)nb * XBLK); // [2][NW][RW]
+    const kq_lds lay = kq_lds_of(1, nb, NW, RW);
+    float *red = (float *)(lds + lay.red); // [2][NW][RW]
 #if GEMV_DIAG
     int stamp_n = 0;
     unsigned long long gwg_clk0 = 0;
@@ -1336,15 +1264,13 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
         // staging is straight-line code (a block past the row is loaded as zeros through the descriptor and staged
         // into the wave's dummy slot): with a branch per block hipcc merges its vmcnt bookkeeping at the joins and
         // makes the second block wait for the WEIGHTS.
-        uint8_t *dummy = (uint8_t *)(red + 2 * NW * RW) + (size_t)wave * XBLK;
+        uint8_t *dummy = (uint8_t *)(red + (lay.dummy - lay.red) / sizeof(float)) + (size_t)wave * XBLK;
         if constexpr (early)
             KQ_ADVANCE(ci);
         else
             KQ_ISSUE(bufA);
         __builtin_amdgcn_sched_barrier(0);
         GSTAMP();
-#define KQ_F4(u) make_float4(__builtin_bit_cast(float, (u).x), __builtin_bit_cast(float, (u).y), __builtin_bit_cast(float, (u).z), \
-                           __builtin_bit_cast(float, (u).w))
 #define KQ_STAGE_GROUP(j0)                                                                                             \
     if constexpr (JX == 1) {                                                                                           \
         const int b = wave + NW * (j0);                                                                                \
@@ -1370,7 +1296,6 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
                 xv[j] = buf_ld16(rx, x_off(j0, j));
             KQ_STAGE_GROUP(j0)
         }
-#undef KQ_F4
 #undef KQ_STAGE_GROUP
     } else {
         if constexpr (early)
@@ -1381,22 +1306,16 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
         if constexpr (PRE1 && JX == 1) {
             if (wave < nb && lane < 32) {
                 uint8_t *dst = lds + (size_t)wave * XBLK;
-                const int hs = put_group(dst, lane, pq.x, pq.y);
-                const int other = (int)dpp_u32<DPP_XOR2>((uint32_t)hs);
-                if ((lane & 2) == 0)
-                    put_pair(dst, lane, hs + other);
+                put_group_pair(dst, lane, pq.x, pq.y);
                 if (lane == 0)
                     *(uint32_t *)(dst + XBLK_D) = pd;
             }
         } else if constexpr (PRE1) {
             { // both half-waves, straight-line (a block past the row was fetched as zeros and lands in the dummy slot)
-                uint8_t *dummy = (uint8_t *)(red + 2 * NW * RW) + (size_t)wave * XBLK;
+                uint8_t *dummy = (uint8_t *)(red + (lay.dummy - lay.red) / sizeof(float)) + (size_t)wave * XBLK;
                 uint8_t *dst = pre_b < nb ? lds + (size_t)pre_b * XBLK : dummy;
                 const int grp = lane & 31;
-                const int hs = put_group(dst, grp, pq.x, pq.y);
-                const int other = (int)dpp_u32<DPP_XOR2>((uint32_t)hs);
-                if ((grp & 2) == 0)
-                    put_pair(dst, grp, hs + other);
+                put_group_pair(dst, grp, pq.x, pq.y);
                 if (grp == 0)
                     *(uint32_t *)(dst + XBLK_D) = pd;
             }
@@ -1485,634 +1404,84 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq_dual_kernel(const uint8_t *__
 }
 
 // ---------------------------------------------------------------------------------------------
-// Q8_0 x Q8_0, bit-exact restatement of tinyBLAS_Q0_AVX2::gemm (tinyblas_cpu.h:934-971).
-// One wave = 8 weight rows, lane = (r = lane>>3, j = lane&7) owns f32 lane j of row r's accumulator
-// Cv; blocks are visited in order l = 0..nblocks-1 exactly like the reference's loop, so every
-// rounding is the same:  a = f32(dA)*f32(dB);  b = f32(int dot of bytes 4j..4j+3);
-// Cv = fma(a, b, Cv)   or, on a PRECISE tile, madder (tinyblas_cpu.h:203-209) with the compiler's
-// contraction of sub(mul(a,b),e) into fma(a,b,-e).
+// One translation unit per weight type (gemv_*.hip) instantiates its kernels by naming them here and exports the lookup that
+// gemv.hip launches through (the 8 column counts x 2 activation types x chunk variants of every type used to compile serially
+// in one 140-second file).  Which (waves, chunk) pairs exist is the plan's range (gemv.hip: lfamd_gemv_plan_of); anything
+// else answers nullptr.
 
-// LDS image of the Q8_0 activations, per QUAD of four 32-blocks (the unit a weight tile covers): for each of the
-// eight dword positions j the four blocks' dwords side by side (a lane = (row r, position j) takes its four
-// activation dwords with ONE ds_read_b128; the eight rows of a wave read the same 128 bytes: broadcast), then the
-// four block scales as f32 (one more ds_read_b128, uniform).  8 ds_read_b32 per quad became 2 ds_read_b128.
-#define X80_QUAD 144
-#define X80_QD 128
-// quads (1 KiB per wave each) kept in flight per wave: the row's blocks MUST be visited in order by one lane
-// (bit-exact f32 chain), so a matrix offers only m/8 waves (2 per CU at m = 4096) and memory-level parallelism
-// has to come from depth.  n = 1: 32 (a whole k = 4096 row group in flight, 192 ring VGPRs); batches: 16.
-#define Q80_WAVES 2  // waves per work-group (8 rows each) sharing one staged activation image
-
-// MODE: 0 = every output plain fma, 1 = every output Kahan (uniform for n = 1: tinyblas_cpu.h:797-925),
-// 2 = per-output choice from the mnpack geometry (small batches n > 1)
-// sibling matrices that share the activations (attn_q/k/v, ffn_gate/up) run as ONE launch over their concatenated
-// 8-row groups: a 1024-row matrix alone is 128 waves, each a serial k-long chain — three such launches cost three times
-// the chain latency, one launch costs it once.  The mnpack geometry (Kahan choice) stays per matrix.
-struct q80_mats {
-    const uint8_t *A[GEMV_MAX_MATS];
-    float *C[GEMV_MAX_MATS];
-    long m[GEMV_MAX_MATS];
-    long ldc[GEMV_MAX_MATS];
-    long rg_end[GEMV_MAX_MATS]; // exclusive prefix of row-group counts
-    int count;
-};
-
-template <int NC, int BT, int MODE, int Q80_DEPTH>
-__global__ __launch_bounds__(Q80_WAVES * 64) void gemv_q80_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, long col0, int nblocks,
-                                                                 int nquads, long n_total, int vregs32, int precise,
-                                                                 const q80_mats mats) {
-    // (activation pointer and sizes lead the argument list: they arrive preloaded in SGPRs — Makefile,
-    // -amdgpu-kernarg-preload-count — and the activation loads below need nothing else)
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane >> 3, j = lane & 7;
-#if GEMV_DIAG
-    int stamp_n = 0;
-#endif
-    GSTAMP();
-    // the first two activation pieces of this thread go out before anything else: they need only the preloaded leading
-    // arguments, while the matrix pick below waits for three dependent rounds of scalar loads
-    float va0[16], vb0[16];
-    if constexpr (BT == LFAMD_TYPE_F32) {
-        const float *x0 = (const float *)(B + col0 * b_row_bytes);
-        const int pieces0 = nblocks * 2;
-        if ((int)threadIdx.x < pieces0)
-            load_piece(va0, x0, threadIdx.x);
-        if ((int)threadIdx.x + Q80_WAVES * 64 < pieces0)
-            load_piece(vb0, x0, threadIdx.x + Q80_WAVES * 64);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    long rg = (long)blockIdx.x * Q80_WAVES + wave;
-    int mj = 0;
-#pragma unroll
-    for (int jj = 1; jj < GEMV_MAX_MATS; jj++)
-        if (jj < mats.count && rg >= mats.rg_end[jj - 1])
-            mj = jj;
-    if (mj > 0)
-        rg -= mats.rg_end[mj - 1];
-    const uint8_t *__restrict__ A = mats.A[mj];
-    float *__restrict__ C = mats.C[mj];
-    const long m = mats.m[mj], ldc = mats.ldc[mj];
-    const long n_rg = (m + 7) / 8;
-    const long row = rg * 8 + r;
-    // bounds-checked, unconditional weight loads (zeros past the row group / for an idle wave): keeps
-    // hipcc's counted vmcnt exact so Q80_DEPTH KiB per wave really stay in flight
-    const uint32_t rg_bytes = (uint32_t)nquads * P80_TILE;
-    const lfamd_rsrc rA = make_rsrc(A + (size_t)(rg < n_rg ? rg : 0) * rg_bytes, rg < n_rg ? rg_bytes : 0u);
-
-    uint4 qa[Q80_DEPTH];
-    uint2 ds[Q80_DEPTH];
-    auto issue = [&](int s, int L) {
-        qa[s] = buf_ld16_nt(rA, (uint32_t)L * P80_TILE + lane * 16);
-        ds[s] = buf_ld8(rA, (uint32_t)L * P80_TILE + P80_D + r * 8);
-    };
-
-    if constexpr (BT == LFAMD_TYPE_F32) {
-        // quantize_row_q8_0 (upstream): d = amax/127, id = 1/d, q = roundf(x*id); 16 floats per lane,
-        // two lanes per 32-block.  The first piece of each thread is fetched BEFORE the weights (vmcnt
-        // retires in order), the weights are issued, then the activations are quantised under their flight.
-        const int pieces = nblocks * 2, nthr = Q80_WAVES * 64;
-        for (int c = 0; c < NC; c++) {
-            const float *x = (const float *)(B + (col0 + c) * b_row_bytes);
-            // two pieces per thread and round: both loads go out together (one memory latency per round, not two)
-            for (int p0 = 0; p0 < pieces; p0 += 2 * nthr) {
-                const int pa = p0 + threadIdx.x, pb = pa + nthr;
-                float va[16], vb[16];
-                if (c == 0 && p0 == 0) { // (fetched at the top of the kernel)
-#pragma unroll
-                    for (int e = 0; e < 16; e++)
-                        va[e] = va0[e], vb[e] = vb0[e];
-                } else {
-                    if (pa < pieces)
-                        load_piece(va, x, pa);
-                    if (pb < pieces)
-                        load_piece(vb, x, pb);
-                }
-                if (c == 0 && p0 == 0) {
-#pragma unroll
-                    for (int s = 0; s < Q80_DEPTH; s++)
-                        issue(s, s);
-                }
-                auto quantise = [&](const float (&v)[16], int p) {
-                    float amax = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < 16; e++)
-                        amax = fmaxf(amax, fabsf(v[e]));
-                    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-                    const float d = amax / 127.0f;
-                    const float id = d != 0.0f ? 1.0f / d : 0.0f;
-                    uint32_t y[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int e = 0; e < 16; e++) {
-                        int q = (int)roundf(v[e] * id);
-                        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-                    }
-                    const int l = p >> 1, hf = p & 1;
-                    uint8_t *dst = lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4;
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        *(uint32_t *)(dst + (4 * hf + e) * 16) = y[e];
-                    if (hf == 0)
-                        *(float *)(dst + X80_QD) = h2f(f2h_bits(d)); // the block stores d as f16
-                };
-                // (pieces is even and nthr a multiple of 64: the lane pair (2i, 2i+1) of a block is either both in or out)
-                if (pa < pieces)
-                    quantise(va, pa);
-                if (pb < pieces)
-                    quantise(vb, pb);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < Q80_DEPTH; s++)
-            issue(s, s);
-        for (int idx = threadIdx.x; idx < NC * nblocks * 9; idx += Q80_WAVES * 64) {
-            int c = idx / (nblocks * 9), rem = idx % (nblocks * 9);
-            int l = rem / 9, w = rem % 9;
-            const uint8_t *y = B + (col0 + c) * b_row_bytes + (size_t)l * 34;
-            uint32_t v;
-            if (w < 8) {
-                const uint16_t *p = (const uint16_t *)(y + 2 + 4 * w); // 34-byte blocks: 2-byte aligned
-                v = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-            } else {
-                v = __builtin_bit_cast(uint32_t, h2f(*(const uint16_t *)y));
-            }
-            *(uint32_t *)(lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4 + (w < 8 ? w * 16 : X80_QD)) = v;
-        }
-    }
-    GSTAMP();
-    __syncthreads();
-    GSTAMP();
-
-    bool kahan[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++)
-        kahan[c] = MODE == 2 ? q0_is_kahan(row < m ? row : m - 1, col0 + c, m, n_total, vregs32 != 0, precise != 0) : MODE == 1;
-
-    float Cv[NC], Ce[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++)
-        Cv[c] = Ce[c] = 0.0f;
-
-    // One block: a = f32(dA)*f32(dB), b = f32(int dot of bytes 4j..4j+3), then the reference's update.  The update is a
-    // chain of dependent f32 ops (four per block under Kahan) that ONE lane must run in block order; everything else
-    // (scale products, integer dots) is independent of it.  A row offers a single wave no other work, so the loop is
-    // software-pipelined by hand: the products of quad L+1 are prepared (prep) before the chain of quad L runs and
-    // fill its latency bubbles (measured: the fused form spent ~80 cycles per block, 4-5 us per k = 4096 row).
-    struct prepd {
-        float a[4][NC], b[4][NC];
-    };
-    auto prep = [&](int sl, int L, prepd &P) {
-        const uint4 q4 = qa[sl];
-        const uint2 d2 = ds[sl];
-        const uint32_t qw[4] = {q4.x, q4.y, q4.z, q4.w};
-        const float da[4] = {h2f((uint16_t)(d2.x & 0xffff)), h2f((uint16_t)(d2.x >> 16)), h2f((uint16_t)(d2.y & 0xffff)),
-                             h2f((uint16_t)(d2.y >> 16))};
-        const int Lc = L < nquads ? L : nquads - 1; // clamped: the LDS reads are unconditional
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const uint8_t *xb = lds + (size_t)(c * nquads + Lc) * X80_QUAD;
-            const uint4 xq4 = *(const uint4 *)(xb + j * 16);
-            const float4 xd4 = *(const float4 *)(xb + X80_QD);
-            const uint32_t xq[4] = {xq4.x, xq4.y, xq4.z, xq4.w};
-            const float xd[4] = {xd4.x, xd4.y, xd4.z, xd4.w};
-#pragma unroll
-            for (int dd = 0; dd < 4; dd++) {
-                P.a[dd][c] = da[dd] * xd[dd];
-                P.b[dd][c] = (float)sdot4(qw[dd], xq[dd], 0);
-            }
-        }
-    };
-    auto chain = [&](const prepd &P, int dd) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const float a = P.a[dd][c], bq = P.b[dd][c];
-            if constexpr (MODE == 0) {
-                Cv[c] = __builtin_fmaf(a, bq, Cv[c]);
-            } else if constexpr (MODE == 1) {
-                const float y = __builtin_fmaf(a, bq, -Ce[c]);
-                const float t = Cv[c] + y;
-                Ce[c] = (t - Cv[c]) - y;
-                Cv[c] = t;
-            } else { // branch-free select
-                const float plain = __builtin_fmaf(a, bq, Cv[c]);
-                const float y = __builtin_fmaf(a, bq, -Ce[c]);
-                const float t = Cv[c] + y;
-                const float e2 = (t - Cv[c]) - y;
-                Cv[c] = kahan[c] ? t : plain;
-                Ce[c] = kahan[c] ? e2 : 0.0f;
-            }
-        }
-    };
-
-    // Blocks past the row (zero padding of the last quad, zero-filled prefetch slots) must NOT run: a Kahan
-    // step with a*b = 0 still folds the pending compensation into the sum.  Full quads run unguarded.
-    const int nq_full = nblocks >> 2;
-    prepd P[2];
-    prep(0, 0, P[0]);
-    issue(0, Q80_DEPTH);
-    // rounds of Q80_DEPTH full quads run without a branch in the body (k = 4096 and 14336: every round);
-    // the remainder round carries the guards
-    int L0 = 0;
-    for (; L0 + Q80_DEPTH <= nq_full; L0 += Q80_DEPTH) {
-#pragma unroll
-        for (int s = 0; s < Q80_DEPTH; s++) {
-            const int sn = (s + 1) % Q80_DEPTH;
-            prep(sn, L0 + s + 1, P[(s + 1) & 1]); // slot sn holds quad L+1
-            issue(sn, L0 + s + 1 + Q80_DEPTH);    // and is refilled as soon as its registers are read
-            const prepd &Pc = P[s & 1];
-            chain(Pc, 0);
-            chain(Pc, 1);
-            chain(Pc, 2);
-            chain(Pc, 3);
-        }
-    }
-    if (L0 < nquads) {
-#pragma unroll
-        for (int s = 0; s < Q80_DEPTH; s++) {
-            const int L = L0 + s;
-            const int sn = (s + 1) % Q80_DEPTH;
-            prep(sn, L + 1, P[(s + 1) & 1]);
-            const prepd &Pc = P[s & 1];
-            if (L < nq_full) {
-                chain(Pc, 0);
-                chain(Pc, 1);
-                chain(Pc, 2);
-                chain(Pc, 3);
-            } else if (L == nq_full) {
-                if (4 * L + 0 < nblocks)
-                    chain(Pc, 0);
-                if (4 * L + 1 < nblocks)
-                    chain(Pc, 1);
-                if (4 * L + 2 < nblocks)
-                    chain(Pc, 2);
-            }
-        }
-    }
-    GSTAMP();
-    // hsum(__m256), tinyblas_cpu.h:277-296: ((v0+v4)+(v2+v6)) + ((v1+v5)+(v3+v7))
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        float v = Cv[c];
-        v = v + __shfl_xor(v, 4, 64);
-        v = v + __shfl_xor(v, 2, 64);
-        v = v + __shfl_xor(v, 1, 64);
-        if (j == 0 && row < m)
-            C[(col0 + c) * ldc + row] = v;
-    }
+// n = 1: {8 x 2, 16 x 1, 16 x 2} plain and with the early first issue; 32-row items (16 x 1 only) where the type takes them
+template <typename TR, int BT, bool ROWS32>
+static const void *kq_kernel_1(int variant, int nw, int ch) {
+    const int form = nw * 10 + ch;
+    if (variant == LFAMD_GEMV_PLAIN)
+        return form == 82    ? (const void *)gemv_kq_kernel<TR, 1, BT, 8, 2>
+               : form == 161 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1>
+               : form == 162 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 2>
+                             : nullptr;
+    if (variant == LFAMD_GEMV_EARLY)
+        return form == 82    ? (const void *)gemv_kq_kernel<TR, 1, BT, 8, 2, false, true>
+               : form == 161 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1, false, true>
+               : form == 162 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 2, false, true>
+                             : nullptr;
+    if constexpr (ROWS32)
+        if (variant == LFAMD_GEMV_ROWS32 && form == 161)
+            return (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1, false, false, true>;
+    return nullptr;
 }
 
-// ---------------------------------------------------------------------------------------------
-
-// ---------------------------------------------------------------------------------------------
-
-static int g_num_cus = 0;
-
-static int num_cus() {
-    if (!g_num_cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
-            g_num_cus = p.multiProcessorCount;
-        if (g_num_cus <= 0)
-            g_num_cus = 256;
-    }
-    return g_num_cus;
+// n = 2..8: {16 x 1, 8 x 2, 8 x 4}, plain
+template <typename TR, int BT, int NC>
+static const void *kq_kernel_n(int nw, int ch) {
+    const int form = nw * 10 + ch;
+    return form == 161  ? (const void *)gemv_kq_kernel<TR, NC, BT, 16, 1>
+           : form == 82 ? (const void *)gemv_kq_kernel<TR, NC, BT, 8, 2>
+           : form == 84 ? (const void *)gemv_kq_kernel<TR, NC, BT, 8, 4>
+                        : nullptr;
 }
 
-// which types take 32-row items on long walks (launch_kq): the ones whose dot is long enough for a second, independent one to
-// fill its gaps.  128256 x 4096, 16-row -> 32-row items: Q6_K 82.0 -> 73.7 us, Q2_K 44.6 -> 40.8, Q3_K 50.3 -> 44.9, IQ4_XS
-// 58.1 -> 55.4; the light dots lose a little: Q4_K 47.4 -> 47.7, Q5_K 58.1 -> 58.5, Q4_0 46.0 -> 47.6 (65536 rows: 27.0 -> 28.2)
-template <typename TR>
-struct kq_pair_items {
-    static constexpr bool value = false;
-};
-template <>
-struct kq_pair_items<q6k_traits> {
-    static constexpr bool value = true;
-};
-template <int TYPE>
-struct kq_pair_items<pk_traits<TYPE>> {
-    static constexpr bool value = true;
-};
-template <>
-struct kq_pair_items<iq4c_traits> {
-    static constexpr bool value = true;
-};
-
-template <typename TR, int NC, int BT, int NW, int CH>
-static hipError_t launch_kq(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    int nb = (int)(k / 256);
-    size_t smem = (size_t)NC * nb * XBLK + 2 * NW * NC * 16 * sizeof(float) + (size_t)NW * XBLK; // (+ dummy slots)
-    // persistent grid: 16 waves per CU, every work-group the same number of half-tiles
-    const int max_wg = (16 / NW) * num_cus();
-    const int per_wg = (n_ht + max_wg - 1) / max_wg;
-    const int grid = (n_ht + per_wg - 1) / per_wg;
-    auto go = [&](auto kernel) {
-        if (smem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess)
-                return e;
-        }
-        kernel<<<grid, NW * 64, smem, s>>>((const uint8_t *)B, brb, col0, nb, n_ht, grid, mats.A[0], mats.count, mats);
-        return hipGetLastError();
-    };
-    if constexpr (NC == 1 && NW == 16 && CH == 1 && kq_pair_items<TR>::value) {
-        // Long walks (output.weight: 63 half-tiles per work-group) take items of a full 32-row tile — both half-tiles in
-        // flight together, ONE barrier + reduce + store per 74 KB instead of per 37 KB; same arithmetic per row, same bits.
-        // 128256 x 4096 Q6_K: 82.8 -> 73.6 us (5.2 -> 5.9 TB/s); 32000 x 4096: 23.6 -> 22.8 (types: kq_pair_items).  Short walks lose to the
-        // coarser division of the tiles over the work-groups (28672 x 4096, 3.5 tiles each: 13.1 -> 14.3 us), hence the bound.
-        // LFAMD_GEMV_PAIR_MIN=<half-tiles per work-group> moves it (0 = never).
-        static const int pair_min = getenv("LFAMD_GEMV_PAIR_MIN") ? atoi(getenv("LFAMD_GEMV_PAIR_MIN")) : 16;
-        if (pair_min > 0 && per_wg >= pair_min) {
-            const int n_t = n_ht / 2, per_t = (n_t + max_wg - 1) / max_wg, grid_t = (n_t + per_t - 1) / per_t;
-            const size_t smem_t = smem + 2 * NW * 16 * sizeof(float);
-            auto kernel = gemv_kq_kernel<TR, NC, BT, NW, CH, false, false, true>;
-            if (smem_t > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_t);
-                if (e != hipSuccess)
-                    return e;
-            }
-            kernel<<<grid_t, NW * 64, smem_t, s>>>((const uint8_t *)B, brb, col0, nb, n_ht, grid_t, mats.A[0], mats.count, mats);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (NC == 1) {
-        if (mats.count == 1) // one matrix: the variant that issues its first weight loads from the preloaded arguments
-            return go(gemv_kq_kernel<TR, NC, BT, NW, CH, false, true>);
-    }
-    return go(gemv_kq_kernel<TR, NC, BT, NW, CH>);
+template <typename TR, int BT, bool ROWS32>
+static const void *kq_kernel(int variant, int nc, int nw, int ch) {
+    static const void *(*const cols[])(int, int) = {kq_kernel_n<TR, BT, 2>, kq_kernel_n<TR, BT, 3>, kq_kernel_n<TR, BT, 4>, kq_kernel_n<TR, BT, 5>,
+                                                    kq_kernel_n<TR, BT, 6>, kq_kernel_n<TR, BT, 7>, kq_kernel_n<TR, BT, 8>};
+    if (nc == 1)
+        return kq_kernel_1<TR, BT, ROWS32>(variant, nw, ch);
+    return nc >= 2 && nc <= 8 && variant == LFAMD_GEMV_PLAIN ? cols[nc - 2](nw, ch) : nullptr;
 }
 
-template <typename TRA, typename TRB, int BT, int NW, int CH>
-static hipError_t launch_kq_dual_nw(const gemv_mats &ma, int n_ht_a, const gemv_mats &mb, int n_ht_b, int nb, const void *B,
-                                    size_t brb, hipStream_t s) {
-    const size_t smem = (size_t)nb * XBLK + 2 * NW * 16 * sizeof(float) + (size_t)NW * XBLK; // (+ dummy slots)
-    // one persistent grid of at most one work-group per CU, split between the types so that the slower side finishes
-    // first: a Q6_K half-tile costs about 1.35 Q4_K / Q5_K ones (dot instructions and bytes), and with equal tiles per
-    // work-group the few Q6_K work-groups of attn_v set the launch's length (7.06 -> see DESIGN §4)
-    const int max_wg = num_cus();
-    int grid_a = 0, grid_b = 0;
-    long best = -1;
-    for (int pb = 1; pb <= n_ht_b; pb++) {
-        const int gb = (n_ht_b + pb - 1) / pb;
-        if (gb >= max_wg)
-            continue;
-        const int pa = (n_ht_a + (max_wg - gb) - 1) / (max_wg - gb);
-        const long cost = (long)pa * 100 > (long)pb * 135 ? (long)pa * 100 : (long)pb * 135;
-        if (best < 0 || cost < best)
-            best = cost, grid_b = gb, grid_a = (n_ht_a + pa - 1) / pa;
-    }
-    if (best < 0) { // (more Q6_K half-tiles than CUs can never be one per work-group: equal shares)
-        const int per_wg = (n_ht_a + n_ht_b + max_wg - 1) / max_wg;
-        grid_a = (n_ht_a + per_wg - 1) / per_wg, grid_b = (n_ht_b + per_wg - 1) / per_wg;
-    }
-    auto kernel = gemv_kq_dual_kernel<TRA, TRB, BT, NW, CH>;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess)
-            return e;
-    }
-    kernel<<<grid_a + grid_b, NW * 64, smem, s>>>((const uint8_t *)B, brb, nb, n_ht_a, n_ht_b, grid_a, grid_b, ma, mb);
-    return hipGetLastError();
-}
-
-template <typename TRA, typename TRB, int BT>
-static hipError_t launch_kq_dual(const gemv_mats &ma, int n_ht_a, const gemv_mats &mb, int n_ht_b, long k, const void *B,
-                                 size_t brb, hipStream_t s) {
-    const int nb = (int)(k / 256);
-    if (nb <= 16)
-        return launch_kq_dual_nw<TRA, TRB, BT, 16, 1>(ma, n_ht_a, mb, n_ht_b, nb, B, brb, s);
-    return launch_kq_dual_nw<TRA, TRB, BT, 16, 2>(ma, n_ht_a, mb, n_ht_b, nb, B, brb, s);
-}
-
-// both launches' half-tiles (n_ht each) on one grid: half of the CUs' work-groups per expert
+// the expert forms (MUL_MAT_ID at decode): {8 x 2, 16 x 1, 16 x 2} for one row, {16 x 1, 16 x 2} for the pair of rows
 template <typename TR, int BT>
-static hipError_t launch_kq_ids_pair(const gemv_mats &ma, const gemv_mats &mb, int n_ht, long k, const void *Ba, const void *Bb, size_t brb,
-                                     hipStream_t s) {
-    const int nb = (int)(k / 256);
-    constexpr int NW = 16;
-    const size_t smem = (size_t)nb * XBLK + 2 * NW * 16 * sizeof(float) + (size_t)NW * XBLK;
-    const int max_wg = num_cus() / 2 > 0 ? num_cus() / 2 : 1;
-    const int per_wg = (n_ht + max_wg - 1) / max_wg;
-    const int g1 = (n_ht + per_wg - 1) / per_wg;
-    auto go = [&](auto kernel) {
-        if (smem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess)
-                return e;
-        }
-        kernel<<<2 * g1, NW * 64, smem, s>>>((const uint8_t *)Ba, (const uint8_t *)Bb, brb, nb, n_ht, n_ht, g1, g1, ma, mb);
-        return hipGetLastError();
-    };
-    // (round 3, 8 waves x two work-groups per CU for this launch: Mixtral decode pass 1.712 -> 1.919 ms; 16 waves stay)
-    if (nb <= 16)
-        return go(gemv_kq_ids_pair_kernel<TR, BT, NW, 1>);
-    return go(gemv_kq_ids_pair_kernel<TR, BT, NW, 2>);
+static const void *kq_kernel_ids(int variant, int nw, int ch) {
+    const int form = nw * 10 + ch;
+    if (variant == LFAMD_GEMV_EXPERT)
+        return form == 82    ? (const void *)gemv_kq_kernel<TR, 1, BT, 8, 2, true>
+               : form == 161 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1, true>
+               : form == 162 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 2, true>
+                             : nullptr;
+    if (variant == LFAMD_GEMV_EXPERT_PAIR)
+        return form == 161   ? (const void *)gemv_kq_ids_pair_kernel<TR, BT, 16, 1>
+               : form == 162 ? (const void *)gemv_kq_ids_pair_kernel<TR, BT, 16, 2>
+                             : nullptr;
+    return nullptr;
 }
 
-template <typename TR, int BT>
-static hipError_t launch_kq_ids(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, hipStream_t s) {
-    const int nb = (int)(k / 256);
-    constexpr int NW = 16;
-    const size_t smem = (size_t)nb * XBLK + 2 * NW * 16 * sizeof(float) + (size_t)NW * XBLK; // (+ dummy slots)
-    const int max_wg = num_cus();
-    const int per_wg = (n_ht + max_wg - 1) / max_wg;
-    const int grid = (n_ht + per_wg - 1) / per_wg;
-    // gate + up experts in one launch (4 x 896 half-tiles of 16 super-blocks, 14 per 16-wave work-group): every item ends in a
-    // work-group barrier, and two independent 8-wave work-groups per CU hide each other's — Mixtral decode pass 1.823 ->
-    // 1.706 ms (548 -> 586 tokens/s).  Shorter walks keep the 16-wave form (see launch_kq_pick).
-    // (the 16-wave form with 32-row items, seven per work-group, was measured too: 1.748 ms per pass against 1.702 for this one)
-    if (nb <= 16 && n_ht >= 8 * num_cus()) {
-        constexpr int NW8 = 8;
-        const size_t smem8 = (size_t)nb * XBLK + 2 * NW8 * 16 * sizeof(float) + (size_t)NW8 * XBLK;
-        const int max8 = 2 * num_cus(), per8 = (n_ht + max8 - 1) / max8, grid8 = (n_ht + per8 - 1) / per8;
-        auto kernel = gemv_kq_kernel<TR, 1, BT, NW8, 2, true>;
-        kernel<<<grid8, NW8 * 64, smem8, s>>>((const uint8_t *)B, brb, 0, nb, n_ht, grid8, mats.A[0], 0, mats);
-    } else if (nb <= 16) {
-        auto kernel = gemv_kq_kernel<TR, 1, BT, NW, 1, true>;
-        kernel<<<grid, NW * 64, smem, s>>>((const uint8_t *)B, brb, 0, nb, n_ht, grid, mats.A[0], 0 /* expert picked on the device: no early issue */, mats);
-    } else {
-        auto kernel = gemv_kq_kernel<TR, 1, BT, NW, 2, true>;
-        if (smem > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess)
-                return e;
-        }
-        kernel<<<grid, NW * 64, smem, s>>>((const uint8_t *)B, brb, 0, nb, n_ht, grid, mats.A[0], 0 /* expert picked on the device: no early issue */, mats);
-    }
-    return hipGetLastError();
+// What a type's unit exports.  QTYPE: the type's pre-quantised activation format.  ROWS32: the unit holds the 32-row-item
+// kernel (the plan asks for it by kq_unit::rows32 in gemv.hip).  IDS: it holds the expert forms (Q4_K, Q5_K, Q6_K).
+template <typename TR, int QTYPE, bool ROWS32, bool IDS>
+static const void *kq_unit_kernel(int variant, int nc, int f32in, int nw, int ch) {
+    if constexpr (IDS)
+        if (nc == 1 && (variant == LFAMD_GEMV_EXPERT || variant == LFAMD_GEMV_EXPERT_PAIR))
+            return f32in ? kq_kernel_ids<TR, LFAMD_TYPE_F32>(variant, nw, ch) : kq_kernel_ids<TR, QTYPE>(variant, nw, ch);
+    return f32in ? kq_kernel<TR, LFAMD_TYPE_F32, ROWS32>(variant, nc, nw, ch) : kq_kernel<TR, QTYPE, ROWS32>(variant, nc, nw, ch);
 }
 
-template <typename TR, int NC, int BT>
-static hipError_t launch_kq_pick(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0,
-                                 hipStream_t s) {
-    const long nb = k / 256;
-    if constexpr (NC == 1) {
-        // a launch of at most one half-tile per CU (attn_output, attn_k/v alone: the whole kernel is one prologue + one
-        // item) runs 8 waves of two super-blocks each: half as many waves contend for a SIMD while the row is quantised
-        // (two blocks per pass cost 140 VALU against 2 x 120) — 4096 x 4096: 4.35 -> 3.88 us, 1024 x 4096: 3.65 -> 3.27,
-        // 4096 x 8192: 6.83 -> 6.49.  With more tiles per work-group the 16-wave form streams better (14336 x 4096:
-        // 8.4 vs 9.1 us), and rows of 56 super-blocks lose too (9.4 vs 10.3).
-        // (the same form for f32 and pre-quantised rows: the two launches stay bit-identical)
-        if (n_ht <= num_cus() && nb <= 32)
-            return launch_kq<TR, NC, BT, 8, 2>(mats, n_ht, k, B, brb, col0, s);
-        // (round 3, 8 waves for launches of MANY items too: 14336 x 4096 8.30 vs 9.10 us, 28672 13.3 vs 14.2, 32000 (Q6_K) 23.5 vs
-        // 24.3, 128256 83.7 vs 84.2 — the 16-wave form keeps them; only at 57344 rows, 14 half-tiles per work-group, does
-        // the 8-wave form win (24.4 -> 23.5), which is the expert launch below)
-        if (nb <= 16)
-            return launch_kq<TR, NC, BT, 16, 1>(mats, n_ht, k, B, brb, col0, s);
-        return launch_kq<TR, NC, BT, 16, 2>(mats, n_ht, k, B, brb, col0, s);
-    } else {
-        // several columns (n = 2..8): 16 waves when a work-group walks several half-tiles (14336 x 4096, n = 4: 24.0 ->
-        // 17.5 us), 8 waves of two blocks for single-tile launches (4096 x 4096: the same either way) and for deep rows
-        // (4096 x 14336, n = 4: 22.6 vs 23.7 us with 16)
-        if (nb <= 16 && n_ht > num_cus())
-            return launch_kq<TR, NC, BT, 16, 1>(mats, n_ht, k, B, brb, col0, s);
-        if (nb <= 16)
-            return launch_kq<TR, NC, BT, 8, 2>(mats, n_ht, k, B, brb, col0, s);
-        return launch_kq<TR, NC, BT, 8, 4>(mats, n_ht, k, B, brb, col0, s);
-    }
+// ... and a two-type unit (16 x 1, 16 x 2; the shared activation image is Q8_K)
+template <typename TRA, typename TRB>
+static const void *kq_dual_unit_kernel(int variant, int nc, int f32in, int nw, int ch) {
+    if (variant != LFAMD_GEMV_TWO_TYPES || nc != 1 || nw != 16 || (ch != 1 && ch != 2))
+        return nullptr;
+    if (f32in)
+        return ch == 1 ? (const void *)gemv_kq_dual_kernel<TRA, TRB, LFAMD_TYPE_F32, 16, 1>
+                       : (const void *)gemv_kq_dual_kernel<TRA, TRB, LFAMD_TYPE_F32, 16, 2>;
+    return ch == 1 ? (const void *)gemv_kq_dual_kernel<TRA, TRB, LFAMD_TYPE_Q8_K, 16, 1>
+                   : (const void *)gemv_kq_dual_kernel<TRA, TRB, LFAMD_TYPE_Q8_K, 16, 2>;
 }
-
-template <int NC, int BT>
-static hipError_t launch_q4k(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<q4k_traits, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q40(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<q40_traits, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q5k(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<q5k_traits, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q6k(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<q6k_traits, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q2k(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<pk_traits<LFAMD_TYPE_Q2_K>, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q3k(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<pk_traits<LFAMD_TYPE_Q3_K>, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q41(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<pcl_traits<LFAMD_TYPE_Q4_1>, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q50(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<pcl_traits<LFAMD_TYPE_Q5_0>, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q51(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<pcl_traits<LFAMD_TYPE_Q5_1>, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_iq4xs(const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s) {
-    return launch_kq_pick<iq4c_traits, NC, BT>(mats, n_ht, k, B, brb, col0, s);
-}
-
-template <int NC, int BT>
-static hipError_t launch_q80(const q80_mats &mats, long n_total, long k, const void *B, size_t brb, long col0, int vregs32,
-                             int precise, hipStream_t s) {
-    int nblocks = (int)(k / 32), nquads = (nblocks + 3) / 4;
-    size_t smem = (size_t)NC * nquads * X80_QUAD;
-    const long rgs = mats.rg_end[GEMV_MAX_MATS - 1];
-    unsigned grid = (unsigned)((rgs + Q80_WAVES - 1) / Q80_WAVES);
-    // n = 1: the whole problem is one column of 2x1 / 1x1 tiles, so the summation mode is uniform
-    const int mode = n_total == 1 ? ((vregs32 || precise) ? 1 : 0) : 2;
-#define Q80_GO(MODE)                                                                                                   \
-    do {                                                                                                               \
-        auto kernel = gemv_q80_kernel<NC, BT, MODE, 16>;                                                               \
-        if (smem > 64 * 1024) {                                                                                        \
-            hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-            if (e != hipSuccess)                                                                                       \
-                return e;                                                                                              \
-        }                                                                                                              \
-        kernel<<<grid, Q80_WAVES * 64, smem, s>>>((const uint8_t *)B, brb, col0, nblocks, nquads, n_total, vregs32, precise, \
-                                                  mats);                                                               \
-    } while (0)
-    if (mode == 0)
-        Q80_GO(0);
-    else if (mode == 1)
-        Q80_GO(1);
-    else
-        Q80_GO(2);
-#undef Q80_GO
-    return hipGetLastError();
-}
-
-
-#define DISPATCH_NC(FN, BT, nc, ...)                                                                                   \
-    switch (nc) {                                                                                                      \
-    case 1:                                                                                                            \
-        e = FN<1, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    case 2:                                                                                                            \
-        e = FN<2, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    case 3:                                                                                                            \
-        e = FN<3, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    case 4:                                                                                                            \
-        e = FN<4, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    case 5:                                                                                                            \
-        e = FN<5, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    case 6:                                                                                                            \
-        e = FN<6, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    case 7:                                                                                                            \
-        e = FN<7, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    default:                                                                                                           \
-        e = FN<8, BT>(__VA_ARGS__);                                                                                    \
-        break;                                                                                                         \
-    }
-
-
-// ---- one translation unit per weight type (gemv_*.hip) instantiates its kernels through these stamps (the 8 column
-// counts x 2 activation types x chunk variants of every type used to compile serially in one 140-second file)
-#define GEMV_GO_ARGS int nc, int f32in, const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb, long col0, hipStream_t s
-#define GEMV_INSTANTIATE(NAME, TRAITS, QTYPE)                                                                          \
-    hipError_t lfamd_gemv_go_##NAME(GEMV_GO_ARGS) {                                                                    \
-        hipError_t e = hipSuccess;                                                                                     \
-        if (f32in) {                                                                                                   \
-            DISPATCH_NC(launch_##NAME, LFAMD_TYPE_F32, nc, mats, n_ht, k, B, brb, col0, s)                             \
-        } else {                                                                                                       \
-            DISPATCH_NC(launch_##NAME, QTYPE, nc, mats, n_ht, k, B, brb, col0, s)                                      \
-        }                                                                                                              \
-        return e;                                                                                                      \
-    }
-#define GEMV_INSTANTIATE_DUAL(NAME, TRA, TRB)                                                                           \
-    hipError_t lfamd_gemv_dual_go_##NAME(int f32in, const gemv_mats &ma, int n_ht_a, const gemv_mats &mb, int n_ht_b, long k, \
-                                         const void *B, size_t brb, hipStream_t s) {                                   \
-        return f32in ? launch_kq_dual<TRA, TRB, LFAMD_TYPE_F32>(ma, n_ht_a, mb, n_ht_b, k, B, brb, s)                  \
-                     : launch_kq_dual<TRA, TRB, LFAMD_TYPE_Q8_K>(ma, n_ht_a, mb, n_ht_b, k, B, brb, s);                \
-    }
-#define GEMV_INSTANTIATE_IDS_PAIR(NAME, TRAITS)                                                                        \
-    hipError_t lfamd_gemv_ids_pair_go_##NAME(int f32in, const gemv_mats &ma, const gemv_mats &mb, int n_ht, long k, const void *Ba, \
-                                             const void *Bb, size_t brb, hipStream_t s) {                                \
-        return f32in ? launch_kq_ids_pair<TRAITS, LFAMD_TYPE_F32>(ma, mb, n_ht, k, Ba, Bb, brb, s)                       \
-                     : launch_kq_ids_pair<TRAITS, LFAMD_TYPE_Q8_K>(ma, mb, n_ht, k, Ba, Bb, brb, s);                     \
-    }
-#define GEMV_INSTANTIATE_IDS(NAME, TRAITS)                                                                             \
-    hipError_t lfamd_gemv_ids_go_##NAME(int f32in, const gemv_mats &mats, int n_ht, long k, const void *B, size_t brb,  \
-                                        hipStream_t s) {                                                               \
-        return f32in ? launch_kq_ids<TRAITS, LFAMD_TYPE_F32>(mats, n_ht, k, B, brb, s)                                 \
-                     : launch_kq_ids<TRAITS, LFAMD_TYPE_Q8_K>(mats, n_ht, k, B, brb, s);                               \
-    }

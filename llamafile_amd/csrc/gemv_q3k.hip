@@ -1,4 +1,6 @@
-// gemv_q3k.hip — Q3_K instantiations of the decode GEMV (gemv_impl.h)
+// gemv_q3k.hip — Q3_K instantiations of the decode GEMV, with 32-row items (kernels: gemv_impl.h; launched from gemv.hip)
 #include "gemv_impl.h"
 
-GEMV_INSTANTIATE(q3k, unused, LFAMD_TYPE_Q8_K)
+const void *lfamd_gemv_kernel_q3k(int variant, int nc, int f32in, int nw, int ch) {
+    return kq_unit_kernel<pk_traits<LFAMD_TYPE_Q3_K>, LFAMD_TYPE_Q8_K, true, false>(variant, nc, f32in, nw, ch);
+}

@@ -1,4 +1,6 @@
-// gemv_q41.hip — Q4_1 instantiations of the decode GEMV (gemv_impl.h)
+// gemv_q41.hip — Q4_1 instantiations of the decode GEMV (kernels: gemv_impl.h; launched from gemv.hip)
 #include "gemv_impl.h"
 
-GEMV_INSTANTIATE(q41, unused, LFAMD_TYPE_Q8_1)
+const void *lfamd_gemv_kernel_q41(int variant, int nc, int f32in, int nw, int ch) {
+    return kq_unit_kernel<pcl_traits<LFAMD_TYPE_Q4_1>, LFAMD_TYPE_Q8_1, false, false>(variant, nc, f32in, nw, ch);
+}

@@ -1,6 +1,6 @@
-// gemv_q4k.hip — Q4_K instantiations of the decode GEMV (gemv_impl.h)
+// gemv_q4k.hip — Q4_K instantiations of the decode GEMV, with the expert forms (kernels: gemv_impl.h; launched from gemv.hip)
 #include "gemv_impl.h"
 
-GEMV_INSTANTIATE(q4k, q4k_traits, LFAMD_TYPE_Q8_K)
-GEMV_INSTANTIATE_IDS(q4k, q4k_traits)
-GEMV_INSTANTIATE_IDS_PAIR(q4k, q4k_traits)
+const void *lfamd_gemv_kernel_q4k(int variant, int nc, int f32in, int nw, int ch) {
+    return kq_unit_kernel<q4k_traits, LFAMD_TYPE_Q8_K, false, true>(variant, nc, f32in, nw, ch);
+}

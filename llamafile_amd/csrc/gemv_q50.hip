@@ -1,4 +1,6 @@
-// gemv_q50.hip — Q5_0 instantiations of the decode GEMV (gemv_impl.h)
+// gemv_q50.hip — Q5_0 instantiations of the decode GEMV (kernels: gemv_impl.h; launched from gemv.hip)
 #include "gemv_impl.h"
 
-GEMV_INSTANTIATE(q50, unused, LFAMD_TYPE_Q8_0)
+const void *lfamd_gemv_kernel_q50(int variant, int nc, int f32in, int nw, int ch) {
+    return kq_unit_kernel<pcl_traits<LFAMD_TYPE_Q5_0>, LFAMD_TYPE_Q8_0, false, false>(variant, nc, f32in, nw, ch);
+}

@@ -6,6 +6,24 @@
 #include <stddef.h>
 #include <stdint.h>
 
+// A planned decode GEMV launch.  kind = the entry point that asks, variant = the kernel form it gets.
+enum { LFAMD_GEMV_MULTI, LFAMD_GEMV_IDS, LFAMD_GEMV_IDS_PAIR, LFAMD_GEMV_DUAL };
+enum {
+    LFAMD_GEMV_PLAIN,       // gemv_kq_kernel
+    LFAMD_GEMV_EARLY,       // ... one matrix, one column: first weight loads from the preloaded arguments
+    LFAMD_GEMV_ROWS32,      // ... items of a whole 32-row tile (long walks of the types with a long dot)
+    LFAMD_GEMV_EXPERT,      // ... expert picked on the device (MUL_MAT_ID)
+    LFAMD_GEMV_EXPERT_PAIR, // gemv_kq_ids_pair_kernel: two experts, two activation rows, two sub-grids
+    LFAMD_GEMV_TWO_TYPES,   // gemv_kq_dual_kernel: {Q4_K | Q5_K} and Q6_K matrices, two sub-grids
+    LFAMD_GEMV_Q80          // gemv_q80_kernel
+};
+struct lfamd_gemv_plan {
+    int variant, nc, nw, ch; // columns, waves per work-group, super-blocks per chunk (Q8_0: ch = 0)
+    int grid, grid_b;        // work-groups; grid_b: the second sub-grid of the two split launches, else 0
+    int rows;                // result rows per item (16, ROWS32: 32; Q8_0: 8 per wave)
+    int lds;                 // dynamic LDS bytes
+};
+
 extern "C" {
 void lfamd_set_error(const char *); // (api.hip: sets lfamd_last_error)
 size_t lfamd_mul_mat_workspace_upto(int, long, long, long);
@@ -49,6 +67,13 @@ hipError_t lfamd_launch_gemv_ids(int, int, const void *const *, long, int, const
                                  float *const *, hipStream_t);
 hipError_t lfamd_launch_gemv_ids_pair(int, const void *, long, int, const int32_t *, int, int, long, long, int, const void *, const void *, size_t,
                                       float *, float *, hipStream_t);
+// the decode GEMVs' launch plan (gemv.hip): pure host arithmetic, the CU count is an argument
+int lfamd_num_cus(void); // of the current device, read once per process; 256 when no device answers
+int lfamd_gemv_depth_ok(long);                    // one row's K-quant LDS image (k / 256 blocks of 384 bytes) fits in 150 KiB
+int lfamd_gemv_cols_per_launch(int, long);        // (Atype, k): activation columns one launch takes, 0 = the row is too deep
+size_t lfamd_gemv_lds_bytes(int, int, long, int, int); // (Atype, nc, k, nw, rows per item): the LDS layout's total
+int lfamd_gemv_plan_of(int, int, int, long, long, long, int, int, struct lfamd_gemv_plan *);
+int lfamd_gemv_has_kernel(int, int, const struct lfamd_gemv_plan *); // (Atype, f32in, plan): the type's unit instantiates it
 int lfamd_gemv_float_ok(int, long, long);
 hipError_t lfamd_launch_gemv_float(int, const void *, long, long, int, const void *, size_t, long, float *, long, hipStream_t);
 // batch bodies (gemm_*.hip, generic.hip)

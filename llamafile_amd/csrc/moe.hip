@@ -149,7 +149,7 @@ extern "C" size_t lfamd_moe_workspace(int type, long rows, long cols, int expert
 extern "C" bool lfamd_moe_decode_multi_ok(int type, long cols, int Btype, int tasks, long tokens, unsigned flags) {
     return tokens <= 4 && tasks == 1 && (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K) &&
            !(flags & LFAMD_FLAG_FORCE_GENERIC) && (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && cols % 256 == 0 &&
-           (size_t)(cols / 256) * 384 <= 150 * 1024;
+           lfamd_gemv_depth_ok(cols);
 }
 extern "C" hipError_t lfamd_launch_moe_decode_multi(int type, int count, const void *const *W, long rows, long cols, int experts,
                                                     size_t expert_bytes, int Btype, const void *thought, size_t b_row_bytes, long tokens,
@@ -186,7 +186,7 @@ extern "C" hipError_t lfamd_launch_moe(int type, const void *W, long rows, long 
     // reference's host round trip (ggml-cuda.cu.patch:18528-18531).
     if (tokens <= 4 && (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K) &&
         !(flags & LFAMD_FLAG_FORCE_GENERIC) &&
-        (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && (size_t)(cols / 256) * 384 <= 150 * 1024) {
+        (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && lfamd_gemv_depth_ok(cols)) {
         for (long t = 0; t < tokens; t++) {
             int th = 0;
             while (th < thinkers) {

@@ -1,6 +1,6 @@
 // oneshot_impl.h — the one-shot peer exchange protocol (comm.hip), as device code that other kernels can end with:
-// the decode GEMV of attn_output / ffn_down runs it in its LAST work-group to finish (gemv_impl.h: gemv_kq_fx_kernel),
-// so that product and all-reduce are one launch.
+// comm.hip's all-reduce kernel is its one user today.  (A decode GEMV of attn_output / ffn_down that ran it in its LAST work-group to
+// finish, product and all-reduce in one launch, was measured in round 3 — DESIGN.md section 10.8 — and is no longer in the tree.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

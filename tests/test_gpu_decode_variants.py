@@ -106,7 +106,7 @@ def test_small_batch_respects_the_result_stride(gpu, oracle):
 def test_32_row_items_give_the_same_bits(gpu, tmp_path):
     """gemv_kq_body1<..., PAIR>: long walks take both half-tiles of a 32-row tile as one item (one barrier per tile).  The
     launch rule needs >= 16 half-tiles per work-group (output.weight) and a type with a long dot (Q6_K, Q2_K, Q3_K, IQ4_XS:
-    gemv_impl.h kq_pair_items); LFAMD_GEMV_PAIR_MIN=1 forces the form on every 16-wave / one-super-block launch of those types,
+    gemv.hip kq_unit::rows32); LFAMD_GEMV_PAIR_MIN=1 forces the form on every 16-wave / one-super-block launch of those types,
     here 8192 x 4096 and 8200 x 2048 (ragged last tile) and a two-matrix launch: every result must be the bytes the 16-row
     items give (Q4_K rides along unchanged; the env is read once per process: two child processes)."""
     import subprocess
