@@ -13,6 +13,7 @@
  *   Q2_K..Q6_K  llama.cpp.patches/patches/ggml-cuda.cu.patch:3217-3471,
  *               llamafile/iqk_mul_mat.inc:417-599
  *   IQ4_XS llamafile/iqk_mul_mat.inc:432-470
+ *   IQ4_NL llama.cpp.patches/patches/ggml-cuda.cu.patch:3662-3677 (Q4_0's block shape, the IQ4_XS codebook)
  *   Q8_K  llama.cpp.patches/patches/ggml-common.h.patch:25-35
  *         (llamafile order: d, bsums[16], qs[256] — NOT upstream's d, qs, bsums)
  *
@@ -45,6 +46,7 @@ enum lfamd_ggml_type {
     LFAMD_TYPE_Q5_K = 13,
     LFAMD_TYPE_Q6_K = 14,
     LFAMD_TYPE_Q8_K = 15,
+    LFAMD_TYPE_IQ4_NL = 20,
     LFAMD_TYPE_IQ4_XS = 23,
     LFAMD_TYPE_I32 = 26,
     LFAMD_TYPE_BF16 = 30,
@@ -136,6 +138,11 @@ typedef struct {
     uint8_t qs[128];
 } lfamd_block_iq4_xs; /* 136 B */
 
+typedef struct {
+    lfamd_half d;
+    uint8_t qs[16]; /* codebook indices: low nibbles = weights 0..15, high nibbles = 16..31 */
+} lfamd_block_iq4_nl; /* 18 B / 32 w */
+
 /* llamafile's re-ordered Q8_K (ggml-common.h.patch:25-35) */
 typedef struct {
     float d;
@@ -159,6 +166,7 @@ static inline int lfamd_blck_size(int type) {
     case LFAMD_TYPE_Q5_1:
     case LFAMD_TYPE_Q8_0:
     case LFAMD_TYPE_Q8_1:
+    case LFAMD_TYPE_IQ4_NL:
         return 32;
     case LFAMD_TYPE_Q2_K:
     case LFAMD_TYPE_Q3_K:
@@ -207,6 +215,8 @@ static inline size_t lfamd_type_size(int type) {
         return sizeof(lfamd_block_q8_K);
     case LFAMD_TYPE_IQ4_XS:
         return sizeof(lfamd_block_iq4_xs);
+    case LFAMD_TYPE_IQ4_NL:
+        return sizeof(lfamd_block_iq4_nl);
     default:
         return 0;
     }
@@ -225,6 +235,7 @@ static inline int lfamd_vec_dot_type(int type) {
     case LFAMD_TYPE_Q4_0:
     case LFAMD_TYPE_Q5_0:
     case LFAMD_TYPE_Q8_0:
+    case LFAMD_TYPE_IQ4_NL:
         return LFAMD_TYPE_Q8_0;
     case LFAMD_TYPE_Q4_1:
     case LFAMD_TYPE_Q5_1:

@@ -81,8 +81,9 @@ int lfamd_stream_sync(void *stream);
  * them with coalesced 16-byte-per-lane loads (DESIGN.md "Data layout in HBM").  `raw` is the
  * tensor exactly as GGUF/ggml stores it: `rows` rows, `raw_row_bytes` apart, each a sequence of
  * blocks (include/lfamd_blocks.h).  Packing is a device kernel: raw and packed are device
- * pointers.  lfamd_packed_size is the ONLY source of the packed byte count: Q4_K / Q5_K / Q6_K / Q4_0 images are
- * the GGUF size (+ tile round-up); Q2_K / Q3_K / IQ4_XS are compact images of 84 / 116 / 144 bytes per 256 weights (1.00x /
+ * pointers.  lfamd_packed_size is the ONLY source of the packed byte count: Q4_K / Q5_K / Q6_K / Q4_0 / IQ4_NL images are
+ * the GGUF size (+ tile round-up; IQ4_NL is Q4_0's block shape and takes Q4_0's image byte for byte, its nibbles being codebook
+ * indices); Q2_K / Q3_K / IQ4_XS are compact images of 84 / 116 / 144 bytes per 256 weights (1.00x /
  * 1.055x / 1.06x the file: DESIGN.md section 10.10; batches expand them per call into the canonical image in the workspace); Q8_0 is
  * ONE image of the file's size (1.0625 bytes per weight) that the bit-exact vecdot, the exact batch kernel and the f16 MFMA batch
  * body all read — only a process that opted into the vendor GEMM (LFAMD_USE_BLASLT=1) keeps f16(d * q) rows behind it (3.1 bytes
@@ -107,7 +108,8 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
  * GGML_OP_GET_ROWS (k_get_rows / ggml_cuda_op_get_rows, ggml-cuda.cu.patch:10687-10860) and for the to_fp16 / to_fp32 converters
  * (ggml_get_to_fp16_cuda / ggml_get_to_fp32_cuda, :3929-4040), for every type and shape lfamd_packed_size answers non-zero for.
  *   EXACT: every value is the f32 ((d * sc) * q) - (dmin * mn) (K-quants, IQ4_XS) or (d * q) + m (32-blocks) of the block's own
- *   fields, in that order, uncontracted — the same bits as dequantising the GGUF row on the CPU (oracle.c: ora_dequantize_row),
+ *   fields (IQ4_NL: q = the codebook value of the index, m = +0), in that order, uncontracted — the same bits as dequantising the
+ *   GGUF row on the CPU (oracle.c: ora_dequantize_row),
  *   the sign of zero included; F16 output is that value rounded to nearest-even (subnormals kept, overflow to inf); F32 / F16 /
  *   BF16 tensors convert exactly.
  *   An index outside [0, rows) leaves its output row untouched (the rule lfamd_mul_mat_id has for expert ids); bytes of an output
@@ -156,8 +158,8 @@ static inline unsigned lfamd_exact_flag(int type) {
  *     reference's vec_dot_type conversion does, and the products of two 16-bit values are exact in f32;
  *   Q8_0 batches: 0 on the f16 MFMA body (rows of whole 128-weight quads, or the vendor GEMM), 1 on the bit-exact kernel
  *     (LFAMD_FLAG_Q80_EXACT / LFAMD_FLAG_PRECISE, other row lengths);
- *   IQ4_XS batches: 0 (the canonical image rounds |sc * kvalue| above 2048 to f16); Q2_K / Q3_K (|sc * q| <= 128) and the
- *     legacy 32-block bodies: 1;
+ *   IQ4_XS batches: 0 (the canonical image rounds |sc * kvalue| above 2048 to f16); Q2_K / Q3_K (|sc * q| <= 128), the
+ *     legacy 32-block bodies and IQ4_NL (codebook values |v| <= 127 are exact in f16, d is applied in f32 per block): 1;
  *   Q4_K / Q5_K / Q6_K batches of 9 .. 32 columns that run the small-batch kernel (gemm_sb.hip; where lfamd_mul_mat picks it:
  *     at most a few row tiles per CU, or deep rows): 1; other Q6_K batches: 0 (both batch bodies round sc * (q - 32) above
  *     2048); LFAMD_FLAG_PRECISE / _GEMM_NARROW / _GEMM_PLAIN: 1; the Q4_K batches on the int8 matrix cores (gemm_i8.hip: grids

@@ -126,6 +126,7 @@ static bool type_known(int t) {
     case LFAMD_TYPE_Q5_K:
     case LFAMD_TYPE_Q6_K:
     case LFAMD_TYPE_IQ4_XS:
+    case LFAMD_TYPE_IQ4_NL:
         return true;
     default:
         return false;
@@ -144,6 +145,7 @@ size_t lfamd_packed_size(int type, long rows, long cols) {
     case LFAMD_TYPE_Q4_K:
         return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P4K_TILE;
     case LFAMD_TYPE_Q4_0:
+    case LFAMD_TYPE_IQ4_NL: // (Q4_0's block shape: the same image, the nibbles are codebook indices)
         if (cols % 256 == 0) // P40; other row lengths stay RAW (generic kernels)
             return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P4K_TILE;
         return (size_t)rows * lfamd_row_size(type, cols);
@@ -189,6 +191,7 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
         HIPCHK(lfamd_launch_pack_q4k(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q4k");
         break;
     case LFAMD_TYPE_Q4_0:
+    case LFAMD_TYPE_IQ4_NL:
         if (cols % 256 == 0) {
             HIPCHK(lfamd_launch_pack_q40(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q40");
         } else {
@@ -311,9 +314,9 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
 // _takes_staged, _takes_staged_scaled and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
 // HIP call (lfamd_blaslt_ok() touches the device only when a host opted into the vendor library, LFAMD_USE_BLASLT=1).
 
-// Q4_0 rows that are whole 256-weight groups are kept in the P40 layout and served by the tuned kernels
+// Q4_0 / IQ4_NL rows that are whole 256-weight groups are kept in the P40 layout and served by the tuned kernels
 static bool packed40(int Atype, long k) {
-    return Atype == LFAMD_TYPE_Q4_0 && k % 256 == 0;
+    return (Atype == LFAMD_TYPE_Q4_0 || Atype == LFAMD_TYPE_IQ4_NL) && k % 256 == 0;
 }
 // legacy 32-block types whose rows are whole 256-weight groups (Q4_1, Q5_0, Q5_1): resident PCL image
 static bool packed_pcl(int Atype, long k) {
@@ -381,7 +384,7 @@ enum class mm_body {
     kq_narrow,  // K-quant batches, the 128 x 64 split-K body on integer codes (gemm_mfma.hip); exact, Q6_K f16-rounded
     wide,       // K-quant batches, the 128 x 128 family (gemm_wide.hip).  scaled: f16-rounded, reads LFAMD_TYPE_STAGED_SCALED;
                 // else integer codes: exact, Q6_K f16-rounded
-    q40_wide,   // P40 Q4_0 batches on Q8_0-quantised activations, the 128 x 128 body; exact
+    q40_wide,   // P40 Q4_0 / IQ4_NL batches on Q8_0-quantised activations, the 128 x 128 body; exact
     canon,      // Q2_K / Q3_K / IQ4_XS batches: canonical image expanded per call, the 128 x 128 body; exact, IQ4_XS f16-rounded
     canon32,    // PCL Q4_1 / Q5_0 / Q5_1 batches, the 128 x 128 body; exact
     float_lt,   // F16 / BF16 batches on the vendor GEMM (LFAMD_USE_BLASLT=1); exact.  Declined or unaligned: float_lf / float_wide
@@ -411,7 +414,7 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
     else if (n > 8 && (kquant(Atype) || packed40(Atype, k))) {
         if (i8_takes(Atype, k, n, flags, (m + 127) / 128))
             p.body = mm_body::i8;
-        else if (Atype == LFAMD_TYPE_Q4_0)
+        else if (Atype == LFAMD_TYPE_Q4_0 || Atype == LFAMD_TYPE_IQ4_NL)
             p.body = mm_body::q40_wide;
         else {
             // Two families: 128 x 128 / 256 x 128 tiles with K streamed once (gemm_wide.hip and its loader-wave / K-split-wave /

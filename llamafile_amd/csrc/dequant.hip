@@ -4,7 +4,7 @@
 //
 // ARITHMETIC.  Exactly oracle/oracle.c: ora_dequantize_row, in f32, in this order and with no contraction:
 //   K-quants, IQ4_XS   ((d * (float)sc) * (float)q) - (dmin * (float)mn)        (dmin = +0, mn = 0 where the type has no mins)
-//   32-blocks          (d * (float)q) + m                                        (m = +0 where the type has none)
+//   32-blocks          (d * (float)q) + m                                        (m = +0 where the type has none; IQ4_NL: q = kvalue[index])
 // The "+ m" with m = +0 is NOT dropped: it turns a -0 product (q = 0 under a negative d) into the +0 the reference gives.  A fused
 // multiply-add would skip the rounding of the product, so this file must be built with -ffp-contract=off (the Makefile's HIPFLAGS);
 // the pragma below states it here too, so that the file does not depend on the flag silently.
@@ -28,8 +28,8 @@
 
 enum dq_layout {
     LY_P4K, LY_P5K, LY_P6K, LY_P40, LY_PK2, LY_PK3, LY_PX4, // PX4: the compact IQ4_XS image
-    LY_PCL41, LY_PCL50, LY_PCL51, LY_P80,
-    LY_RAW40, LY_RAW41, LY_RAW50, LY_RAW51, LY_F32, LY_F16, LY_BF16, // GGUF rows
+    LY_PCL41, LY_PCL50, LY_PCL51, LY_P80, LY_P4N, // P4N: the P40 image of IQ4_NL (nibbles = codebook indices)
+    LY_RAW40, LY_RAW41, LY_RAW50, LY_RAW51, LY_RAW4N, LY_F32, LY_F16, LY_BF16, // GGUF rows
     LY_NONE
 };
 
@@ -38,7 +38,7 @@ enum dq_layout {
 // themselves are arrays, and an array indexed by a lane-dependent j would go through scratch memory.
 
 __host__ __device__ static constexpr int ly_tile(int ly) {
-    return ly == LY_P4K || ly == LY_P40 || ly == LY_PX4 ? P4K_TILE
+    return ly == LY_P4K || ly == LY_P40 || ly == LY_PX4 || ly == LY_P4N ? P4K_TILE
            : ly == LY_P5K                                ? P5K_TILE
            : ly == LY_P6K                                ? P6K_TILE
            : ly == LY_PK2                                ? PK2_TILE
@@ -48,7 +48,7 @@ __host__ __device__ static constexpr int ly_tile(int ly) {
                                                          : 0;
 }
 __host__ __device__ static constexpr int ly_raw_block(int ly) { // bytes of one 32-block of the RAW legacy layouts
-    return ly == LY_RAW40 ? 18 : ly == LY_RAW41 ? 20 : ly == LY_RAW50 ? 22 : ly == LY_RAW51 ? 24 : 0;
+    return ly == LY_RAW40 || ly == LY_RAW4N ? 18 : ly == LY_RAW41 ? 20 : ly == LY_RAW50 ? 22 : ly == LY_RAW51 ? 24 : 0;
 }
 
 __device__ static inline int nibpos(int j) {
@@ -188,7 +188,7 @@ __device__ static inline void decode4(const uint8_t *__restrict__ img, long row,
 #pragma unroll
         for (int e = 0; e < 4; e++)
             v[e] = kq_value(d, sc, (int)kvalues_iq4nl_dq[(x >> (4 * nibpos(j0 + e))) & 15], 0.0f, 0);
-    } else if constexpr (LY == LY_P40 || LY == LY_PCL41 || LY == LY_PCL50 || LY == LY_PCL51) {
+    } else if constexpr (LY == LY_P40 || LY == LY_P4N || LY == LY_PCL41 || LY == LY_PCL50 || LY == LY_PCL51) {
         const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * ly_tile(LY);
         const uint32_t x = lat_dword(tile, i, t, h);
         const int bl = L >> 3; // 32-block of the 256-weight group
@@ -206,6 +206,8 @@ __device__ static inline void decode4(const uint8_t *__restrict__ img, long row,
                 q |= (int)((f >> (4 * q5pos(j0 + e))) & 1) << 4;
             if constexpr (LY == LY_P40)
                 q -= 8;
+            if constexpr (LY == LY_P4N)
+                q = (int)kvalues_iq4nl_dq[q];
             if constexpr (LY == LY_PCL50)
                 q -= 16;
             v[e] = lq_value(d, q, m);
@@ -218,7 +220,7 @@ __device__ static inline void decode4(const uint8_t *__restrict__ img, long row,
 #pragma unroll
         for (int e = 0; e < 4; e++)
             v[e] = lq_value(d, (int)(int8_t)(x >> (8 * e)), 0.0f);
-    } else if constexpr (LY == LY_RAW40 || LY == LY_RAW41 || LY == LY_RAW50 || LY == LY_RAW51) {
+    } else if constexpr (LY == LY_RAW40 || LY == LY_RAW41 || LY == LY_RAW50 || LY == LY_RAW51 || LY == LY_RAW4N) {
         constexpr int BS = ly_raw_block(LY);
         constexpr bool HAS_M = LY == LY_RAW41 || LY == LY_RAW51, HAS_H = LY == LY_RAW50 || LY == LY_RAW51;
         constexpr int QH_OFF = HAS_M ? 4 : 2, QS_OFF = QH_OFF + (HAS_H ? 4 : 0);
@@ -239,6 +241,8 @@ __device__ static inline void decode4(const uint8_t *__restrict__ img, long row,
                 q |= (int)((f >> e) & 1) << 4;
             if constexpr (LY == LY_RAW40)
                 q -= 8;
+            if constexpr (LY == LY_RAW4N)
+                q = (int)kvalues_iq4nl_dq[q];
             if constexpr (LY == LY_RAW50)
                 q -= 16;
             v[e] = lq_value(d, q, m);
@@ -488,6 +492,8 @@ static int layout_of(int type, long cols) {
         return LY_P80;
     case LFAMD_TYPE_Q4_0:
         return g256 ? LY_P40 : LY_RAW40;
+    case LFAMD_TYPE_IQ4_NL:
+        return g256 ? LY_P4N : LY_RAW4N;
     case LFAMD_TYPE_Q4_1:
         return g256 ? LY_PCL41 : LY_RAW41;
     case LFAMD_TYPE_Q5_0:
@@ -545,10 +551,12 @@ extern "C" hipError_t lfamd_launch_get_rows(int type, const void *img, long rows
         GR(LY_PCL50)
         GR(LY_PCL51)
         GR(LY_P80)
+        GR(LY_P4N)
         GR(LY_RAW40)
         GR(LY_RAW41)
         GR(LY_RAW50)
         GR(LY_RAW51)
+        GR(LY_RAW4N)
         GR(LY_F32)
         GR(LY_F16)
         GR(LY_BF16)
@@ -584,6 +592,7 @@ extern "C" hipError_t lfamd_launch_unpack(int type, const void *img, long rows, 
             UP(LFAMD_TYPE_Q2_K)
             UP(LFAMD_TYPE_Q3_K)
             UP(LFAMD_TYPE_IQ4_XS)
+        case LFAMD_TYPE_IQ4_NL: // the P40 image: Q4_0's gather
             UP(LFAMD_TYPE_Q4_0)
             UP(LFAMD_TYPE_Q4_1)
             UP(LFAMD_TYPE_Q5_0)

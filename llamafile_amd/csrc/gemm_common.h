@@ -80,6 +80,27 @@ __device__ static inline half8_t dequant_q40(uint32_t x, uint32_t magic) {
     return f.v;
 }
 
+// IQ4_NL: the dword's eight nibbles are indices into the 16-entry codebook (kvalues_iq4nl, |value| <= 127: exact in f16).  The
+// look-up is three v_perm per four indices on a table of value + 128 (lower / upper eight entries by the index's low three bits,
+// then byte i of one or the other by its bit 3); v_perm then builds the f16 pairs 1024 + u (bytes [u, 0x64, u', 0x64]) and one
+// packed add removes the 1152, as dequant_bytes does.  Element order: dequant_q40's (nibbles 0, 4, 1, 5, 2, 6, 3, 7).
+__device__ static inline half8_t dequant_iq4nl(uint32_t x) {
+    constexpr uint32_t T0 = 0x3F2D1801u, T1 = 0x766A5D4Fu, T2 = 0xA6998D81u, T3 = 0xF1D9C5B5u; // kvalues_iq4nl + 128, 4 entries each
+    const half2_t m1152 = {(_Float16)-1152.0f, (_Float16)-1152.0f};
+    const uint32_t n0 = x & 0x0F0F0F0Fu, n1 = (x >> 4) & 0x0F0F0F0Fu; // nibbles 0, 2, 4, 6 / 1, 3, 5, 7, one per byte
+    const uint32_t s0 = n0 & 0x07070707u, s1 = n1 & 0x07070707u;
+    const uint32_t u0 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(T3, T2, s0), __builtin_amdgcn_perm(T1, T0, s0),
+                                              ((n0 >> 1) & 0x04040404u) | 0x03020100u);
+    const uint32_t u1 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(T3, T2, s1), __builtin_amdgcn_perm(T1, T0, s1),
+                                              ((n1 >> 1) & 0x04040404u) | 0x03020100u);
+    frag_u f;
+    f.p[0] = as_half2(__builtin_amdgcn_perm(0x64646464u, u0, 0x04020400u)) + m1152; // nibbles 0, 4
+    f.p[1] = as_half2(__builtin_amdgcn_perm(0x64646464u, u1, 0x04020400u)) + m1152; // 1, 5
+    f.p[2] = as_half2(__builtin_amdgcn_perm(0x64646464u, u0, 0x04030401u)) + m1152; // 2, 6
+    f.p[3] = as_half2(__builtin_amdgcn_perm(0x64646464u, u1, 0x04030401u)) + m1152; // 3, 7
+    return f.v;
+}
+
 // legacy 32-block types on a per-call image: code (4 or 5 bits, fifth bits Hd on the P5K lattice) minus `off`, no scale
 template <bool H5>
 __device__ static inline half8_t dequant_legacy(uint32_t x, uint32_t Hd, float off, uint32_t magic) {

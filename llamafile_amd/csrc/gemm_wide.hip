@@ -12,6 +12,7 @@ hipError_t lfamd_wide_go_q51(WIDE_ARGS);
 hipError_t lfamd_wide_go_q2k(WIDE_ARGS);
 hipError_t lfamd_wide_go_q3k(WIDE_ARGS);
 hipError_t lfamd_wide_go_iq4xs(WIDE_ARGS);
+hipError_t lfamd_wide_go_iq4nl(WIDE_ARGS);
 hipError_t lfamd_wide_go_f16(WIDE_ARGS);
 hipError_t lfamd_wide_go_bf16(WIDE_ARGS);
 
@@ -152,6 +153,8 @@ static hipError_t wide_go(int Atype, int mode, float *P, size_t P_bytes, WIDE_AR
         return lfamd_wide_go_q3k(mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, ks, nbs, n_wg, moe, s);
     case LFAMD_TYPE_IQ4_XS:
         return lfamd_wide_go_iq4xs(mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, ks, nbs, n_wg, moe, s);
+    case LFAMD_TYPE_IQ4_NL:
+        return lfamd_wide_go_iq4nl(mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, ks, nbs, n_wg, moe, s);
     case LFAMD_TYPE_F16:
         return lfamd_wide_go_f16(mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, ks, nbs, n_wg, moe, s);
     case LFAMD_TYPE_BF16:

@@ -136,9 +136,11 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
                                                         const float *__restrict__ d8T, const _Float16 *__restrict__ Xm, long n,
                                                         long n_pad, int n_rb, int n_ct, int ks_n, int nbs) {
     __shared__ __attribute__((aligned(16))) uint8_t xs[2][WD_XSTAGE];     // activation codes, XOR-swizzled rows
-    // 32-blocks: f16 scale per block, Q8_0 / Q8_1 activations (8 d8 per 256).  Q4_0 is resident in P40; Q4_1 / Q5_0 / Q5_1
-    // come as a per-call PCL image (generic.hip, wprep32): L5 = fifth bits, L1 = w = d*q + m with the s = d8*sum(q8) term
-    constexpr bool LEGACY = TYPE == LFAMD_TYPE_Q4_0 || TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
+    // 32-blocks: f16 scale per block, Q8_0 / Q8_1 activations (8 d8 per 256).  Q4_0 and IQ4_NL (nibbles = codebook indices) are
+    // resident in P40; Q4_1 / Q5_0 / Q5_1 come as a per-call PCL image (generic.hip, wprep32): L5 = fifth bits, L1 = w = d*q + m
+    // with the s = d8*sum(q8) term
+    constexpr bool P40 = TYPE == LFAMD_TYPE_Q4_0 || TYPE == LFAMD_TYPE_IQ4_NL;
+    constexpr bool LEGACY = P40 || TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr bool L5 = TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr bool L1 = TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr float LOFF = TYPE == LFAMD_TYPE_Q4_0 ? 8.0f : TYPE == LFAMD_TYPE_Q5_0 ? 16.0f : 0.0f;
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
     constexpr bool FLT = TYPE == LFAMD_TYPE_F16 || TYPE == LFAMD_TYPE_BF16;
     __shared__ __attribute__((aligned(16))) float d8s[2][(BLK8 ? 8 : 1) * WD_COLS]; // d8 of the 128 tokens
     __shared__ __attribute__((aligned(16))) uint8_t xms[2][WD_COLS * 32]; // Q4_K mins operand rows; L1: the 8 x 128 f32 s values
-    constexpr int TILE = (TYPE == LFAMD_TYPE_Q4_K || TYPE == LFAMD_TYPE_Q4_0) ? P4K_TILE : LEGACY ? PCL_TILE : TYPE == LFAMD_TYPE_Q5_K ? P5K_TILE : CANON16 ? PCK_TILE : BYTES8 ? PC8_TILE : P6K_TILE;
+    constexpr int TILE = (TYPE == LFAMD_TYPE_Q4_K || P40) ? P4K_TILE : LEGACY ? PCL_TILE : TYPE == LFAMD_TYPE_Q5_K ? P5K_TILE : CANON16 ? PCK_TILE : BYTES8 ? PC8_TILE : P6K_TILE;
     constexpr bool MINS = TYPE == LFAMD_TYPE_Q4_K || TYPE == LFAMD_TYPE_Q5_K; // Q4_K family: {d, dmin, 6-bit scales/mins}
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, h = lane >> 5;
@@ -639,6 +641,8 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
                     half8_t wf;
                     if constexpr (TYPE == LFAMD_TYPE_Q4_0)
                         wf = dequant_q40(qw[t], magic);
+                    else if constexpr (TYPE == LFAMD_TYPE_IQ4_NL)
+                        wf = dequant_iq4nl(qw[t]);
                     else
                         wf = dequant_legacy<L5>(qw[t], L5 ? (hq5[t >> 2] >> (t & 3)) : 0u, LOFF, magic);
                     if (t + 1 < 16) {
@@ -652,8 +656,8 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
                         tmp[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F[t & 1][nt], wf, e == 0 ? zero16 : tmp[nt], 0, 0, 0);
                     prefetch_step(t, bn, st ^ 1, wn);
                 }
-                // per 32-block: acc += (<q - 8, q8> * d8[token]) * d[row].  The d8 reads are asm: hipcc hoists plain LDS
-                // reads of all eight blocks above the MFMAs and then spills ~500 registers — among them asm-loaded
+                // per 32-block: acc += (<q - 8, q8> * d8[token]) * d[row] (IQ4_NL: <kvalue[q], q8>).  The d8 reads are asm: hipcc
+                // hoists plain LDS reads of all eight blocks above the MFMAs and then spills ~500 registers — among them asm-loaded
                 // weight registers whose data has not landed yet (garbage).
                 const float dbl = h2f((uint16_t)((bl & 1) ? (hdw[bl >> 1] >> 16) : (hdw[bl >> 1] & 0xffff)));
 #pragma unroll

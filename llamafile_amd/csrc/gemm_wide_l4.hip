@@ -3,3 +3,4 @@
 
 WIDE_INSTANTIATE(q40, LFAMD_TYPE_Q4_0)
 WIDE_INSTANTIATE(q41, LFAMD_TYPE_Q4_1)
+WIDE_INSTANTIATE(iq4nl, LFAMD_TYPE_IQ4_NL)

@@ -1,6 +1,6 @@
 // gemv.hip — the decode GEMVs' host side: the launch plan (which kernel form, how many waves, which grid, how much LDS), the
 // matrix tables and the launches.  No kernel is compiled here: the units gemv_q4k / q5k / q6k / q40 / q41 / q50 / q51 / q2k /
-// q3k / iq4xs / dual / q80 / q80b.hip instantiate them (gemv_impl.h, gemv_q80_impl.h) and hand out their addresses.
+// q3k / iq4xs / iq4nl / dual / q80 / q80b.hip instantiate them (gemv_impl.h, gemv_q80_impl.h) and hand out their addresses.
 #include "gemv_launch.h"
 #include <stdlib.h>
 
@@ -24,7 +24,9 @@ struct kq_unit {
     // which types take 32-row items on long walks (LFAMD_GEMV_ROWS32): the ones whose dot is long enough for a second,
     // independent one to fill its gaps.  128256 x 4096, 16-row -> 32-row items: Q6_K 82.0 -> 73.7 us, Q2_K 44.6 -> 40.8, Q3_K
     // 50.3 -> 44.9, IQ4_XS 58.1 -> 55.4; the light dots lose a little: Q4_K 47.4 -> 47.7, Q5_K 58.1 -> 58.5, Q4_0 46.0 -> 47.6
-    // (65536 rows: 27.0 -> 28.2)
+    // (65536 rows: 27.0 -> 28.2).  IQ4_NL carries IQ4_XS's look-up on Q4_0's image (816 VALU per kernel against Q4_0's 564) and
+    // sides with IQ4_XS: 128256 x 4096 66.1 / 66.8 -> 63.5 / 62.8 us (two processes each, alternated), 65536 rows 29.1 / 30.7 ->
+    // 30.1 / 29.4 (a tie); 14336 x 4096 walks 4 half-tiles per work-group and never takes the form (9.4 us either way)
     bool rows32;
     gemv_kernel_fn *with_q6k; // the two-type unit that pairs this type with Q6_K
 };
@@ -39,6 +41,7 @@ static const kq_unit kq_units[] = {
     {LFAMD_TYPE_Q2_K, lfamd_gemv_kernel_q2k, true, nullptr},
     {LFAMD_TYPE_Q3_K, lfamd_gemv_kernel_q3k, true, nullptr},
     {LFAMD_TYPE_IQ4_XS, lfamd_gemv_kernel_iq4xs, true, nullptr},
+    {LFAMD_TYPE_IQ4_NL, lfamd_gemv_kernel_iq4nl, true, nullptr},
 };
 static const kq_unit *kq_unit_of(int Atype) {
     for (const kq_unit &u : kq_units)

@@ -340,6 +340,54 @@ struct q40_traits {
     }
 };
 
+// The 16-entry int8 codebook of IQ4_NL / IQ4_XS (kvalues_iq4nl), four indices (one per byte) -> four values: four constant
+// registers and three v_perm per four codes: the lower and the upper eight entries by the index's low three bits, then byte i of
+// one or the other by its bit 3.
+__device__ static inline uint32_t kvalues_lut4(uint32_t n) {
+    constexpr uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u; // kvalues_iq4nl, 4 entries each
+    const uint32_t sel = n & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(T1, T0, sel), hi = __builtin_amdgcn_perm(T3, T2, sel);
+    return __builtin_amdgcn_perm(hi, lo, ((n >> 1) & 0x04040404u) | 0x03020100u);
+}
+
+// IQ4_NL (32-blocks {f16 d, 16 index bytes}, activations Q8_0): Q4_0's resident image byte for byte (P40), the nibbles being
+// codebook indices.  Per 32-block: (d * d8) * <kvalue[q], q8>; no offset, so the staged pair sums are not read.
+struct iq4nl_traits {
+    static constexpr int ACT = LFAMD_TYPE_Q8_0;
+    static constexpr int TILE = P4K_TILE;
+    using chunk = q40_traits::chunk;
+    __device__ static inline void load(chunk &ch, int s, lfamd_rsrc r, uint32_t off, int gsel, int slot, int hrow) {
+        q40_traits::load(ch, s, r, off, gsel, slot, hrow);
+    }
+    __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
+        const uint4 q0 = ch.q0[s], q1 = ch.q1[s];
+        const uint2 hd = ch.hd[s];
+        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
+        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
+        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
+                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
+        const float4 d8 = *(const float4 *)(xb + XBLK_D + 16 * gsel);
+        const float d8v[4] = {d8.x, d8.y, d8.z, d8.w};
+        float acc = 0.0f;
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) { // block 4 gsel + jj
+            int isum = 0;
+#pragma unroll
+            for (int d2 = 0; d2 < 2; d2++) {
+                const int t8 = 2 * jj + d2;
+                const uint32_t x = qw[t8];
+                isum = sdot4(kvalues_lut4(x & 0x0F0F0F0Fu), yw[2 * t8], isum);
+                isum = sdot4(kvalues_lut4((x >> 4) & 0x0F0F0F0Fu), yw[2 * t8 + 1], isum);
+            }
+            const uint32_t dw = jj < 2 ? hd.x : hd.y;
+            const float d = h2f((uint16_t)((jj & 1) ? (dw >> 16) : (dw & 0xffff)));
+            acc = fmaf(d * d8v[jj], (float)isum, acc);
+        }
+        return acc;
+    }
+};
+
 // Q5_K: Q4_K with a fifth bit per weight (DequantizerQ5K, iqk_mul_mat.inc:496-511): codes 0..31, same scales / mins.
 struct q5k_traits {
     static constexpr int ACT = LFAMD_TYPE_Q8_K; // activation quantisation the reference uses for this type
@@ -597,8 +645,7 @@ struct pk_traits {
 
 // IQ4_XS on the RESIDENT compact image (generic.hip: pk4x_pack_kernel): codebook indices on the P4K nibble lattice, so a dword's
 // nibbles already sit in the order of the staged activation codes; the 16-entry int8 codebook (kvalues_iq4nl,
-// iqk_mul_mat.inc:601-628 looks it up with a byte shuffle too) is four registers and three v_perm per four codes: the lower
-// and the upper eight entries by the index's low three bits, then byte i of one or the other by its bit 3.
+// iqk_mul_mat.inc:601-628 looks it up with a byte shuffle too) is looked up by kvalues_lut4 (above, shared with IQ4_NL).
 struct iq4c_traits {
     static constexpr int ACT = LFAMD_TYPE_Q8_K;
     static constexpr int TILE = P4K_TILE;
@@ -609,12 +656,6 @@ struct iq4c_traits {
         ch.q0[s] = buf_ld16_nt(r, off + (2 * gsel + 0) * 1024 + slot * 16);
         ch.q1[s] = buf_ld16_nt(r, off + (2 * gsel + 1) * 1024 + slot * 16);
         ch.hd[s] = buf_ld16(r, off + P4K_HDR + hrow * 16);
-    }
-    __device__ static inline uint32_t lut4(uint32_t n) { // four indices (one per byte) -> four codebook values
-        constexpr uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u; // kvalues_iq4nl, 4 entries each
-        const uint32_t sel = n & 0x07070707u;
-        const uint32_t lo = __builtin_amdgcn_perm(T1, T0, sel), hi = __builtin_amdgcn_perm(T3, T2, sel);
-        return __builtin_amdgcn_perm(hi, lo, ((n >> 1) & 0x04040404u) | 0x03020100u);
     }
     __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
         const uint4 q0 = ch.q0[s], q1 = ch.q1[s], hd = ch.hd[s];
@@ -631,8 +672,8 @@ struct iq4c_traits {
 #pragma unroll
             for (int e = 0; e < 2; e++) {
                 const uint32_t x = qw[2 * u + e];
-                isum = sdot4(lut4(x & 0x0F0F0F0Fu), yw[2 * (2 * u + e)], isum);
-                isum = sdot4(lut4((x >> 4) & 0x0F0F0F0Fu), yw[2 * (2 * u + e) + 1], isum);
+                isum = sdot4(kvalues_lut4(x & 0x0F0F0F0Fu), yw[2 * (2 * u + e)], isum);
+                isum = sdot4(kvalues_lut4((x >> 4) & 0x0F0F0F0Fu), yw[2 * (2 * u + e) + 1], isum);
             }
             sumi += (int)(int8_t)((scw >> (8 * u)) & 0xff) * isum;
         }

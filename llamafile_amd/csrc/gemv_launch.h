@@ -77,7 +77,7 @@ struct q80_mats {
 // for a form the unit does not hold.  (variant, nc, f32in, nw, ch); the two-type units: type A of the pair, Q6_K as type B.
 typedef const void *gemv_kernel_fn(int variant, int nc, int f32in, int nw, int ch);
 gemv_kernel_fn lfamd_gemv_kernel_q4k, lfamd_gemv_kernel_q5k, lfamd_gemv_kernel_q6k, lfamd_gemv_kernel_q40, lfamd_gemv_kernel_q41,
-    lfamd_gemv_kernel_q50, lfamd_gemv_kernel_q51, lfamd_gemv_kernel_q2k, lfamd_gemv_kernel_q3k, lfamd_gemv_kernel_iq4xs,
+    lfamd_gemv_kernel_q50, lfamd_gemv_kernel_q51, lfamd_gemv_kernel_q2k, lfamd_gemv_kernel_q3k, lfamd_gemv_kernel_iq4xs, lfamd_gemv_kernel_iq4nl,
     lfamd_gemv_kernel_q4k_q6k, lfamd_gemv_kernel_q5k_q6k;
 // Q8_0 (gemv_q80.hip: f32 activations, gemv_q80b.hip: Q8_0 blocks); mode = the summation form, see gemv_q80_kernel
 const void *lfamd_gemv_kernel_q80_f32(int nc, int mode);

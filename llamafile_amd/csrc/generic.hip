@@ -1,7 +1,7 @@
 // generic.hip — mat-mul on RAW-layout weights, and the upload-time / per-call canonical images.
 //
 // The untuned kernels serve what has no resident packed layout: the legacy 32-block types when a row is not a whole
-// number of 256-weight groups (Q4_0, Q4_1, Q5_0, Q5_1; tinyblas_cpu_sgemm.inc:45-240, iqk_mul_mat.inc:998-1349) and
+// number of 256-weight groups (Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL; tinyblas_cpu_sgemm.inc:45-240, iqk_mul_mat.inc:998-1349) and
 // float weights outside the MFMA body's shapes, with the reference's arithmetic: exact integer block dot products, f32
 // scales.  Every K-quant and IQ4_XS is packed (lfamd_device.h) and never comes here.
 //
@@ -70,6 +70,11 @@ __global__ __launch_bounds__(256) void generic_legacy_kernel(const uint8_t *__re
             for (int j = 0; j < 16; j++) {
                 q[j] = (blk[2 + j] & 15) - 8;
                 q[j + 16] = (blk[2 + j] >> 4) - 8;
+            }
+        } else if constexpr (TYPE == LFAMD_TYPE_IQ4_NL) { // Q4_0's block, the nibbles index the codebook
+            for (int j = 0; j < 16; j++) {
+                q[j] = kvalues_iq4nl_dev[blk[2 + j] & 15];
+                q[j + 16] = kvalues_iq4nl_dev[blk[2 + j] >> 4];
             }
         } else if constexpr (TYPE == LFAMD_TYPE_Q4_1) {
             mval = h2f(*(const uint16_t *)(blk + 2));
@@ -162,6 +167,9 @@ extern "C" hipError_t lfamd_launch_generic(int Atype, const void *A, long m, lon
     switch (Atype) {
     case LFAMD_TYPE_Q4_0:
         LG(LFAMD_TYPE_Q4_0, 18, false);
+        break;
+    case LFAMD_TYPE_IQ4_NL:
+        LG(LFAMD_TYPE_IQ4_NL, 18, false);
         break;
     case LFAMD_TYPE_Q4_1:
         LG(LFAMD_TYPE_Q4_1, 20, true);

@@ -58,17 +58,19 @@ void logf(const char *fmt, const char *a = "", const char *b = "") {
 struct type_row {
     int id;
     const char *name;
+    bool optional = false; // a host whose table does not name the type still links; the type is declined (supports_op says no)
 };
 // the types this module has kernels for, with upstream's names (ggml.c type_traits[].type_name)
 const type_row k_types[] = {{LFAMD_TYPE_F32, "f32"},   {LFAMD_TYPE_F16, "f16"},   {LFAMD_TYPE_Q4_0, "q4_0"}, {LFAMD_TYPE_Q4_1, "q4_1"},
                             {LFAMD_TYPE_Q5_0, "q5_0"}, {LFAMD_TYPE_Q5_1, "q5_1"}, {LFAMD_TYPE_Q8_0, "q8_0"}, {LFAMD_TYPE_Q2_K, "q2_K"},
                             {LFAMD_TYPE_Q3_K, "q3_K"}, {LFAMD_TYPE_Q4_K, "q4_K"}, {LFAMD_TYPE_Q5_K, "q5_K"}, {LFAMD_TYPE_Q6_K, "q6_K"},
-                            {LFAMD_TYPE_IQ4_XS, "iq4_xs"}, {LFAMD_TYPE_BF16, "bf16"}};
+                            {LFAMD_TYPE_IQ4_XS, "iq4_xs"}, {LFAMD_TYPE_BF16, "bf16"}, {LFAMD_TYPE_IQ4_NL, "iq4_nl", true}};
+bool g_type_declined[sizeof(k_types) / sizeof(k_types[0])]; // optional types the linked host does not know (ggml_cuda_link)
 
 bool type_ok(int t) {
-    for (const type_row &r : k_types)
-        if (r.id == t)
-            return true;
+    for (size_t i = 0; i < sizeof(k_types) / sizeof(k_types[0]); i++)
+        if (k_types[i].id == t)
+            return !g_type_declined[i];
     return false;
 }
 
@@ -872,8 +874,12 @@ GGML_CALL bool ggml_cuda_link(const struct ggml_backend_api *backend_api) {
         return false;
     }
     // type numbers, block and element sizes must be the ones this module was built for
-    for (const type_row &r : k_types) {
+    for (size_t i = 0; i < sizeof(k_types) / sizeof(k_types[0]); i++) {
+        const type_row &r = k_types[i];
         const char *n = backend_api->ggml_type_name(r.id);
+        g_type_declined[i] = r.optional && (!n || strcmp(n, r.name)); // (a host built before the type existed)
+        if (g_type_declined[i])
+            continue;
         if (!n || strcmp(n, r.name) || backend_api->ggml_type_size(r.id) != lfamd_type_size(r.id) ||
             backend_api->ggml_blck_size(r.id) != lfamd_blck_size(r.id)) {
             logf("%s: ggml type %s does not match this module's block formats: refusing to link\n", "ggml_cuda_link", r.name);

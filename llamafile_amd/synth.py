@@ -15,7 +15,7 @@ from . import ggml_types as T
 _SCALE_OFF = {
     T.Q4_0: (0, None), T.Q4_1: (0, 2), T.Q5_0: (0, None), T.Q5_1: (0, 2), T.Q8_0: (0, None),
     T.Q2_K: (80, 82), T.Q3_K: (108, None), T.Q4_K: (0, 2), T.Q5_K: (0, 2), T.Q6_K: (208, None),
-    T.IQ4_XS: (0, None),
+    T.IQ4_XS: (0, None), T.IQ4_NL: (0, None),
 }
 
 
