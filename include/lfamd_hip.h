@@ -190,7 +190,26 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
  * faster, the small-batch MFMA kernel (also 9 .. 32 tokens on deep rows and matrices of at most 8192 rows: csrc/gemm_sb.hip);
  * larger batches -> dequant-to-MFMA GEMM on 64- / 128-token tiles (plain F16 / BF16 weights and Q8_0: the vendor GEMM instead when
  * lfamd_vendor_gemm_available()).  `workspace` must hold lfamd_mul_mat_workspace() bytes (may be NULL
- * if that is 0). */
+ * if that is 0).
+ *
+ * Operand layout of lfamd_mul_mat, lfamd_mul_mat_multi, lfamd_mul_mat_multi_types, lfamd_mul_mat_id and lfamd_mul_mat_id_multi,
+ * checked before any launch (LFAMD_ERR_INVALID, nothing written; a workspace smaller than lfamd_mul_mat_workspace() — of the
+ * set's largest for the _multi calls — or lfamd_mul_mat_id_workspace() is LFAMD_ERR_WORKSPACE, whichever body the call would run):
+ *   - d_B / d_thought, F32 rows under QUANTISED weights: 16-byte aligned, b_row_bytes a multiple of 16 (the staging kernels and the
+ *     decode GEMVs read the rows as float4);
+ *   - d_B / d_thought in the vec_dot format: the format's own alignment and no more — Q8_K and Q8_1 rows 4-byte aligned with
+ *     b_row_bytes a multiple of 4, Q8_0 rows 2-byte aligned with b_row_bytes a multiple of 2 (292-, 36- and 34-byte blocks put every
+ *     block behind the first at that alignment anyway; the kernels read fields and code words, never more);
+ *   - d_B under F32 / F16 / BF16 weights: aligned to the element (4 / 2 bytes), b_row_bytes a multiple of it.  Rows that are also
+ *     16-byte aligned with b_row_bytes a multiple of 16 take the 16-byte-load GEMV (n <= 8); any other layout runs the generic
+ *     kernel instead — the same products summed in another order, within 2e-6.  Batches stage the rows element by element where
+ *     they are not aligned and give the same bits either way;
+ *   - b_row_bytes is at least the row's size and otherwise free: the bytes between rows are never read or written;
+ *   - d_C / d_result: 4-byte aligned, ldc >= m and otherwise free; nothing outside the m x n results is written;
+ *   - d_workspace: 256-byte aligned (every device allocation is).  Its contents on entry do not matter — nothing in it is read
+ *     before the same call wrote it — and no byte beyond lfamd_mul_mat_workspace() / lfamd_mul_mat_id_workspace() is touched;
+ *   - d_plan: 4-byte aligned int32, contiguous [tokens][thinkers];
+ *   - a staged image (LFAMD_TYPE_STAGED_*): 16-byte aligned, b_row_bytes ignored (below). */
 size_t lfamd_mul_mat_workspace(int Atype, long m, long k, long n);
 int lfamd_mul_mat(int Atype, const void *d_A_packed, long m, long k, int Btype, const void *d_B,
                   size_t b_row_bytes, long n, float *d_C, long ldc, void *d_workspace,

@@ -10,6 +10,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+
 static thread_local char g_err[512] = "";
 
 static int fail(int code, const char *fmt, const char *detail) {
@@ -550,6 +552,42 @@ static bool aligned16(const void *p) {
     return ((uintptr_t)p & 15) == 0;
 }
 
+static bool workspace_short(size_t need, const void *d_ws, size_t ws_bytes) {
+    return need && (ws_bytes < need || !d_ws);
+}
+
+// The largest lfamd_mul_mat_workspace of sibling matrices (type of matrix j: Atype[j * type_stride]), whichever route runs them; a
+// staged image brings its own staging, so those calls keep the sizes their routes check
+static size_t set_workspace(int count, const int *Atype, int type_stride, const long *m, long k, int Btype, long n) {
+    size_t need = 0;
+    for (int j = 0; j < count && Btype != LFAMD_TYPE_STAGED_Q8K && Btype != LFAMD_TYPE_STAGED_SCALED; j++)
+        if (m[j] > 0)
+            need = std::max(need, lfamd_mul_mat_workspace(Atype[j * type_stride], m[j], k, n));
+    return need;
+}
+
+// The operand layouts every mat-mul entry point takes (include/lfamd_hip.h, "Operand layout"), checked before the first launch:
+// activation rows (not a staged image) at the alignment their readers need, with a stride that keeps it; f32 results; a workspace
+// at an allocation's alignment.  quantised: one of the weight types of the call is not a float type (its f32 rows are read as
+// float4 by the staging kernels and the decode GEMVs).
+static int check_operands(const char *who, bool quantised, int Btype, const void *d_B, size_t b_row_bytes, int count, float *const *d_C,
+                          const void *d_ws, size_t ws_bytes) {
+    if (Btype != LFAMD_TYPE_STAGED_Q8K && Btype != LFAMD_TYPE_STAGED_SCALED) {
+        const size_t a = Btype == LFAMD_TYPE_F32    ? (quantised ? 16 : 4)
+                         : Btype == LFAMD_TYPE_Q8_K ? 4
+                         : Btype == LFAMD_TYPE_Q8_1 ? 4
+                                                    : 2; // (Q8_0, F16, BF16)
+        if ((uintptr_t)d_B % a || b_row_bytes % a)
+            return fail(LFAMD_ERR_INVALID, "%s: activation rows are not aligned (base and row stride) as include/lfamd_hip.h asks", who);
+    }
+    for (int j = 0; j < count; j++)
+        if ((uintptr_t)d_C[j] % 4)
+            return fail(LFAMD_ERR_INVALID, "%s: a result pointer is not 4-byte aligned", who);
+    if (d_ws && ws_bytes && (uintptr_t)d_ws % 256)
+        return fail(LFAMD_ERR_INVALID, "%s: the workspace is not 256-byte aligned", who);
+    return LFAMD_OK;
+}
+
 // Everything lfamd_mul_mat checks before its first launch: LFAMD_OK and the plan, or the error the call returns.
 static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n, long ldc, const void *d_ws,
                          size_t ws_bytes, unsigned flags, mm_plan &p) {
@@ -589,6 +627,10 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: FORCE_GENERIC needs RAW-layout weights; this type is packed%s", "");
     if (uses_ws && (ws_bytes < need || !d_ws))
         return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace too small%s", "");
+    // the size the header asks for, whichever body runs: a caller that sizes the workspace by anything but lfamd_mul_mat_workspace()
+    // learns it on every call, not on the day a flag or a shape picks the body with the largest one
+    if (!staged && workspace_short(lfamd_mul_mat_workspace(Atype, m, k, n), d_ws, ws_bytes))
+        return fail(LFAMD_ERR_WORKSPACE, "mul_mat: workspace smaller than lfamd_mul_mat_workspace()%s", "");
     return LFAMD_OK;
 }
 
@@ -666,7 +708,7 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
         return LFAMD_OK;
     }
     case mm_body::float_lt: // the vendor's GEMM on plain 16-bit float weights
-        if (aligned16(d_A) && (Btype == LFAMD_TYPE_F32 || (aligned16(d_B) && !(b_row_bytes & 15)))) {
+        if (aligned16(d_A) && aligned16(d_B) && !(b_row_bytes & 15)) { // (rows_to_16 reads f32 rows as float4)
             const void *X16 = d_B;
             long ldx = (long)(b_row_bytes / 2);
             if (Btype == LFAMD_TYPE_F32) {
@@ -735,8 +777,10 @@ int lfamd_mul_mat(int Atype, const void *d_A, long m, long k, int Btype, const v
                   void *d_ws, size_t ws_bytes, unsigned flags, void *stream) {
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
     mm_plan p = {};
-    const int r = check_mul_mat(Atype, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags, p);
+    int r = check_mul_mat(Atype, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags, p);
     if (r != LFAMD_OK || m == 0 || n == 0)
+        return r;
+    if ((r = check_operands("mul_mat", !float_type(Atype), Btype, d_B, b_row_bytes, 1, &d_C, d_ws, ws_bytes)) != LFAMD_OK)
         return r;
     return launch_mul_mat(p, Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags, (hipStream_t)stream);
 }
@@ -927,7 +971,12 @@ int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long
                         unsigned flags, void *stream) {
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
     const mm_group_plan g = plan_group(Atype, count, m, k, Btype, b_row_bytes, n, ldc, flags);
-    const int r = check_group(g, Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags);
+    int r = check_group(g, Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags);
+    if (r == LFAMD_OK && g.route != mm_route::none && n > 0) {
+        if (workspace_short(set_workspace(count, &Atype, 0, m, k, Btype, n), d_ws, ws_bytes))
+            return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi: workspace smaller than the largest lfamd_mul_mat_workspace() of the set%s", "");
+        r = check_operands("mul_mat_multi", !float_type(Atype), Btype, d_B, b_row_bytes, count, d_C, d_ws, ws_bytes);
+    }
     return r != LFAMD_OK ? r : launch_group(g, Atype, count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags, stream);
 }
 
@@ -1011,6 +1060,15 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
         if (r != LFAMD_OK)
             return r;
     }
+    if (n > 0) {
+        bool quantised = false;
+        for (int j = 0; j < count; j++)
+            quantised = quantised || !float_type(Atype[j]);
+        if (workspace_short(set_workspace(count, Atype, 1, m, k, Btype, n), d_ws, ws_bytes))
+            return fail(LFAMD_ERR_WORKSPACE, "mul_mat_multi_types: workspace smaller than the largest lfamd_mul_mat_workspace() of the set%s", "");
+        if (const int r = check_operands("mul_mat_multi_types", quantised, Btype, d_B, b_row_bytes, count, d_C, d_ws, ws_bytes))
+            return r;
+    }
     hipStream_t s = (hipStream_t)stream;
     const lfamd_kq_image im = lfamd_kq_image_of(k, n);
     uint8_t *img = p.workspace ? (uint8_t *)d_ws : (uint8_t *)const_cast<void *>(d_B); // (a staged image has the workspace's layout)
@@ -1070,6 +1128,10 @@ int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int expert
     size_t need = lfamd_moe_workspace(type, rows, cols, experts, tokens, thinkers);
     if (need && (ws_bytes < need || !d_ws))
         return fail(LFAMD_ERR_WORKSPACE, "mul_mat_id: workspace too small%s", "");
+    if (b_row_bytes < lfamd_row_size(Btype, cols) || !d_plan || (uintptr_t)d_plan % 4)
+        return fail(LFAMD_ERR_INVALID, "mul_mat_id: activation row stride too small, or the routing table is NULL or not 4-byte aligned%s", "");
+    if (const int r = check_operands("mul_mat_id", true, Btype, d_thought, b_row_bytes, 1, &d_result, d_ws, ws_bytes))
+        return r;
     HIPCHK(lfamd_launch_moe(type, d_W, rows, cols, experts, lfamd_packed_size(type, rows, cols), Btype, d_thought,
                             b_row_bytes, tasks, tokens, d_plan, thinkers, d_result, d_ws, ws_bytes, flags,
                             (hipStream_t)stream),
@@ -1094,6 +1156,11 @@ int lfamd_mul_mat_id_multi(int type, int count, const void *const *d_W, long row
             return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: null expert stack or result%s", "");
     if (tasks <= 0 || tasks > thinkers || !type_known(Btype))
         return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: bad shape or activation type%s", "");
+    if ((uintptr_t)d_plan % 4)
+        return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: the routing table is not 4-byte aligned%s", "");
+    if (tokens > 0 && rows > 0)
+        if (const int r = check_operands("mul_mat_id_multi", true, Btype, d_thought, b_row_bytes, count, d_result, d_ws, ws_bytes))
+            return r;
     if (count <= 4 && type_known(type) && rows > 0 && cols > 0 && experts > 0 && thinkers > 0 && thinkers <= experts && tokens > 0 &&
         b_row_bytes >= lfamd_row_size(Btype, cols) && lfamd_moe_decode_multi_ok(type, cols, Btype, tasks, tokens, flags)) {
         HIPCHK(lfamd_launch_moe_decode_multi(type, count, d_W, rows, cols, experts, lfamd_packed_size(type, rows, cols), Btype, d_thought,

@@ -460,6 +460,19 @@ bool op_layout_agrees(const struct ggml_tensor *op) {
     return ok;
 }
 
+// The operand layout lfamd_mul_mat / lfamd_mul_mat_id take (include/lfamd_hip.h): f32 activation rows of quantised weights are
+// read as float4, so the tensor's base (a view's offset included: supports_op may be asked before the tensor has its address),
+// its row stride and the strides of the slices a call starts from are multiples of 16; float weights take any f32 rows.
+// Declined here, a node is not accepted by supports_op and then failed by graph_compute over its layout.
+bool rows_aligned(const struct ggml_tensor *b, size_t align) {
+    if ((uintptr_t)b->data % align || b->view_offs % align)
+        return false;
+    for (int i = 1; i < 4; i++)
+        if (b->ne[i] > 1 && b->nb[i] % align)
+            return false;
+    return true;
+}
+
 bool mul_mat_supported(const struct ggml_tensor *op) {
     const struct ggml_tensor *a = op->src[0], *b = op->src[1];
     if (!a || !b || !type_ok(a->type) || b->type != LFAMD_TYPE_F32 || op->type != LFAMD_TYPE_F32)
@@ -470,7 +483,7 @@ bool mul_mat_supported(const struct ggml_tensor *op) {
         return false;
     if (lfamd_packed_size(a->type, (long)a->ne[1], (long)a->ne[0]) == 0 && a->ne[1] && a->ne[0])
         return false;
-    return true;
+    return rows_aligned(b, lfamd_blck_size(a->type) == 1 ? 4 : 16);
 }
 
 // MUL_MAT with a row-split src0 (ggml_cuda_op_mul_mat with split = true, ggml-cuda.cu.patch:18060-18330): device d computes
@@ -586,6 +599,14 @@ bool mul_mat_id_supported(const struct ggml_tensor *op) {
     if (!g_api->ggml_is_contiguous(as) || !g_api->ggml_is_contiguous(b) || !g_api->ggml_is_contiguous(op) || as->ne[3] != 1)
         return false;
     if (b->ne[1] != 1 && b->ne[1] != ids->ne[0])
+        return false;
+    if (ids->nb[0] != 4 || !rows_aligned(ids, 4) || !rows_aligned(b, 16))
+        return false;
+    // src1 is F32 here, and lfamd_mul_mat_id takes F32 activations for Q4_K / Q5_K / Q6_K experts only (other types want rows in
+    // their vec_dot format: LFAMD_ERR_UNSUPPORTED); batches of more than 4 tokens go through the routed launch and its limits
+    if (as->type != LFAMD_TYPE_Q4_K && as->type != LFAMD_TYPE_Q5_K && as->type != LFAMD_TYPE_Q6_K)
+        return false;
+    if (b->ne[2] > 4 && (as->ne[2] >= 255 || b->ne[2] * ids->ne[0] > 60 * 1024))
         return false;
     return as->ne[0] % lfamd_blck_size(as->type) == 0 && lfamd_packed_size(as->type, (long)as->ne[1], (long)as->ne[0]) != 0;
 }

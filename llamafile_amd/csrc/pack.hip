@@ -661,9 +661,20 @@ __global__ __launch_bounds__(256) void prep_float_kernel(const uint8_t *__restri
     int t = threadIdx.x & 63;
     uint16_t o[4] = {0, 0, 0, 0};
     if (tok < n) {
+        // rows of float weights' activations may sit at any element-aligned address (include/lfamd_hip.h): whole 16- / 8-byte loads
+        // only where the row is aligned to them, element by element otherwise (the same values either way)
+        const uint8_t *row = X + tok * x_row_bytes;
         if constexpr (F32IN) {
-            const float4 f = *(const float4 *)((const float *)(X + tok * x_row_bytes) + (size_t)b * 256 + 4 * t);
-            const float v[4] = {f.x, f.y, f.z, f.w};
+            const float *src = (const float *)row + (size_t)b * 256 + 4 * t;
+            float v[4];
+            if (((uintptr_t)row & 15) == 0) {
+                const float4 f = *(const float4 *)src;
+                v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    v[e] = src[e];
+            }
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 if constexpr (OUT == LFAMD_TYPE_F16) {
@@ -673,9 +684,14 @@ __global__ __launch_bounds__(256) void prep_float_kernel(const uint8_t *__restri
                     o[e] = (u & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((u >> 16) | 64) : (uint16_t)((u + (0x7fffu + ((u >> 16) & 1))) >> 16);
                 }
             }
-        } else {
-            const uint2 w = *(const uint2 *)(X + tok * x_row_bytes + ((size_t)b * 256 + 4 * t) * 2);
+        } else if (((uintptr_t)row & 7) == 0) {
+            const uint2 w = *(const uint2 *)(row + ((size_t)b * 256 + 4 * t) * 2);
             o[0] = (uint16_t)w.x, o[1] = (uint16_t)(w.x >> 16), o[2] = (uint16_t)w.y, o[3] = (uint16_t)(w.y >> 16);
+        } else {
+            const uint16_t *src = (const uint16_t *)row + (size_t)b * 256 + 4 * t;
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                o[e] = src[e];
         }
     }
     *(uint2 *)(Xh + ((size_t)b * n_pad + tok) * 256 + 4 * t) =

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from llamafile_amd import ggml_types as T, synth
+from llamafile_amd import _hip, ggml_types as T, synth
 
 BAND_MIN, BAND_MAX, BAND_SCMAX, BAND_SCNEG, BAND_ALT = 0, 1, 2, 3, 4
 ZERO_ROW = 6  # every block: d = dmin = 0
@@ -195,3 +195,42 @@ def for_vec_dot(x: np.ndarray, vec_dot_type: int) -> np.ndarray:
     small = (bmax > 0) & (bmax < 1e-2)
     xb[small] *= (np.float32(1e-2) / bmax[small])[:, None]
     return x
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# One entry per batch body the dispatcher can pick (test_gpu_operand_extremes.py feeds them the operands above,
+# test_gpu_operand_layouts.py varies where their operands sit).  Flags by the names of CASE_FLAGS.
+CASE_FLAGS = {"precise": _hip.FLAG_PRECISE, "narrow": _hip.FLAG_GEMM_NARROW, "plain": _hip.FLAG_GEMM_PLAIN,
+              "q80_exact": _hip.FLAG_Q80_EXACT, "generic": _hip.FLAG_FORCE_GENERIC}
+# (type, m, n, k, flags, expected answer of lfamd_mul_mat_is_exact or None)
+CASES = [
+    # small batch gemm_sb (SB_SHAPES: at most one row tile per CU): the int8 body for Q4_K at 4 tokens, f16 bodies at 9 .. 32
+    (T.Q4_K, 1000, 4, 2048, (), True),
+    (T.Q5_K, 1000, 9, 2048, (), True), (T.Q5_K, 1000, 32, 2048, (), True),
+    (T.Q6_K, 1000, 9, 2048, (), True), (T.Q6_K, 1000, 17, 2048, (), True), (T.Q6_K, 1000, 32, 2048, (), True),
+    # the int8 body: 4096 x 4096 x 512 class grid
+    (T.Q4_K, 4096, 512, 4096, (), True),
+    # scaled f16 bodies at 512 tokens: the 14336-row Q4_K grid (too many tiles for the int8 body), Q5_K, Q6_K
+    (T.Q4_K, 14336, 512, 4096, (), False), (T.Q5_K, 4096, 512, 4096, (), False), (T.Q6_K, 4096, 512, 4096, (), False),
+    # the exact-code f16 bodies
+    (T.Q4_K, 1024, 200, 2048, ("precise",), True), (T.Q4_K, 1024, 200, 2048, ("narrow",), True),
+    (T.Q4_K, 1024, 200, 2048, ("plain",), True), (T.Q5_K, 1024, 200, 2048, ("precise",), True),
+    (T.Q5_K, 1024, 200, 2048, ("narrow",), True), (T.Q5_K, 1024, 200, 2048, ("plain",), True),
+    (T.Q6_K, 1024, 200, 2048, ("precise",), None), (T.Q6_K, 1024, 200, 2048, ("narrow",), None),
+    # canonical image (n > 8)
+    (T.Q2_K, 256, 64, 1024, (), True), (T.Q3_K, 256, 64, 1024, (), True), (T.IQ4_XS, 256, 64, 1024, (), False),
+    # legacy 32-blocks: P40, PCL
+    (T.Q4_0, 256, 64, 1024, (), True), (T.Q4_1, 256, 64, 1024, (), True), (T.Q5_0, 256, 64, 1024, (), True),
+    (T.Q5_1, 256, 64, 1024, (), True),
+    # Q8_0: the f16 MFMA body by default; the bit-exact kernel by flag and for rows that are not whole 128-weight quads
+    (T.Q8_0, 512, 200, 1024, (), False), (T.Q8_0, 512, 64, 1024, ("q80_exact",), True), (T.Q8_0, 512, 64, 1056, (), True),
+    # the generic kernels: rows kept as GGUF rows (legacy types, not whole 256-weight groups)
+    (T.Q4_0, 100, 40, 288, ("generic",), True), (T.Q4_1, 100, 40, 288, ("generic",), True),
+    (T.Q5_0, 100, 40, 288, ("generic",), True), (T.Q5_1, 100, 40, 288, ("generic",), True),
+    (T.Q8_0, 100, 40, 288, (), True), (T.Q4_0, 100, 3, 288, ("generic",), True),
+]
+
+
+def case_id(c):
+    t, m, n, k, fl, _ = c
+    return f"{T.NAMES[t]}-{m}x{n}x{k}" + ("-" + "+".join(fl) if fl else "")

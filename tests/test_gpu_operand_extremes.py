@@ -12,15 +12,14 @@ import pytest
 import torch
 
 from llamafile_amd import _hip, ggml_types as T, synth
-from extremes import ZERO_ROW, ZERO_TOKEN, KINDS, edge_scale_weights, extreme_activations, extreme_weights, for_vec_dot
+from extremes import CASES, CASE_FLAGS, ZERO_ROW, ZERO_TOKEN, KINDS, case_id, edge_scale_weights, extreme_activations, extreme_weights, for_vec_dot
 from helpers import elem_err, rel_err
 
 pytestmark = pytest.mark.gpu
 
 EXACT = (2e-6, 1e-5)
 SCALED = (1e-3, 1.5e-3)
-F = {"precise": _hip.FLAG_PRECISE, "narrow": _hip.FLAG_GEMM_NARROW, "plain": _hip.FLAG_GEMM_PLAIN,
-     "q80_exact": _hip.FLAG_Q80_EXACT, "generic": _hip.FLAG_FORCE_GENERIC}
+F = CASE_FLAGS
 
 _cache = {}
 
@@ -169,41 +168,7 @@ def test_decode_gemv(gpu, oracle, t, real_scale):
 
 
 # ------------------------------------------------------------------------------------------------------------- batch bodies
-# (type, m, n, k, flags, expected answer of lfamd_mul_mat_is_exact or None)
-CASES = [
-    # small batch gemm_sb (SB_SHAPES: at most one row tile per CU): the int8 body for Q4_K at 4 tokens, f16 bodies at 9 .. 32
-    (T.Q4_K, 1000, 4, 2048, (), True),
-    (T.Q5_K, 1000, 9, 2048, (), True), (T.Q5_K, 1000, 32, 2048, (), True),
-    (T.Q6_K, 1000, 9, 2048, (), True), (T.Q6_K, 1000, 17, 2048, (), True), (T.Q6_K, 1000, 32, 2048, (), True),
-    # the int8 body: 4096 x 4096 x 512 class grid
-    (T.Q4_K, 4096, 512, 4096, (), True),
-    # scaled f16 bodies at 512 tokens: the 14336-row Q4_K grid (too many tiles for the int8 body), Q5_K, Q6_K
-    (T.Q4_K, 14336, 512, 4096, (), False), (T.Q5_K, 4096, 512, 4096, (), False), (T.Q6_K, 4096, 512, 4096, (), False),
-    # the exact-code f16 bodies
-    (T.Q4_K, 1024, 200, 2048, ("precise",), True), (T.Q4_K, 1024, 200, 2048, ("narrow",), True),
-    (T.Q4_K, 1024, 200, 2048, ("plain",), True), (T.Q5_K, 1024, 200, 2048, ("precise",), True),
-    (T.Q5_K, 1024, 200, 2048, ("narrow",), True), (T.Q5_K, 1024, 200, 2048, ("plain",), True),
-    (T.Q6_K, 1024, 200, 2048, ("precise",), None), (T.Q6_K, 1024, 200, 2048, ("narrow",), None),
-    # canonical image (n > 8)
-    (T.Q2_K, 256, 64, 1024, (), True), (T.Q3_K, 256, 64, 1024, (), True), (T.IQ4_XS, 256, 64, 1024, (), False),
-    # legacy 32-blocks: P40, PCL
-    (T.Q4_0, 256, 64, 1024, (), True), (T.Q4_1, 256, 64, 1024, (), True), (T.Q5_0, 256, 64, 1024, (), True),
-    (T.Q5_1, 256, 64, 1024, (), True),
-    # Q8_0: the f16 MFMA body by default; the bit-exact kernel by flag and for rows that are not whole 128-weight quads
-    (T.Q8_0, 512, 200, 1024, (), False), (T.Q8_0, 512, 64, 1024, ("q80_exact",), True), (T.Q8_0, 512, 64, 1056, (), True),
-    # the generic kernels: rows kept as GGUF rows (legacy types, not whole 256-weight groups)
-    (T.Q4_0, 100, 40, 288, ("generic",), True), (T.Q4_1, 100, 40, 288, ("generic",), True),
-    (T.Q5_0, 100, 40, 288, ("generic",), True), (T.Q5_1, 100, 40, 288, ("generic",), True),
-    (T.Q8_0, 100, 40, 288, (), True), (T.Q4_0, 100, 3, 288, ("generic",), True),
-]
-
-
-def _case_id(c):
-    t, m, n, k, fl, _ = c
-    return f"{T.NAMES[t]}-{m}x{n}x{k}" + ("-" + "+".join(fl) if fl else "")
-
-
-@pytest.mark.parametrize("case", CASES, ids=_case_id)
+@pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_batch_body(gpu, oracle, case):
     """The bound is the predicate's; where the case says what the predicate must answer, it is checked too."""
     t, m, n, k, fl, expect = case

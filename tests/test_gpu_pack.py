@@ -35,14 +35,50 @@ def test_pack_matches_layout_spec(gpu, t, ref, shape):
     assert np.array_equal(got, want)
 
 
-def test_pack_honours_raw_row_stride(gpu):
-    rows, cols = 40, 512
-    raw = synth.random_weights(T.Q4_K, rows, cols, seed=3)
-    padded = np.zeros((rows, raw.shape[1] + 48), dtype=np.uint8)
-    padded[:, : raw.shape[1]] = raw
-    a = gpu.upload_weights(T.Q4_K, raw, rows, cols).data.cpu().numpy()
-    b = gpu.upload_weights(T.Q4_K, padded, rows, cols).data.cpu().numpy()
-    assert np.array_equal(a, b)
+# every type lfamd_packed_size answers for (test_stride_types_are_the_packable_types holds the list to the module's answer)
+STRIDE_TYPES = (T.F32, T.F16, T.BF16, T.Q4_0, T.Q4_1, T.Q5_0, T.Q5_1, T.Q8_0, T.Q2_K, T.Q3_K, T.Q4_K, T.Q5_K, T.Q6_K, T.IQ4_XS, T.IQ4_NL)
+# 512: the packed layouts; 288: rows that are not whole 256-weight groups, kept as GGUF rows (32-blocks and floats)
+STRIDE_CASES = [(t, 512) for t in STRIDE_TYPES] + [(t, 288) for t in STRIDE_TYPES if T.BLCK[t] <= 32]
+
+
+def test_stride_types_are_the_packable_types():
+    from llamafile_amd import _hip
+    L = _hip.lib()
+    assert sorted(t for t in T.NAMES if L.lfamd_packed_size(t, 40, 512)) == sorted(STRIDE_TYPES)
+
+
+@pytest.mark.parametrize("t,cols", STRIDE_CASES, ids=[f"{T.NAMES[t]}-{c}" for t, c in STRIDE_CASES])
+def test_pack_honours_raw_row_stride(gpu, t, cols):
+    """Rows `row size + 48` bytes apart inside a 0xFF-filled buffer pack into the image of the contiguous rows, byte for byte (both
+    images start from the same fill, so bytes a pack kernel leaves alone compare equal too), and the source is unchanged;
+    lfamd_unpack_weights with the padded raw_row_bytes writes the rows and leaves the gaps alone."""
+    import ctypes as C
+    import torch
+    from llamafile_amd import _hip
+    L = _hip.lib()
+    rows, pad = 40, 48
+    raw = synth.random_weights(t, rows, cols, seed=3)
+    rb = raw.shape[1]
+    padded = np.full((rows, rb + pad), 0xFF, dtype=np.uint8)
+    padded[:, :rb] = raw
+    size = L.lfamd_packed_size(t, rows, cols)
+    assert size > 0
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    images = []
+    for src in (raw, padded):
+        d_src = torch.from_numpy(src).cuda()
+        out = torch.full((size,), 0xEE, dtype=torch.uint8, device="cuda")
+        _hip.check(L.lfamd_pack_weights(t, rows, cols, C.c_void_p(d_src.data_ptr()), src.shape[1], C.c_void_p(out.data_ptr()), st), "pack")
+        torch.cuda.synchronize()
+        assert np.array_equal(d_src.cpu().numpy(), src), "pack wrote into its source"
+        images.append(out)
+    assert torch.equal(images[0], images[1]), T.NAMES[t]
+    back = torch.full((rows, rb + pad), 0xA5, dtype=torch.uint8, device="cuda")
+    _hip.check(L.lfamd_unpack_weights(t, rows, cols, C.c_void_p(images[1].data_ptr()), C.c_void_p(back.data_ptr()), rb + pad, st), "unpack")
+    torch.cuda.synchronize()
+    got = back.cpu().numpy()
+    assert np.array_equal(got[:, :rb], raw), T.NAMES[t]
+    assert (got[:, rb:] == 0xA5).all(), "unpack wrote between the rows"
 
 
 @pytest.mark.parametrize("t", [T.Q2_K, T.Q3_K], ids=lambda t: T.NAMES[t])
