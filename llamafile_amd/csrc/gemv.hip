@@ -50,12 +50,19 @@ static const kq_unit *kq_unit_of(int Atype) {
     return nullptr;
 }
 
-static const void *kernel_of(int Atype, int f32in, const lfamd_gemv_plan &p, int q80_mode) {
+// early: the launch fits the preloaded arguments (early_fits), so a PLAIN plan runs on the unit's EARLY kernels and a TWO_TYPES
+// plan on the two-type unit's early ones.  Same forms, so a unit that holds the planned kernel holds this one too.
+static const void *kernel_of(int Atype, int f32in, const lfamd_gemv_plan &p, int q80_mode, bool early = false) {
     if (p.variant == LFAMD_GEMV_Q80)
         return Atype != LFAMD_TYPE_Q8_0 ? nullptr : f32in ? lfamd_gemv_kernel_q80_f32(p.nc, q80_mode) : lfamd_gemv_kernel_q80_q80(p.nc, q80_mode);
     const kq_unit *u = kq_unit_of(Atype);
     gemv_kernel_fn *fn = !u ? nullptr : p.variant == LFAMD_GEMV_TWO_TYPES ? u->with_q6k : u->kernel;
-    return fn ? fn(p.variant, p.nc, f32in, p.nw, p.ch) : nullptr;
+    int variant = p.variant;
+    if (early && p.variant == LFAMD_GEMV_PLAIN)
+        variant = LFAMD_GEMV_EARLY;
+    if (early && p.variant == LFAMD_GEMV_TWO_TYPES)
+        variant = KQ_TWO_TYPES_EARLY;
+    return fn ? fn(variant, p.nc, f32in, p.nw, p.ch) : nullptr;
 }
 
 extern "C" int lfamd_gemv_has_kernel(int Atype, int f32in, const lfamd_gemv_plan *p) {
@@ -219,10 +226,33 @@ static hipError_t launch(const void *kernel, const lfamd_gemv_plan &p, void **ar
     return hipGetLastError();
 }
 
-// gemv_kq_kernel.  cnt: mats.count, or 0 where the expert is picked on the device (no early first issue)
-static hipError_t launch_kq(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nb, int n_ht, int cnt,
+// gemv_kq_kernel
+static hipError_t launch_kq(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nb, int n_ht,
                             gemv_mats &mats, hipStream_t s) {
-    void *args[] = {&B, &brb, &col0, &nb, &n_ht, (void *)&p.grid, &mats.A[0], &cnt, &mats};
+    void *args[] = {&B, &brb, &col0, &nb, &n_ht, (void *)&p.grid, &mats};
+    return launch(kernel, p, args, s);
+}
+
+// A one-column launch of one to three matrices fits the preloaded arguments of the early kernels (a PLAIN plan of four keeps
+// gemv_kq_kernel; ROWS32 and the expert launches have kernels of their own).
+static bool early_fits(const lfamd_gemv_plan &p, const gemv_mats &mats) {
+    return p.nc == 1 && mats.count <= 3 && (p.variant == LFAMD_GEMV_EARLY || p.variant == LFAMD_GEMV_PLAIN);
+}
+// the boundary behind matrix i, for the pick without a count
+static int pre_boundary(const gemv_mats &mats, int i) {
+    return i + 1 < mats.count ? mats.ht_end[i] : KQ_NO_BOUNDARY;
+}
+
+// gemv_kq_early_kernel: the column is folded into the row pointer and into a copy of the table's result pointers
+static hipError_t launch_kq_early(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nb, int n_ht,
+                                  const gemv_mats &mats, hipStream_t s) {
+    gemv_mats mc = mats;
+    for (int i = 0; i < GEMV_MAX_MATS; i++)
+        if (mc.C[i])
+            mc.C[i] += col0 * mc.ldc[i];
+    const uint8_t *xrow = (const uint8_t *)B + col0 * (long)brb;
+    int e0 = pre_boundary(mats, 0), e1 = pre_boundary(mats, 1);
+    void *args[] = {&xrow, &mc.A[0], &mc.A[1], &mc.A[2], &nb, &n_ht, (void *)&p.grid, &e0, &e1, &mc};
     return launch(kernel, p, args, s);
 }
 
@@ -230,6 +260,14 @@ static hipError_t launch_kq(const void *kernel, const lfamd_gemv_plan &p, const 
 static hipError_t launch_kq_dual(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, int nb, int n_ht_a, int n_ht_b,
                                  gemv_mats &ma, gemv_mats &mb, hipStream_t s) {
     void *args[] = {&B, &brb, &nb, &n_ht_a, &n_ht_b, (void *)&p.grid, (void *)&p.grid_b, &ma, &mb};
+    return launch(kernel, p, args, s);
+}
+
+// gemv_kq_dual_early_kernel (B: the one activation row)
+static hipError_t launch_kq_dual_early(const void *kernel, const lfamd_gemv_plan &p, const void *B, int nb, int n_ht_a, int n_ht_b,
+                                       gemv_mats &ma, gemv_mats &mb, hipStream_t s) {
+    int ea0 = pre_boundary(ma, 0);
+    void *args[] = {&B, &ma.A[0], &ma.A[1], &mb.A[0], &nb, &n_ht_a, &n_ht_b, (void *)&p.grid, &ea0, (void *)&p.grid_b, &ma, &mb};
     return launch(kernel, p, args, s);
 }
 
@@ -326,7 +364,10 @@ extern "C" hipError_t lfamd_launch_gemv_multi(int Atype, int count, const void *
     for (long col0 = 0; col0 < n && e == hipSuccess; col0 += step) {
         const int nc = (int)((n - col0) < step ? (n - col0) : step);
         lfamd_gemv_plan_of(LFAMD_GEMV_MULTI, Atype, nc, n_ht, 0, k, mats.count, cus, &p);
-        e = launch_kq(kernel_of(Atype, f32in, p, 0), p, B, b_row_bytes, col0, (int)(k / 256), n_ht, mats.count, mats, s);
+        if (early_fits(p, mats))
+            e = launch_kq_early(kernel_of(Atype, f32in, p, 0, true), p, B, b_row_bytes, col0, (int)(k / 256), n_ht, mats, s);
+        else
+            e = launch_kq(kernel_of(Atype, f32in, p, 0), p, B, b_row_bytes, col0, (int)(k / 256), n_ht, mats, s);
     }
     return e;
 }
@@ -345,7 +386,10 @@ extern "C" hipError_t lfamd_launch_gemv_dual(int type_a, int count_a, const void
     if (ma.count == 0 || mb.count == 0 || // (the caller sends an empty group through the one-type path)
         lfamd_gemv_plan_of(LFAMD_GEMV_DUAL, type_a, 1, n_ht_a, n_ht_b, k, ma.count + mb.count, lfamd_num_cus(), &p) != 0)
         return hipErrorInvalidValue;
-    return launch_kq_dual(kernel_of(type_a, Btype == LFAMD_TYPE_F32, p, 0), p, B, b_row_bytes, (int)(k / 256), n_ht_a, n_ht_b, ma, mb, s);
+    const int f32in = Btype == LFAMD_TYPE_F32;
+    if (ma.count <= 2 && mb.count == 1) // (every Q4_K_M / Q5_K_M layer: attn_q/k + attn_v)
+        return launch_kq_dual_early(kernel_of(type_a, f32in, p, 0, true), p, B, (int)(k / 256), n_ht_a, n_ht_b, ma, mb, s);
+    return launch_kq_dual(kernel_of(type_a, f32in, p, 0), p, B, b_row_bytes, (int)(k / 256), n_ht_a, n_ht_b, ma, mb, s);
 }
 
 // GGML_OP_MUL_MAT_ID for ONE activation row: `count` (<= GEMV_MAX_MATS) outputs C[j] = W[ids[id_idx[j]]] x B, the expert
@@ -365,7 +409,7 @@ extern "C" hipError_t lfamd_launch_gemv_ids(int Atype, int count, const void *co
     const void *kernel = kernel_of(Atype, Btype == LFAMD_TYPE_F32, p, 0);
     if (!kernel) // (a K-quant type whose unit holds no expert kernels)
         return hipErrorInvalidValue;
-    return launch_kq(kernel, p, B, b_row_bytes, 0, (int)(k / 256), n_ht, 0, mats, s);
+    return launch_kq(kernel, p, B, b_row_bytes, 0, (int)(k / 256), n_ht, mats, s);
 }
 
 // two experts of one tensor, each against its own activation row (ffn_down_exps at decode): one launch

@@ -16,6 +16,9 @@ __device__ static inline void load_piece(float (&v)[16], const float *x, int p) 
 #define GEMV_DIAG 0
 #endif
 #if GEMV_DIAG // development: in-kernel s_memtime stamps of two work-groups (never in the product build)
+#ifndef GEMV_DIAG_WG
+#define GEMV_DIAG_WG 100 // the second stamped work-group (the first is 0)
+#endif
 static __device__ unsigned long long g_gemv_stamps[4 * 16 * 16];
 extern "C" __attribute__((weak)) int lfamd_debug_gemv_stamps(unsigned long long *dst) { // per TU; dev only
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemv_stamps), sizeof(g_gemv_stamps));
@@ -41,7 +44,7 @@ extern "C" __attribute__((weak)) int lfamd_debug_gemv_wgs(unsigned long long *ds
 #define GSTAMP()                                                                                                 \
     do {                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if ((blockIdx.x == 0 || blockIdx.x == 100) && lane == 0 && stamp_n < 16)                                  \
+        if ((blockIdx.x == 0 || blockIdx.x == GEMV_DIAG_WG) && lane == 0 && stamp_n < 16)                                  \
             g_gemv_stamps[((blockIdx.x ? 1 : 0) * 16 + wave) * 16 + stamp_n++] = __builtin_amdgcn_s_memrealtime(); \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
     } while (0)

@@ -1146,11 +1146,23 @@ __device__ static inline float kq_sum_rows(float v) {
     return p + q;
 }
 
+// What the EARLY kernels know of their first item without the table, all of it in PRELOADED arguments: the weights of up to
+// three matrices and the two half-tile boundaries between them.  The host sets the boundary in front of an absent matrix to
+// KQ_NO_BOUNDARY, which no half-tile reaches, so the pick needs no count (gemv.hip: launch_kq_early).
+struct kq_pre {
+    const uint8_t *A0, *A1, *A2;
+    int e0, e1;
+};
+
 template <typename TR, int BT, int NW, int GEMV_CH, bool IDS, bool EARLY = false, bool PAIR = false>
 __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, const uint8_t *__restrict__ B,
                                               size_t b_row_bytes, long col0, int n_ht, const int bid, int gdim,
-                                              uint8_t *lds, const uint8_t *A0_pre, int cnt_pre) {
-    asm volatile("" : "+s"(nb), "+s"(B), "+s"(b_row_bytes), "+s"(col0), "+s"(n_ht), "+s"(gdim)); // (one s_load round)
+                                              uint8_t *lds, const kq_pre pre) {
+    // (EARLY: B is the activation row itself, b_row_bytes and col0 are the literal 0 and fold away)
+    if constexpr (EARLY)
+        asm volatile("" : "+s"(nb), "+s"(B), "+s"(n_ht), "+s"(gdim));
+    else
+        asm volatile("" : "+s"(nb), "+s"(B), "+s"(b_row_bytes), "+s"(col0), "+s"(n_ht), "+s"(gdim)); // (one s_load round)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i16 = lane & 15, h = (lane >> 4) & 1, gsel = lane >> 5;
@@ -1196,13 +1208,13 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
         pd = __builtin_amdgcn_raw_buffer_load_b32(rq, (uint32_t)pre_b * 292u, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    // a single-matrix launch (attn_output, ffn_down) knows its weights from the preloaded arguments: its first item goes
-    // out BEFORE the argument table's scalar loads have returned (~0.4 us earlier); both branches issue the same loads
+    // a launch of up to three matrices (attn_output, ffn_down; attn_q/k/v, ffn_gate + ffn_up) knows its weights and the
+    // boundaries between them from the preloaded arguments: its first item goes out BEFORE the argument table's scalar
+    // loads have returned (~0.4 us earlier); both branches issue the same loads
     typename TR::chunk bufA, bufB;
     typename TR::chunk bufA2, bufB2; // (PAIR: the second half-tile of the item; dead otherwise)
     static_assert(!(PAIR && (EARLY || IDS)), "the paired item is a variant of the plain launch");
     constexpr bool early = EARLY && !IDS; // (a kernel variant, not a run-time branch: hipcc merges its wait counts at a join)
-    (void)cnt_pre;
     // Tiles whose size is not a multiple of the 128-byte cache line (P6K: 6720 B) start 64 B into a line every other
     // super-block: then every 256-byte run of a half-tile has its edge lines in common with the other half-tile of the
     // tile, and both halves' d sit in one line.  Fetched by two work-groups on two XCDs, such a line crosses the fabric
@@ -1216,12 +1228,19 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
     };
     if constexpr (early) {
         const int hb = ht_of(bid);
-        const int hh = hb & 1;
+        const bool s1 = hb >= pre.e0, s2 = hb >= pre.e1; // (kq_pick's choice, from SGPRs the hardware filled)
+        const uint8_t *Ap = s2 ? pre.A2 : (s1 ? pre.A1 : pre.A0);
+        const int hl = hb - (s2 ? pre.e1 : (s1 ? pre.e0 : 0)); // half-tile inside the matrix
+        const int hh = hl & 1;
         const uint32_t rtb = (uint32_t)nb * TR::TILE;
-        const lfamd_rsrc r = make_rsrc(A0_pre + (size_t)(hb >> 1) * rtb, hb < n_ht ? rtb : 0u);
+        const lfamd_rsrc r = make_rsrc(Ap + (size_t)(hl >> 1) * rtb, hb < n_ht ? rtb : 0u);
 #pragma unroll
         for (int s = 0; s < GEMV_CH; s++)
             TR::load(bufA, s, r, (uint32_t)(wave + NW * s) * TR::TILE, gsel, h * 32 + hh * 16 + i16, hh * 16 + i16);
+        // (left alone, the scheduler lets the table's s_waitcnt lgkmcnt(0) in between these loads: the 16 x 1 form's header load,
+        // which the dot needs first, then waited for the table after all)
+        __builtin_amdgcn_sched_barrier(0);
+        GSTAMP(); // (the second stamp of a wave = its first weight loads are out, here as behind KQ_ISSUE below: tools/gemv_stamps.py --fused)
     }
     const kq_tab tab = kq_table(mats);
 
@@ -1401,17 +1420,28 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
 #undef KQ_CONSUME
 }
 
-template <typename TR, int NC, int BT, int NW, int GEMV_CH, bool IDS = false, bool EARLY = false, bool PAIR = false>
+template <typename TR, int NC, int BT, int NW, int GEMV_CH, bool IDS = false, bool PAIR = false>
 __global__ __launch_bounds__(NW * 64) void gemv_kq_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, long col0, int nb,
-                                                          int n_ht, int gdim, const uint8_t *__restrict__ A0, int cnt,
-                                                          const gemv_mats mats) {
-    // (A0 = mats.A[0], cnt = mats.count once more, among the PRELOADED leading arguments: a single-matrix launch issues its
-    // first weight loads without waiting for the argument table)
+                                                          int n_ht, int gdim, const gemv_mats mats) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if constexpr (NC == 1)
-        gemv_kq_body1<TR, BT, NW, GEMV_CH, IDS, EARLY, PAIR>(mats, nb, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds, A0, cnt);
+        gemv_kq_body1<TR, BT, NW, GEMV_CH, IDS, false, PAIR>(mats, nb, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds, kq_pre{});
     else
         gemv_kq_body<TR, NC, BT, NW, GEMV_CH, IDS>(mats, nb, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds);
+}
+
+// ONE activation row, one to three matrices: the 13 dwords the hardware preloads are exactly what work-group `bid` needs to
+// address its first item — the row (column offset and row stride folded in on the host, which folds the column into mats.C as
+// well), the three weight pointers, nb, n_ht, gdim and the two boundaries.  mats (and so the store path and every later item) is
+// what gemv_kq_kernel gets.
+template <typename TR, int NC, int BT, int NW, int GEMV_CH>
+__global__ __launch_bounds__(NW * 64) void gemv_kq_early_kernel(const uint8_t *__restrict__ xrow, const uint8_t *__restrict__ A0,
+                                                                const uint8_t *__restrict__ A1, const uint8_t *__restrict__ A2, int nb,
+                                                                int n_ht, int gdim, int e0, int e1, const gemv_mats mats) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    static_assert(NC == 1, "one activation row (the parameter keeps the kernel's name in line with gemv_kq_kernel's)");
+    asm volatile("" : "+s"(A0), "+s"(A1), "+s"(A2), "+s"(e0), "+s"(e1));
+    gemv_kq_body1<TR, BT, NW, GEMV_CH, false, true>(mats, nb, xrow, 0, 0, n_ht, (int)blockIdx.x, gdim, lds, kq_pre{A0, A1, A2, e0, e1});
 }
 
 // Two expert GEMVs on DIFFERENT activation rows in ONE decode launch (GGML_OP_MUL_MAT_ID ffn_down_exps: every chosen expert
@@ -1423,9 +1453,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq_ids_pair_kernel(const uint8_t
                                                                    const gemv_mats mats_a, const gemv_mats mats_b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if ((int)blockIdx.x < grid_a)
-        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_a, nb, Ba, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, nullptr, 0);
+        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_a, nb, Ba, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, kq_pre{});
     else
-        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_b, nb, Bb, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, nullptr, 0);
+        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_b, nb, Bb, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, kq_pre{});
 }
 
 // Two weight types in ONE decode launch (sibling mat-muls on the same activations whose types differ: attn_q/k in Q4_K
@@ -1438,10 +1468,28 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq_dual_kernel(const uint8_t *__
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     static_assert(TRA::ACT == TRB::ACT, "both types must share the activation image");
     if ((int)blockIdx.x < grid_a)
-        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false>(mats_a, nb, B, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, nullptr, 0);
+        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false>(mats_a, nb, B, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, kq_pre{});
     else
-        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false>(mats_b, nb, B, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, nullptr,
-                                                   0);
+        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false>(mats_b, nb, B, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, kq_pre{});
+}
+
+// ... with the first item of BOTH sub-grids from preloaded arguments, for the launch every Q4_K_M / Q5_K_M layer makes: one or
+// two matrices of type A (one boundary) and ONE of type B.  13 dwords again; grid_b, which only later items need, comes last
+// (a fourteenth dword is all the hardware grants beside the kernel-argument pointer).
+template <typename TRA, typename TRB, int BT, int NW, int GEMV_CH>
+__global__ __launch_bounds__(NW * 64) void gemv_kq_dual_early_kernel(const uint8_t *__restrict__ xrow, const uint8_t *__restrict__ Aa0,
+                                                                     const uint8_t *__restrict__ Aa1, const uint8_t *__restrict__ Ab0, int nb,
+                                                                     int n_ht_a, int n_ht_b, int grid_a, int ea0, int grid_b,
+                                                                     const gemv_mats mats_a, const gemv_mats mats_b) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    static_assert(TRA::ACT == TRB::ACT, "both types must share the activation image");
+    asm volatile("" : "+s"(Aa0), "+s"(Aa1), "+s"(Ab0), "+s"(ea0), "+s"(grid_a));
+    if ((int)blockIdx.x < grid_a)
+        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false, true>(mats_a, nb, xrow, 0, 0, n_ht_a, (int)blockIdx.x, grid_a, lds,
+                                                         kq_pre{Aa0, Aa1, Aa1, ea0, KQ_NO_BOUNDARY});
+    else
+        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false, true>(mats_b, nb, xrow, 0, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds,
+                                                         kq_pre{Ab0, Ab0, Ab0, KQ_NO_BOUNDARY, KQ_NO_BOUNDARY});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1450,7 +1498,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq_dual_kernel(const uint8_t *__
 // in one 140-second file).  Which (waves, chunk) pairs exist is the plan's range (gemv.hip: lfamd_gemv_plan_of); anything
 // else answers nullptr.
 
-// n = 1: {8 x 2, 16 x 1, 16 x 2} plain and with the early first issue; 32-row items (16 x 1 only) where the type takes them
+// n = 1: {8 x 2, 16 x 1, 16 x 2} plain (four matrices) and with the early first issue (one to three); 32-row items (16 x 1 only) where the type takes them
 template <typename TR, int BT, bool ROWS32>
 static const void *kq_kernel_1(int variant, int nw, int ch) {
     const int form = nw * 10 + ch;
@@ -1460,13 +1508,13 @@ static const void *kq_kernel_1(int variant, int nw, int ch) {
                : form == 162 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 2>
                              : nullptr;
     if (variant == LFAMD_GEMV_EARLY)
-        return form == 82    ? (const void *)gemv_kq_kernel<TR, 1, BT, 8, 2, false, true>
-               : form == 161 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1, false, true>
-               : form == 162 ? (const void *)gemv_kq_kernel<TR, 1, BT, 16, 2, false, true>
+        return form == 82    ? (const void *)gemv_kq_early_kernel<TR, 1, BT, 8, 2>
+               : form == 161 ? (const void *)gemv_kq_early_kernel<TR, 1, BT, 16, 1>
+               : form == 162 ? (const void *)gemv_kq_early_kernel<TR, 1, BT, 16, 2>
                              : nullptr;
     if constexpr (ROWS32)
         if (variant == LFAMD_GEMV_ROWS32 && form == 161)
-            return (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1, false, false, true>;
+            return (const void *)gemv_kq_kernel<TR, 1, BT, 16, 1, false, true>;
     return nullptr;
 }
 
@@ -1518,6 +1566,13 @@ static const void *kq_unit_kernel(int variant, int nc, int f32in, int nw, int ch
 // ... and a two-type unit (16 x 1, 16 x 2; the shared activation image is Q8_K)
 template <typename TRA, typename TRB>
 static const void *kq_dual_unit_kernel(int variant, int nc, int f32in, int nw, int ch) {
+    if (variant == KQ_TWO_TYPES_EARLY && nc == 1 && nw == 16 && (ch == 1 || ch == 2)) {
+        if (f32in)
+            return ch == 1 ? (const void *)gemv_kq_dual_early_kernel<TRA, TRB, LFAMD_TYPE_F32, 16, 1>
+                           : (const void *)gemv_kq_dual_early_kernel<TRA, TRB, LFAMD_TYPE_F32, 16, 2>;
+        return ch == 1 ? (const void *)gemv_kq_dual_early_kernel<TRA, TRB, LFAMD_TYPE_Q8_K, 16, 1>
+                       : (const void *)gemv_kq_dual_early_kernel<TRA, TRB, LFAMD_TYPE_Q8_K, 16, 2>;
+    }
     if (variant != LFAMD_GEMV_TWO_TYPES || nc != 1 || nw != 16 || (ch != 1 && ch != 2))
         return nullptr;
     if (f32in)

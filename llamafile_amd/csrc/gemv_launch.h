@@ -73,6 +73,14 @@ struct q80_mats {
     int count;
 };
 
+// The n = 1 launches of one to three matrices address their first item from preloaded kernel arguments (gemv_impl.h: kq_pre).
+// The boundary in front of an absent matrix: a value no half-tile index reaches.
+#define KQ_NO_BOUNDARY 0x7fffffff
+// What the launcher asks a two-type unit for when the launch fits those arguments (<= 2 matrices of type A, one of type B): not a
+// plan variant — the plan says LFAMD_GEMV_TWO_TYPES either way.  (One type: the unit's LFAMD_GEMV_EARLY kernels, which a PLAIN
+// plan of two or three matrices runs on as well.)
+#define KQ_TWO_TYPES_EARLY 0x100
+
 // Each unit maps a planned launch to one of the kernels it instantiates: the kernel's address for hipLaunchKernel, nullptr
 // for a form the unit does not hold.  (variant, nc, f32in, nw, ch); the two-type units: type A of the pair, Q6_K as type B.
 typedef const void *gemv_kernel_fn(int variant, int nc, int f32in, int nw, int ch);
