@@ -284,6 +284,21 @@ int lfamd_mul_mat_takes_staged(int Atype, long m, long k, long n, unsigned flags
 #define LFAMD_TYPE_STAGED_SCALED 0x1001
 size_t lfamd_staged_scaled_size(long k, long nrows);
 int lfamd_mul_mat_takes_staged_scaled(int Atype, long m, long k, long n, unsigned flags);
+/* The same for the batch bodies of the legacy 32-block weight types, whose activations are Q8_0 / Q8_1 blocks: LFAMD_TYPE_STAGED_B32, a
+ * buffer of lfamd_staged_b32_size(k, nrows) bytes written by the two _b32 producers below.  With n_pad = roundup(nrows, 128) and nb
+ * = k / 256 it holds, each part starting on 256 bytes:
+ *     Xh  f16 [nb][n_pad][256]   the codes of quantize_row_q8_0 as f16
+ *     d8T f32 [nb * 8][n_pad]    the blocks' f32(f16(d))
+ *     sT  f32 [nb * 8][n_pad]    the blocks' f32(f16(sum * d)) of quantize_row_q8_1 (d not yet rounded); always filled
+ * so one image serves Q4_0 / IQ4_NL (which read Xh and d8T) and Q4_1 / Q5_0 / Q5_1 (Q4_1 / Q5_1 read sT too).  k % 256 == 0.
+ * lfamd_mul_mat_takes_staged_b32() says whether a call accepts it: batches (n > 8) of Q4_0, IQ4_NL, Q4_1, Q5_0, Q5_1 whose rows are
+ * whole 256-weight groups, without LFAMD_FLAG_FORCE_GENERIC.  lfamd_mul_mat and lfamd_mul_mat_multi then run the GEMM alone — no
+ * staging launch, the workspace untouched — and give the bits of the same call on the producer's f32 output.  Other calls answer
+ * LFAMD_ERR_UNSUPPORTED for it (lfamd_mul_mat_multi_types, lfamd_mul_mat_id and lfamd_mul_mat_id_multi always do); a NULL image or
+ * one not 16-byte aligned is LFAMD_ERR_INVALID.  Q8_0 weight batches stage in a layout of their own and take Q8_0 rows or f32. */
+#define LFAMD_TYPE_STAGED_B32 0x1002
+size_t lfamd_staged_b32_size(long k, long nrows);
+int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned flags);
 
 /* ---- the step in front of the path, fused: RMS-norm x weight -> Q8_K -----------------------------
  * y[i] = (x[i] * 1/sqrtf(mean(x^2) + eps)) * weight[i] per row (ggml_compute_forward_rms_norm_f32 + the MUL node; GPU
@@ -317,6 +332,30 @@ int lfamd_rms_norm_quantize(const float *d_x, size_t x_row_bytes, const float *d
  * requirements and domain as lfamd_rms_norm_quantize; at most 65408 rows. */
 int lfamd_swiglu_quantize(const float *d_gate, size_t gate_row_bytes, const float *d_up, size_t up_row_bytes, long nrows, long k,
                           int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes, void *stream);
+
+/* ---- the same two steps for the 32-block activation formats ---------------------------------------
+ * RMS-norm x weight, and silu(gate) * up, written as Q8_0 or Q8_1 rows (the vec_dot formats of Q8_0, Q4_0, Q5_0, IQ4_NL and of
+ * Q4_1, Q5_1 weights: the decode GEMVs behind then take Btype = Q8_0 / Q8_1 and quantise nothing) or as the staged image above
+ * (vec_dot_type = LFAMD_TYPE_STAGED_B32: no staging launch in front of the batch).  y is the value of lfamd_rms_norm_quantize /
+ * lfamd_swiglu_quantize bit for bit; the blocks are quantize_row_q8_0 / quantize_row_q8_1 of it, as lfamd_quantize_rows writes them:
+ * d = amax / 127, codes roundf(y / d) (halves away from zero; Q8_K rounds to even), d stored as f16, Q8_1's s = f16(sum * d).
+ * Requirements, checked before any launch (LFAMD_ERR_INVALID, nothing written) — those of the two producers above, except:
+ *   - k % 32 == 0 for rows (k = 96 or 4128 are legal); k % 256 == 0 for the image;
+ *   - Q8_0 rows (34-byte blocks) are 2-byte aligned with yq_row_bytes a multiple of 2, Q8_1 rows (36-byte blocks) 4-byte aligned
+ *     with yq_row_bytes a multiple of 4 — what lfamd_mul_mat asks of such rows; yq_row_bytes is at least k / 32 blocks, and the
+ *     bytes between rows are never written;
+ *   - the image (d_yq) is 16-byte aligned and lfamd_staged_b32_size(k, nrows) bytes long: all of it is written, the padding tokens
+ *     nrows .. roundup(nrows, 128) as zeros; yq_row_bytes is ignored;
+ *   - vec_dot_type is Q8_0, Q8_1 or LFAMD_TYPE_STAGED_B32 (Q8_K and the K-quant images: the two producers above); d_yq = NULL
+ *     writes f32 only, whatever vec_dot_type says.
+ * Asynchronous and graph-capturable; no workspace, no host read-back.
+ * Domain: lfamd_quantize_rows' own — finite inputs.  A block whose amax / 127 exceeds 65504 stores the f16 infinity as its d, as the
+ * reference quantiser does (Q8_1's s overflows earlier, from |y| of about 2047 on); a block whose largest |y| is non-zero and below
+ * about 4e-37 has no representation (1 / d overflows, in the reference as here). */
+int lfamd_rms_norm_quantize_b32(const float *d_x, size_t x_row_bytes, const float *d_weight, float eps, long nrows, long k,
+                                int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes, void *stream);
+int lfamd_swiglu_quantize_b32(const float *d_gate, size_t gate_row_bytes, const float *d_up, size_t up_row_bytes, long nrows, long k,
+                              int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes, void *stream);
 
 /* ---- F16 batched GEMM (attention KQ / KQV) ------------------------------------------------------
  * The interface of tinyblasGemmStridedBatchedEx / tinyblasGemmBatchedEx (llamafile/tinyblas.h:59-71, tinyblas.cu:652-857)

@@ -22,6 +22,7 @@ FLAG_GEMM_PLAIN = 32
 FLAG_Q80_EXACT = 64
 TYPE_STAGED_Q8K = 0x1000  # the int8 batch body's staged activation image (lfamd_hip.h)
 TYPE_STAGED_SCALED = 0x1001  # the scaled-operand f16 batch bodies' staged activation image
+TYPE_STAGED_B32 = 0x1002  # the 32-block batch bodies' staged activation image (Q8_0 / Q8_1-quantised activations)
 
 
 class LfamdError(RuntimeError):
@@ -54,6 +55,8 @@ _SIGS = {
     "lfamd_staged_q8k_size": (_sz, [_l, _l]),
     "lfamd_mul_mat_takes_staged_scaled": (_i, [_i, _l, _l, _l, _u]),
     "lfamd_staged_scaled_size": (_sz, [_l, _l]),
+    "lfamd_mul_mat_takes_staged_b32": (_i, [_i, _l, _l, _l, _u]),
+    "lfamd_staged_b32_size": (_sz, [_l, _l]),
     "lfamd_quantize_rows": (_i, [_i, _vp, _l, _l, _sz, _vp, _sz, _vp]),
     "lfamd_mul_mat_workspace": (_sz, [_i, _l, _l, _l]),
     "lfamd_mul_mat": (_i, [_i, _vp, _l, _l, _i, _vp, _sz, _l, _vp, _l, _vp, _sz, _u, _vp]),
@@ -65,6 +68,8 @@ _SIGS = {
     "lfamd_mul_mat_id_multi": (_i, [_i, _i, _vp, _l, _l, _i, _i, _vp, _sz, _i, _l, _vp, _i, _vp, _vp, _sz, _u, _vp]),
     "lfamd_rms_norm_quantize": (_i, [_vp, _sz, _vp, C.c_float, _l, _l, _i, _vp, _sz, _vp, _sz, _vp]),
     "lfamd_swiglu_quantize": (_i, [_vp, _sz, _vp, _sz, _l, _l, _i, _vp, _sz, _vp, _sz, _vp]),
+    "lfamd_rms_norm_quantize_b32": (_i, [_vp, _sz, _vp, C.c_float, _l, _l, _i, _vp, _sz, _vp, _sz, _vp]),
+    "lfamd_swiglu_quantize_b32": (_i, [_vp, _sz, _vp, _sz, _l, _l, _i, _vp, _sz, _vp, _sz, _vp]),
     "lfamd_gemm_strided_batched_f16": (_i, [_l, _l, _l, C.c_float, _vp, _l, C.c_longlong, _vp, _l, C.c_longlong, C.c_float, _vp, _i, _l,
                                             C.c_longlong, _i, _vp]),
     "lfamd_gemm_batched_f16": (_i, [_l, _l, _l, C.c_float, _vp, _l, _vp, _l, C.c_float, _vp, _i, _l, _i, _vp]),

@@ -313,7 +313,7 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
 
 // ---------------------------------------------------------------------------------------------
 // Dispatch.  plan_mul_mat answers, once per call, which body runs it; lfamd_mul_mat launches that body, and lfamd_mul_mat_is_exact,
-// _takes_staged, _takes_staged_scaled and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
+// _takes_staged, _takes_staged_scaled, _takes_staged_b32 and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
 // HIP call (lfamd_blaslt_ok() touches the device only when a host opted into the vendor library, LFAMD_USE_BLASLT=1).
 
 // Q4_0 / IQ4_NL rows that are whole 256-weight groups are kept in the P40 layout and served by the tuned kernels
@@ -516,6 +516,15 @@ int lfamd_mul_mat_takes_staged(int Atype, long m, long k, long n, unsigned flags
     return plan_mul_mat(Atype, m, k, n, flags).body == mm_body::i8 ? 1 : 0;
 }
 
+// Does a call accept the 32-block staged image a fused producer wrote (LFAMD_TYPE_STAGED_B32)?  The batches of the legacy 32-block
+// types on the 128 x 128 body: what lfamd_mul_mat would stage with prep80_kernel itself.
+int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned flags) {
+    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+        return 0;
+    const mm_body b = plan_mul_mat(Atype, m, k, n, flags).body;
+    return b == mm_body::q40_wide || b == mm_body::canon32 ? 1 : 0;
+}
+
 // The largest workspace of the bodies this call can run: the default one and any a testing flag can force.
 size_t lfamd_mul_mat_workspace(int Atype, long m, long k, long n) {
     if (!type_known(Atype))
@@ -552,6 +561,10 @@ static bool aligned16(const void *p) {
     return ((uintptr_t)p & 15) == 0;
 }
 
+static bool staged_type(int Btype) { // a staged activation image: no rows, no stride, staging of its own
+    return Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED || Btype == LFAMD_TYPE_STAGED_B32;
+}
+
 static bool workspace_short(size_t need, const void *d_ws, size_t ws_bytes) {
     return need && (ws_bytes < need || !d_ws);
 }
@@ -560,7 +573,7 @@ static bool workspace_short(size_t need, const void *d_ws, size_t ws_bytes) {
 // staged image brings its own staging, so those calls keep the sizes their routes check
 static size_t set_workspace(int count, const int *Atype, int type_stride, const long *m, long k, int Btype, long n) {
     size_t need = 0;
-    for (int j = 0; j < count && Btype != LFAMD_TYPE_STAGED_Q8K && Btype != LFAMD_TYPE_STAGED_SCALED; j++)
+    for (int j = 0; j < count && !staged_type(Btype); j++)
         if (m[j] > 0)
             need = std::max(need, lfamd_mul_mat_workspace(Atype[j * type_stride], m[j], k, n));
     return need;
@@ -572,7 +585,7 @@ static size_t set_workspace(int count, const int *Atype, int type_stride, const 
 // float4 by the staging kernels and the decode GEMVs).
 static int check_operands(const char *who, bool quantised, int Btype, const void *d_B, size_t b_row_bytes, int count, float *const *d_C,
                           const void *d_ws, size_t ws_bytes) {
-    if (Btype != LFAMD_TYPE_STAGED_Q8K && Btype != LFAMD_TYPE_STAGED_SCALED) {
+    if (!staged_type(Btype)) {
         const size_t a = Btype == LFAMD_TYPE_F32    ? (quantised ? 16 : 4)
                          : Btype == LFAMD_TYPE_Q8_K ? 4
                          : Btype == LFAMD_TYPE_Q8_1 ? 4
@@ -595,7 +608,7 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: unsupported weight type%s", "");
     if (m < 0 || n < 0 || k < 0 || ldc < m || k % lfamd_blck_size(Atype))
         return fail(LFAMD_ERR_INVALID, "mul_mat: bad shape%s", "");
-    const bool staged = Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED;
+    const bool staged = staged_type(Btype);
     if (!staged) {
         if (float_type(Atype)) {
             if (!(Btype == LFAMD_TYPE_F32 || Btype == Atype))
@@ -622,6 +635,12 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run a scaled-operand batch body (lfamd_mul_mat_takes_staged_scaled)%s", "");
         need = lfamd_gemm_lw_ksplit_bytes(m, n); // partial tiles of a K-split launch: the only workspace left
         uses_ws = need != 0;
+    } else if (Btype == LFAMD_TYPE_STAGED_B32) { // a fused producer wrote the 32-block bodies' staged image
+        if (p.body != mm_body::q40_wide && p.body != mm_body::canon32)
+            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run a 32-block batch body (lfamd_mul_mat_takes_staged_b32)%s", "");
+        if (!d_B || !aligned16(d_B))
+            return fail(LFAMD_ERR_INVALID, "mul_mat: the staged image must be 16-byte aligned%s", "");
+        uses_ws = false;
     }
     if (p.body == mm_body::refused)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: FORCE_GENERIC needs RAW-layout weights; this type is packed%s", "");
@@ -660,6 +679,14 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
     if (Btype == LFAMD_TYPE_STAGED_SCALED) {
         const uint8_t *img = (const uint8_t *)d_B;
         HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, img, img + im.d8T, img + im.Xm, n, (long)n_pad, d_C, ldc, plain | 2, d_ws, ws_bytes, s),
+               "gemm_wide (staged input)");
+        return LFAMD_OK;
+    }
+    if (Btype == LFAMD_TYPE_STAGED_B32) { // (q40_wide reads Xh and d8T, canon32 sT too under Q8_1 types)
+        const uint8_t *img = (const uint8_t *)d_B;
+        const lfamd_b32_image b32 = lfamd_b32_image_of(k, n);
+        const void *sT = p.body == mm_body::canon32 && vdt == LFAMD_TYPE_Q8_1 ? img + b32.sT : nullptr;
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, img, img + b32.d8T, sT, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s),
                "gemm_wide (staged input)");
         return LFAMD_OK;
     }
@@ -852,8 +879,10 @@ struct mm_group_plan {
 static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int Btype, size_t b_row_bytes, long n, const long *ldc,
                                 unsigned flags) {
     mm_group_plan g = {mm_route::each, count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags), 0, {}, {}};
-    if (count <= 0 || ((Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED) && n == 0))
+    if (count <= 0 || (staged_type(Btype) && n == 0))
         g.route = mm_route::none;
+    else if (Btype == LFAMD_TYPE_STAGED_B32) // one GEMM per matrix on the one image (check_group: every matrix must take it)
+        g.route = mm_route::each;
     else if (Btype == LFAMD_TYPE_STAGED_Q8K) // (check_group: every matrix must take the image, unless the group takes it together)
         g.route = mm_route::staged_i8;
     else if (Btype == LFAMD_TYPE_STAGED_SCALED) { // the route the same call takes on f32 rows
@@ -1051,6 +1080,8 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
         return LFAMD_OK;
     if (!Atype || !d_A || !m || !d_C || !ldc)
         return fail(LFAMD_ERR_INVALID, "mul_mat_multi_types: null argument%s", "");
+    if (Btype == LFAMD_TYPE_STAGED_B32)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: the 32-block staged image is taken by lfamd_mul_mat / lfamd_mul_mat_multi%s", "");
     const mm_group_plan p = plan_types(count, Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags);
     auto run_plan = [&](int j0, int j1) { return plan_group(Atype[j0], j1 - j0, m + j0, k, Btype, b_row_bytes, n, ldc + j0, flags); };
     if (p.route == mm_route::runs) { // every run is checked before the first one is launched
@@ -1154,6 +1185,8 @@ int lfamd_mul_mat_id_multi(int type, int count, const void *const *d_W, long row
     for (int j = 0; j < count; j++) // (the fused launch below goes straight into the kernel: a null stack or result would be a device fault)
         if (!d_W[j] || !d_result[j])
             return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: null expert stack or result%s", "");
+    if (Btype == LFAMD_TYPE_STAGED_B32)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_id_multi: no staged image is taken here%s", "");
     if (tasks <= 0 || tasks > thinkers || !type_known(Btype))
         return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: bad shape or activation type%s", "");
     if ((uintptr_t)d_plan % 4)

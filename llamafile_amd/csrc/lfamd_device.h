@@ -137,6 +137,15 @@ __device__ static inline uint16_t f2h_bits(float f) { // RNE, like F16C
     return __builtin_bit_cast(uint16_t, (_Float16)f);
 }
 
+// f16(a * b) with the product rounded to f32 first, as the scalar reference computes block_q8_1's s.  Left to itself the compiler
+// folds the multiply into the conversion (v_fma_mixlo_f16), which rounds the exact product once: about one value in 10^4 then lies
+// one f16 step from the reference's.  The empty asm keeps the f32 product a value of its own.
+__device__ static inline uint16_t f2h_bits_of_product(float a, float b) {
+    float p = a * b;
+    asm("" : "+v"(p));
+    return f2h_bits(p);
+}
+
 __device__ static inline int sdot4(uint32_t a, uint32_t b, int c) { // signed i8 x signed i8
     return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
 }

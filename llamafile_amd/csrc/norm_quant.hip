@@ -25,6 +25,37 @@ __device__ static inline double wave_sum_f64(double v) {
     return v;
 }
 
+// ---- the arithmetic of y, shared by every kernel of this unit (the Q8_K producers, the scaled ones, the 32-block ones): the same
+// instructions on the same inputs, so y has the same bits whichever format it is quantised to
+__device__ static inline double squares4(const float4 v) { // f32 products, f64 sum
+    return (double)(v.x * v.x) + (double)(v.y * v.y) + (double)(v.z * v.z) + (double)(v.w * v.w);
+}
+// the row's scale from each lane's partial sum of squares (one work-group of 4 waves per row; holds a barrier)
+__device__ static inline float rms_scale(double s, double *part, int wave, int lane, long k, float eps) {
+    s = wave_sum_f64(s);
+    if (lane == 0)
+        part[wave] = s;
+    __syncthreads();
+    const double sum = (part[0] + part[1]) + (part[2] + part[3]);
+    const float mean = (float)(sum / (double)k);
+    return 1.0f / sqrtf(mean + eps);
+}
+// y = (x * scale) * w for the four values of a lane; w: the lane's four weights, or NULL (= 1)
+__device__ static inline void norm_y(float (&y)[4], const float4 v, float scale, const float *w) {
+    y[0] = v.x * scale, y[1] = v.y * scale, y[2] = v.z * scale, y[3] = v.w * scale;
+    if (w) {
+        const float4 g = *(const float4 *)w;
+        y[0] *= g.x, y[1] *= g.y, y[2] *= g.z, y[3] *= g.w;
+    }
+}
+// y = silu(gate) * up
+__device__ static inline void swiglu_y(float (&y)[4], const float4 g, const float4 u) {
+    const float gv[4] = {g.x, g.y, g.z, g.w}, uv[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+        y[e] = (gv[e] / (1.0f + expf(-gv[e]))) * uv[e];
+}
+
 // quantize_row_q8_K on one 256-block held as four values per lane (element 4 lane + e), written in the reference's block
 // format {d, bsums[16], qs[256]} (cf. gemv_impl.h stage_f32_q8k_wave: same arithmetic)
 __device__ static inline void put_q8k_block(uint8_t *blk, const float (&y)[4], int lane) {
@@ -193,25 +224,14 @@ __global__ __launch_bounds__(256) void rms_norm_q8k_kernel(const float *__restri
     const float *xr = (const float *)((const uint8_t *)x + row * x_row_bytes);
     const int nb = (int)(k / 256);
     double s = 0.0;
-    for (int b = wave; b < nb; b += 4) {
-        const float4 v = *(const float4 *)(xr + (size_t)b * 256 + 4 * lane);
-        s += (double)(v.x * v.x) + (double)(v.y * v.y) + (double)(v.z * v.z) + (double)(v.w * v.w);
-    }
-    s = wave_sum_f64(s);
-    if (lane == 0)
-        part[wave] = s;
-    __syncthreads();
-    const double sum = (part[0] + part[1]) + (part[2] + part[3]);
-    const float mean = (float)(sum / (double)k);
-    const float scale = 1.0f / sqrtf(mean + eps);
+    for (int b = wave; b < nb; b += 4)
+        s += squares4(*(const float4 *)(xr + (size_t)b * 256 + 4 * lane));
+    const float scale = rms_scale(s, part, wave, lane, k, eps);
     uint8_t *qrow = yq ? yq + row * yq_row_bytes : nullptr;
     float *frow = yf ? (float *)((uint8_t *)yf + row * yf_row_bytes) : nullptr;
     for (int b = wave; b < nb; b += 4) {
-        const float4 v = *(const float4 *)(xr + (size_t)b * 256 + 4 * lane); // (second read: L1 / L2)
-        const float4 g = w ? *(const float4 *)(w + (size_t)b * 256 + 4 * lane) : make_float4(1.f, 1.f, 1.f, 1.f);
-        float y[4] = {v.x * scale, v.y * scale, v.z * scale, v.w * scale};
-        if (w)
-            y[0] *= g.x, y[1] *= g.y, y[2] *= g.z, y[3] *= g.w;
+        float y[4];
+        norm_y(y, *(const float4 *)(xr + (size_t)b * 256 + 4 * lane), scale, w ? w + (size_t)b * 256 + 4 * lane : nullptr); // (second read: L1 / L2)
         if (frow)
             *(float4 *)(frow + (size_t)b * 256 + 4 * lane) = make_float4(y[0], y[1], y[2], y[3]);
         if constexpr (STAGED) {
@@ -241,11 +261,8 @@ __global__ __launch_bounds__(256) void swiglu_q8k_kernel(const float *__restrict
     }
     const float4 g = *(const float4 *)((const float *)((const uint8_t *)gate + row * gate_row_bytes) + (size_t)b * 256 + 4 * lane);
     const float4 u = *(const float4 *)((const float *)((const uint8_t *)up + row * up_row_bytes) + (size_t)b * 256 + 4 * lane);
-    const float gv[4] = {g.x, g.y, g.z, g.w}, uv[4] = {u.x, u.y, u.z, u.w};
     float y[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++)
-        y[e] = (gv[e] / (1.0f + expf(-gv[e]))) * uv[e];
+    swiglu_y(y, g, u);
     if (yf)
         *(float4 *)((float *)((uint8_t *)yf + row * yf_row_bytes) + (size_t)b * 256 + 4 * lane) = make_float4(y[0], y[1], y[2], y[3]);
     if constexpr (STAGED)
@@ -273,24 +290,11 @@ __global__ __launch_bounds__(256) void rms_norm_scaled_kernel(const float *__res
     }
     const float *xr = (const float *)((const uint8_t *)x + row * x_row_bytes);
     double s = 0.0;
-    for (int b = wave; b < nb; b += 4) {
-        const float4 v = *(const float4 *)(xr + (size_t)b * 256 + 4 * lane);
-        s += (double)(v.x * v.x) + (double)(v.y * v.y) + (double)(v.z * v.z) + (double)(v.w * v.w);
-    }
-    s = wave_sum_f64(s);
-    if (lane == 0)
-        part[wave] = s;
-    __syncthreads();
-    const double sum = (part[0] + part[1]) + (part[2] + part[3]);
-    const float mean = (float)(sum / (double)k);
-    const float scale = 1.0f / sqrtf(mean + eps);
+    for (int b = wave; b < nb; b += 4)
+        s += squares4(*(const float4 *)(xr + (size_t)b * 256 + 4 * lane));
+    const float scale = rms_scale(s, part, wave, lane, k, eps);
     auto y_of = [&](int b, float (&y)[4]) {
-        const float4 v = *(const float4 *)(xr + (size_t)b * 256 + 4 * lane);
-        y[0] = v.x * scale, y[1] = v.y * scale, y[2] = v.z * scale, y[3] = v.w * scale;
-        if (w) {
-            const float4 g = *(const float4 *)(w + (size_t)b * 256 + 4 * lane);
-            y[0] *= g.x, y[1] *= g.y, y[2] *= g.z, y[3] *= g.w;
-        }
+        norm_y(y, *(const float4 *)(xr + (size_t)b * 256 + 4 * lane), scale, w ? w + (size_t)b * 256 + 4 * lane : nullptr);
     };
     float dmax = 0.0f;
     for (int b = wave; b < nb; b += 4) {
@@ -327,12 +331,7 @@ __global__ __launch_bounds__(256) void swiglu_scaled_kernel(const float *__restr
     }
     const float *gr = (const float *)((const uint8_t *)gate + row * gate_row_bytes), *ur = (const float *)((const uint8_t *)up + row * up_row_bytes);
     auto y_of = [&](int b, float (&y)[4]) {
-        const float4 g = *(const float4 *)(gr + (size_t)b * 256 + 4 * lane);
-        const float4 u = *(const float4 *)(ur + (size_t)b * 256 + 4 * lane);
-        const float gv[4] = {g.x, g.y, g.z, g.w}, uv[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-            y[e] = (gv[e] / (1.0f + expf(-gv[e]))) * uv[e];
+        swiglu_y(y, *(const float4 *)(gr + (size_t)b * 256 + 4 * lane), *(const float4 *)(ur + (size_t)b * 256 + 4 * lane));
     };
     float dmax = 0.0f;
     for (int b = wave; b < nb; b += 4) {
@@ -349,6 +348,153 @@ __global__ __launch_bounds__(256) void swiglu_scaled_kernel(const float *__restr
             *(float4 *)(frow + (size_t)b * 256 + 4 * lane) = make_float4(y[0], y[1], y[2], y[3]);
         put_scaled_block(im, b, row, y, nscale, lane);
     }
+}
+
+// ---- the 32-block formats: Q8_0 / Q8_1 rows, what the decode GEMVs of the legacy types and of Q8_0 read, and
+// the staged image of the 32-block batch bodies (lfamd_b32_image_of; what prep80_kernel<true, true> of pack.hip writes).
+// quantize_row_q8_0 / quantize_row_q8_1 as csrc/quantize.hip has them: d = amax / 127, id = d ? 1 / d : 0, codes roundf(v * id)
+// (half away from zero — Q8_K's are nearest-even), d stored as f16, s = f16(sum * d) with d not yet rounded.
+// A 256-chunk is four values per lane, so 32-block j of the chunk is lanes 8 j .. 8 j + 7: maximum and code sum are reduced over
+// those eight lanes in three DPP steps.  Rows need only k % 32 == 0: the lanes of the last chunk that lie past k hold zeros, load
+// and store nothing, and — eight lanes being one whole block — never share a reduction with a block of the row.
+enum { B32_Q8_0, B32_Q8_1, B32_IMAGE };
+struct b32_image {
+    _Float16 *Xh;
+    float *d8T, *sT;
+    long n_pad;
+};
+template <int CTRL>
+__device__ static inline float max_dpp(float v) {
+    return fmaxf(v, dpp_f32<CTRL>(v));
+}
+__device__ static inline void quantize_b32(const float (&y)[4], int (&q)[4], float &d, int &sum) {
+    float amax = fmaxf(fmaxf(fabsf(y[0]), fabsf(y[1])), fmaxf(fabsf(y[2]), fabsf(y[3])));
+    amax = max_dpp<DPP_HALF_MIRROR>(max_dpp<DPP_XOR2>(max_dpp<DPP_XOR1>(amax)));
+    d = amax / 127.0f;
+    const float id = d != 0.0f ? 1.0f / d : 0.0f;
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+        q[e] = (int)roundf(y[e] * id);
+    sum = q[0] + q[1] + q[2] + q[3];
+    sum += (int)dpp_u32<DPP_XOR1>((uint32_t)sum);
+    sum += (int)dpp_u32<DPP_XOR2>((uint32_t)sum);
+    sum += (int)dpp_u32<DPP_HALF_MIRROR>((uint32_t)sum);
+}
+// chunk: the row's blocks 8 b .. 8 b + 7.  Q8_1 blocks (36 bytes) keep their code words 4-byte aligned; Q8_0 blocks (34 bytes) only
+// 2-byte aligned, so a lane's four codes go out as two 16-bit stores.  `valid` is false for the lanes past the end of the row.
+template <bool Q81>
+__device__ static inline void put_b32_rows(uint8_t *chunk, const float (&y)[4], int lane, bool valid) {
+    int q[4], sum;
+    float d;
+    quantize_b32(y, q, d, sum);
+    if (!valid)
+        return;
+    const uint32_t codes = (uint32_t)(q[0] & 0xff) | ((uint32_t)(q[1] & 0xff) << 8) | ((uint32_t)(q[2] & 0xff) << 16) | ((uint32_t)(q[3] & 0xff) << 24);
+    uint8_t *blk = chunk + (lane >> 3) * (Q81 ? 36 : 34);
+    if constexpr (Q81) {
+        *(uint32_t *)(blk + 4 + 4 * (lane & 7)) = codes;
+        if ((lane & 7) == 0)
+            *(uint32_t *)blk = (uint32_t)f2h_bits(d) | ((uint32_t)f2h_bits_of_product((float)sum, d) << 16);
+    } else {
+        uint16_t *p = (uint16_t *)(blk + 2 + 4 * (lane & 7));
+        p[0] = (uint16_t)codes;
+        p[1] = (uint16_t)(codes >> 16);
+        if ((lane & 7) == 0)
+            *(uint16_t *)blk = f2h_bits(d);
+    }
+}
+__device__ static inline void put_b32_image(const b32_image &im, int b, long tok, const float (&y)[4], int lane) {
+    typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+    int q[4], sum;
+    float d;
+    quantize_b32(y, q, d, sum);
+    const half4_t h4 = {(_Float16)q[0], (_Float16)q[1], (_Float16)q[2], (_Float16)q[3]};
+    *(half4_t *)(im.Xh + ((size_t)b * im.n_pad + tok) * 256 + 4 * lane) = h4;
+    if ((lane & 7) == 0) {
+        const size_t o = ((size_t)b * 8 + (lane >> 3)) * im.n_pad + tok;
+        im.d8T[o] = h2f(f2h_bits(d));
+        im.sT[o] = h2f(f2h_bits_of_product((float)sum, d));
+    }
+}
+__device__ static inline void put_b32_zero(const b32_image &im, int b, long tok, int lane) { // a padding token of the image
+    *(uint2 *)(im.Xh + ((size_t)b * im.n_pad + tok) * 256 + 4 * lane) = make_uint2(0u, 0u);
+    if ((lane & 7) == 0) {
+        const size_t o = ((size_t)b * 8 + (lane >> 3)) * im.n_pad + tok;
+        im.d8T[o] = 0.0f;
+        im.sT[o] = 0.0f;
+    }
+}
+
+// one work-group (4 waves) per row like rms_norm_q8k_kernel; wave w owns the 256-chunks w, w + 4, ..., the last one maybe partial
+template <int FMT>
+__global__ __launch_bounds__(256) void rms_norm_b32_kernel(const float *__restrict__ x, size_t x_row_bytes, const float *__restrict__ w,
+                                                           float eps, long k, uint8_t *__restrict__ yq, size_t yq_row_bytes,
+                                                           float *__restrict__ yf, size_t yf_row_bytes, long nrows, b32_image im) {
+    __shared__ double part[4];
+    const long row = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nc = (int)((k + 255) / 256);
+    if (FMT == B32_IMAGE && row >= nrows) { // (uniform) the image's padding tokens
+        for (int b = wave; b < nc; b += 4)
+            put_b32_zero(im, b, row, lane);
+        return;
+    }
+    const float *xr = (const float *)((const uint8_t *)x + row * x_row_bytes);
+    double s = 0.0;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        if (at < k)
+            s += squares4(*(const float4 *)(xr + at));
+    }
+    const float scale = rms_scale(s, part, wave, lane, k, eps);
+    uint8_t *qrow = yq ? yq + row * yq_row_bytes : nullptr;
+    float *frow = yf ? (float *)((uint8_t *)yf + row * yf_row_bytes) : nullptr;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        const bool valid = at < k;
+        float y[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (valid) {
+            norm_y(y, *(const float4 *)(xr + at), scale, w ? w + at : nullptr); // (second read: L1 / L2)
+            if (frow)
+                *(float4 *)(frow + at) = make_float4(y[0], y[1], y[2], y[3]);
+        }
+        if constexpr (FMT == B32_IMAGE) {
+            put_b32_image(im, b, row, y, lane); // (k % 256 == 0: every lane is valid)
+        } else {
+            if (!qrow) // (uniform)
+                continue;
+            put_b32_rows<FMT == B32_Q8_1>(qrow + (size_t)b * 8 * (FMT == B32_Q8_1 ? 36 : 34), y, lane, valid);
+        }
+    }
+}
+
+// one wave per 256-chunk like swiglu_q8k_kernel
+template <int FMT>
+__global__ __launch_bounds__(256) void swiglu_b32_kernel(const float *__restrict__ gate, size_t gate_row_bytes, const float *__restrict__ up,
+                                                         size_t up_row_bytes, long k, uint8_t *__restrict__ yq, size_t yq_row_bytes,
+                                                         float *__restrict__ yf, size_t yf_row_bytes, long nrows, b32_image im) {
+    const long row = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= (int)((k + 255) / 256))
+        return;
+    if (FMT == B32_IMAGE && row >= nrows) { // (uniform) the image's padding tokens
+        put_b32_zero(im, b, row, lane);
+        return;
+    }
+    const long at = (long)b * 256 + 4 * lane;
+    const bool valid = at < k;
+    float y[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (valid) {
+        swiglu_y(y, *(const float4 *)((const float *)((const uint8_t *)gate + row * gate_row_bytes) + at),
+                 *(const float4 *)((const float *)((const uint8_t *)up + row * up_row_bytes) + at));
+        if (yf)
+            *(float4 *)((float *)((uint8_t *)yf + row * yf_row_bytes) + at) = make_float4(y[0], y[1], y[2], y[3]);
+    }
+    if constexpr (FMT == B32_IMAGE)
+        put_b32_image(im, b, row, y, lane);
+    else if (yq)
+        put_b32_rows<FMT == B32_Q8_1>(yq + row * yq_row_bytes + (size_t)b * 8 * (FMT == B32_Q8_1 ? 36 : 34), y, lane, valid);
 }
 
 } // namespace
@@ -441,4 +587,91 @@ extern "C" int lfamd_swiglu_quantize(const float *d_gate, size_t gate_row_bytes,
         return LFAMD_ERR_HIP;
     }
     return LFAMD_OK;
+}
+
+// ---- the 32-block formats: Q8_0 / Q8_1 rows and LFAMD_TYPE_STAGED_B32 (entry points of their own: the two above keep refusing them)
+static b32_image b32_of(void *image, long k, long nrows) {
+    const lfamd_b32_image l = lfamd_b32_image_of(k, nrows);
+    uint8_t *p = (uint8_t *)image;
+    return {(_Float16 *)p, (float *)(p + l.d8T), (float *)(p + l.sT), (long)l.n_pad};
+}
+
+extern "C" size_t lfamd_staged_b32_size(long k, long nrows) { // = lfamd_mul_mat_workspace of a canon32 call
+    return k <= 0 || k % 256 || nrows < 0 ? 0 : lfamd_b32_image_of(k, nrows).bytes;
+}
+
+// what both 32-block producers ask of their output arguments (the f32 operands: each entry point's own line)
+static bool b32_output_ok(long nrows, long k, int vec_dot_type, const void *d_yq, size_t yq_row_bytes, const float *d_yf, size_t yf_row_bytes) {
+    if (nrows < 0 || k <= 0 || k % 32 || (!d_yq && !d_yf) || ((uintptr_t)d_yf & 15) || (yf_row_bytes & 15))
+        return false;
+    if (!d_yq)
+        return true;
+    if (vec_dot_type == LFAMD_TYPE_STAGED_B32)
+        return k % 256 == 0 && ((uintptr_t)d_yq & 15) == 0;
+    if (vec_dot_type != LFAMD_TYPE_Q8_0 && vec_dot_type != LFAMD_TYPE_Q8_1)
+        return false;
+    const size_t a = vec_dot_type == LFAMD_TYPE_Q8_1 ? 3 : 1, row = (size_t)(k / 32) * (vec_dot_type == LFAMD_TYPE_Q8_1 ? 36 : 34);
+    return ((uintptr_t)d_yq & a) == 0 && (yq_row_bytes & a) == 0 && yq_row_bytes >= row;
+}
+
+static int b32_launched(void) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        lfamd_set_error(hipGetErrorString(e));
+        return LFAMD_ERR_HIP;
+    }
+    return LFAMD_OK;
+}
+
+extern "C" int lfamd_rms_norm_quantize_b32(const float *d_x, size_t x_row_bytes, const float *d_weight, float eps, long nrows, long k,
+                                           int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes,
+                                           void *stream) {
+    if (!b32_output_ok(nrows, k, vec_dot_type, d_yq, yq_row_bytes, d_yf, yf_row_bytes) || !d_x || ((uintptr_t)d_x & 15) || (x_row_bytes & 15) ||
+        ((uintptr_t)d_weight & 15)) {
+        lfamd_set_error("lfamd_rms_norm_quantize_b32: k must be a multiple of 32 (the staged image: of 256, 16-byte aligned), output format "
+                        "Q8_0 / Q8_1 rows (2- / 4-byte aligned, stride at least the row) or LFAMD_TYPE_STAGED_B32, 16-byte aligned f32 rows");
+        return LFAMD_ERR_INVALID;
+    }
+    if (nrows == 0)
+        return LFAMD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_B32) {
+        const b32_image im = b32_of(d_yq, k, nrows);
+        rms_norm_b32_kernel<B32_IMAGE><<<(unsigned)im.n_pad, 256, 0, s>>>(d_x, x_row_bytes, d_weight, eps, k, nullptr, 0, d_yf, yf_row_bytes, nrows, im);
+    } else if (d_yq && vec_dot_type == LFAMD_TYPE_Q8_1) {
+        rms_norm_b32_kernel<B32_Q8_1><<<(unsigned)nrows, 256, 0, s>>>(d_x, x_row_bytes, d_weight, eps, k, (uint8_t *)d_yq, yq_row_bytes, d_yf,
+                                                                      yf_row_bytes, nrows, b32_image{});
+    } else { // (Q8_0 rows, or f32 alone)
+        rms_norm_b32_kernel<B32_Q8_0><<<(unsigned)nrows, 256, 0, s>>>(d_x, x_row_bytes, d_weight, eps, k, (uint8_t *)d_yq, yq_row_bytes, d_yf,
+                                                                      yf_row_bytes, nrows, b32_image{});
+    }
+    return b32_launched();
+}
+
+extern "C" int lfamd_swiglu_quantize_b32(const float *d_gate, size_t gate_row_bytes, const float *d_up, size_t up_row_bytes, long nrows,
+                                         long k, int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes,
+                                         void *stream) {
+    if (!b32_output_ok(nrows, k, vec_dot_type, d_yq, yq_row_bytes, d_yf, yf_row_bytes) || !d_gate || !d_up || ((uintptr_t)d_gate & 15) ||
+        (gate_row_bytes & 15) || ((uintptr_t)d_up & 15) || (up_row_bytes & 15) || nrows > 65535 - 127) {
+        lfamd_set_error("lfamd_swiglu_quantize_b32: k must be a multiple of 32 (the staged image: of 256, 16-byte aligned), output format "
+                        "Q8_0 / Q8_1 rows (2- / 4-byte aligned, stride at least the row) or LFAMD_TYPE_STAGED_B32, 16-byte aligned f32 rows, "
+                        "<= 65408 rows");
+        return LFAMD_ERR_INVALID;
+    }
+    if (nrows == 0)
+        return LFAMD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned gx = (unsigned)(((k + 255) / 256 + 3) / 4);
+    if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_B32) {
+        const b32_image im = b32_of(d_yq, k, nrows);
+        swiglu_b32_kernel<B32_IMAGE><<<dim3(gx, (unsigned)im.n_pad), 256, 0, s>>>(d_gate, gate_row_bytes, d_up, up_row_bytes, k, nullptr, 0, d_yf,
+                                                                                 yf_row_bytes, nrows, im);
+    } else if (d_yq && vec_dot_type == LFAMD_TYPE_Q8_1) {
+        swiglu_b32_kernel<B32_Q8_1><<<dim3(gx, (unsigned)nrows), 256, 0, s>>>(d_gate, gate_row_bytes, d_up, up_row_bytes, k, (uint8_t *)d_yq,
+                                                                             yq_row_bytes, d_yf, yf_row_bytes, nrows, b32_image{});
+    } else { // (Q8_0 rows, or f32 alone)
+        swiglu_b32_kernel<B32_Q8_0><<<dim3(gx, (unsigned)nrows), 256, 0, s>>>(d_gate, gate_row_bytes, d_up, up_row_bytes, k, (uint8_t *)d_yq,
+                                                                             yq_row_bytes, d_yf, yf_row_bytes, nrows, b32_image{});
+    }
+    return b32_launched();
 }

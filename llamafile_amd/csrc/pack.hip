@@ -623,7 +623,7 @@ __global__ __launch_bounds__(256) void prep80_kernel(const uint8_t *__restrict__
                 sum += __shfl_xor(sum, 1, 64);
                 sum += __shfl_xor(sum, 2, 64);
                 sum += __shfl_xor(sum, 4, 64);
-                sv = h2f(f2h_bits((float)sum * dd));
+                sv = h2f(f2h_bits_of_product((float)sum, dd));
             }
         } else {
             constexpr int BSZ = Q81 ? 36 : 34, QOFF = Q81 ? 4 : 2;
