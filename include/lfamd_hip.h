@@ -299,6 +299,25 @@ int lfamd_mul_mat_takes_staged_scaled(int Atype, long m, long k, long n, unsigne
 #define LFAMD_TYPE_STAGED_B32 0x1002
 size_t lfamd_staged_b32_size(long k, long nrows);
 int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned flags);
+/* The same for Q8_0 WEIGHT batches on the f16 loader-wave body (rows of whole 128-weight quads; lfamd_mul_mat and, for 2 .. 4 sibling
+ * matrices in one launch, lfamd_mul_mat_multi): LFAMD_TYPE_STAGED_Q80, a buffer of lfamd_staged_q80_size(k, nrows) = n_pad * k * 2 +
+ * n_pad * 8 bytes written by the two _b32 producers below, n_pad = roundup(nrows, 128), packed without padding:
+ *     Xh        f16 [k / 128][n_pad][128]  per token and 128-weight quad 256 bytes: f16(f32(f16(d)) * stage * code) of quantize_row_q8_0
+ *                                          (the f32 product is exact, so it is rounded once); block blk of the quad, elements 4 j .. 4 j + 3,
+ *                                          at byte (2 s + (j >> 2)) * 16 + (blk & 1) * 8, s = 2 (j & 3) + (blk >> 1)
+ *     stage     f32 [n_pad]                2^(9 - ilogb(D)), D = f32(f16(max |y| of the row / 127)) * 127
+ *     tok_scale f32 [n_pad]                2^(ilogb(D) - 9): the store multiplies the token's column by it
+ * A row whose D is zero or not finite has 1 in both; the padding tokens nrows .. n_pad hold zero operands and 1 in both.  k % 128 == 0.
+ * It is the layout lfamd_mul_mat stages per call for this body (two launches in front of every GEMM), so the call on the image runs
+ * the GEMM alone, touches no workspace (d_workspace = NULL is legal) and gives the bits of the same call on the producer's f32 output.
+ * lfamd_mul_mat_takes_staged_q80() says whether a call accepts it: Q8_0 weights, n > 8, k % 128 == 0, a packed matrix below 4 GiB,
+ * without LFAMD_FLAG_PRECISE, LFAMD_FLAG_Q80_EXACT or LFAMD_FLAG_FORCE_GENERIC, in a process that did not opt into the vendor GEMM; it
+ * makes no device call.  lfamd_mul_mat_multi takes it when every matrix of the call does.  Other calls answer LFAMD_ERR_UNSUPPORTED for
+ * it (lfamd_mul_mat_multi_types, lfamd_mul_mat_id and lfamd_mul_mat_id_multi always do); a NULL image or one not 16-byte aligned is
+ * LFAMD_ERR_INVALID.  The bit-exact Q8_0 body and the F16 / BF16 bodies take no image. */
+#define LFAMD_TYPE_STAGED_Q80 0x1003
+size_t lfamd_staged_q80_size(long k, long nrows);
+int lfamd_mul_mat_takes_staged_q80(int Atype, long m, long k, long n, unsigned flags);
 
 /* ---- the step in front of the path, fused: RMS-norm x weight -> Q8_K -----------------------------
  * y[i] = (x[i] * 1/sqrtf(mean(x^2) + eps)) * weight[i] per row (ggml_compute_forward_rms_norm_f32 + the MUL node; GPU
@@ -335,23 +354,26 @@ int lfamd_swiglu_quantize(const float *d_gate, size_t gate_row_bytes, const floa
 
 /* ---- the same two steps for the 32-block activation formats ---------------------------------------
  * RMS-norm x weight, and silu(gate) * up, written as Q8_0 or Q8_1 rows (the vec_dot formats of Q8_0, Q4_0, Q5_0, IQ4_NL and of
- * Q4_1, Q5_1 weights: the decode GEMVs behind then take Btype = Q8_0 / Q8_1 and quantise nothing) or as the staged image above
- * (vec_dot_type = LFAMD_TYPE_STAGED_B32: no staging launch in front of the batch).  y is the value of lfamd_rms_norm_quantize /
+ * Q4_1, Q5_1 weights: the decode GEMVs behind then take Btype = Q8_0 / Q8_1 and quantise nothing) or as one of the two staged images
+ * above (vec_dot_type = LFAMD_TYPE_STAGED_B32 for batches of the legacy 4- / 5-bit weights, LFAMD_TYPE_STAGED_Q80 for batches of Q8_0
+ * weights: no staging launch in front of the batch).  y is the value of lfamd_rms_norm_quantize /
  * lfamd_swiglu_quantize bit for bit; the blocks are quantize_row_q8_0 / quantize_row_q8_1 of it, as lfamd_quantize_rows writes them:
  * d = amax / 127, codes roundf(y / d) (halves away from zero; Q8_K rounds to even), d stored as f16, Q8_1's s = f16(sum * d).
  * Requirements, checked before any launch (LFAMD_ERR_INVALID, nothing written) — those of the two producers above, except:
- *   - k % 32 == 0 for rows (k = 96 or 4128 are legal); k % 256 == 0 for the image;
+ *   - k % 32 == 0 for rows (k = 96 or 4128 are legal); k % 256 == 0 for the B32 image, k % 128 == 0 for the Q80 image;
  *   - Q8_0 rows (34-byte blocks) are 2-byte aligned with yq_row_bytes a multiple of 2, Q8_1 rows (36-byte blocks) 4-byte aligned
  *     with yq_row_bytes a multiple of 4 — what lfamd_mul_mat asks of such rows; yq_row_bytes is at least k / 32 blocks, and the
  *     bytes between rows are never written;
- *   - the image (d_yq) is 16-byte aligned and lfamd_staged_b32_size(k, nrows) bytes long: all of it is written, the padding tokens
- *     nrows .. roundup(nrows, 128) as zeros; yq_row_bytes is ignored;
- *   - vec_dot_type is Q8_0, Q8_1 or LFAMD_TYPE_STAGED_B32 (Q8_K and the K-quant images: the two producers above); d_yq = NULL
+ *   - the image (d_yq) is 16-byte aligned, not NULL and lfamd_staged_b32_size / lfamd_staged_q80_size(k, nrows) bytes long: all of
+ *     it is written, the padding tokens nrows .. roundup(nrows, 128) as zeros (the Q80 image: with 1 in stage and tok_scale);
+ *     yq_row_bytes is ignored;
+ *   - vec_dot_type is Q8_0, Q8_1, LFAMD_TYPE_STAGED_B32 or LFAMD_TYPE_STAGED_Q80 (Q8_K and the K-quant images: the two producers above); d_yq = NULL
  *     writes f32 only, whatever vec_dot_type says.
  * Asynchronous and graph-capturable; no workspace, no host read-back.
  * Domain: lfamd_quantize_rows' own — finite inputs.  A block whose amax / 127 exceeds 65504 stores the f16 infinity as its d, as the
  * reference quantiser does (Q8_1's s overflows earlier, from |y| of about 2047 on); a block whose largest |y| is non-zero and below
- * about 4e-37 has no representation (1 / d overflows, in the reference as here). */
+ * about 4e-37 has no representation (1 / d overflows, in the reference as here).  The Q80 image holds the products f16(d) * code:
+ * a block with an infinite d puts inf / NaN into it, as the in-call staging of lfamd_mul_mat does on such a row. */
 int lfamd_rms_norm_quantize_b32(const float *d_x, size_t x_row_bytes, const float *d_weight, float eps, long nrows, long k,
                                 int vec_dot_type, void *d_yq, size_t yq_row_bytes, float *d_yf, size_t yf_row_bytes, void *stream);
 int lfamd_swiglu_quantize_b32(const float *d_gate, size_t gate_row_bytes, const float *d_up, size_t up_row_bytes, long nrows, long k,

@@ -23,6 +23,7 @@ FLAG_Q80_EXACT = 64
 TYPE_STAGED_Q8K = 0x1000  # the int8 batch body's staged activation image (lfamd_hip.h)
 TYPE_STAGED_SCALED = 0x1001  # the scaled-operand f16 batch bodies' staged activation image
 TYPE_STAGED_B32 = 0x1002  # the 32-block batch bodies' staged activation image (Q8_0 / Q8_1-quantised activations)
+TYPE_STAGED_Q80 = 0x1003  # the Q8_0-weight loader-wave batch body's staged activation image
 
 
 class LfamdError(RuntimeError):
@@ -57,6 +58,8 @@ _SIGS = {
     "lfamd_staged_scaled_size": (_sz, [_l, _l]),
     "lfamd_mul_mat_takes_staged_b32": (_i, [_i, _l, _l, _l, _u]),
     "lfamd_staged_b32_size": (_sz, [_l, _l]),
+    "lfamd_mul_mat_takes_staged_q80": (_i, [_i, _l, _l, _l, _u]),
+    "lfamd_staged_q80_size": (_sz, [_l, _l]),
     "lfamd_quantize_rows": (_i, [_i, _vp, _l, _l, _sz, _vp, _sz, _vp]),
     "lfamd_mul_mat_workspace": (_sz, [_i, _l, _l, _l]),
     "lfamd_mul_mat": (_i, [_i, _vp, _l, _l, _i, _vp, _sz, _l, _vp, _l, _vp, _sz, _u, _vp]),

@@ -313,7 +313,7 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
 
 // ---------------------------------------------------------------------------------------------
 // Dispatch.  plan_mul_mat answers, once per call, which body runs it; lfamd_mul_mat launches that body, and lfamd_mul_mat_is_exact,
-// _takes_staged, _takes_staged_scaled, _takes_staged_b32 and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
+// _takes_staged, _takes_staged_scaled, _takes_staged_b32, _takes_staged_q80 and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
 // HIP call (lfamd_blaslt_ok() touches the device only when a host opted into the vendor library, LFAMD_USE_BLASLT=1).
 
 // Q4_0 / IQ4_NL rows that are whole 256-weight groups are kept in the P40 layout and served by the tuned kernels
@@ -525,6 +525,14 @@ int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned f
     return b == mm_body::q40_wide || b == mm_body::canon32 ? 1 : 0;
 }
 
+// Does a call accept the image of the Q8_0-weight loader-wave body a fused producer wrote (LFAMD_TYPE_STAGED_Q80)?  The Q8_0 batches
+// on gemm_lf_q80 (what lfamd_mul_mat would stage with lf_tok_scale_kernel and prep_lf_kernel itself) whose P80 image the loaders can address.
+int lfamd_mul_mat_takes_staged_q80(int Atype, long m, long k, long n, unsigned flags) {
+    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+        return 0;
+    return plan_mul_mat(Atype, m, k, n, flags).body == mm_body::q80_lf && lfamd_gemm_lf_q80_fits(m, k) ? 1 : 0;
+}
+
 // The largest workspace of the bodies this call can run: the default one and any a testing flag can force.
 size_t lfamd_mul_mat_workspace(int Atype, long m, long k, long n) {
     if (!type_known(Atype))
@@ -562,7 +570,7 @@ static bool aligned16(const void *p) {
 }
 
 static bool staged_type(int Btype) { // a staged activation image: no rows, no stride, staging of its own
-    return Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED || Btype == LFAMD_TYPE_STAGED_B32;
+    return Btype == LFAMD_TYPE_STAGED_Q8K || Btype == LFAMD_TYPE_STAGED_SCALED || Btype == LFAMD_TYPE_STAGED_B32 || Btype == LFAMD_TYPE_STAGED_Q80;
 }
 
 static bool workspace_short(size_t need, const void *d_ws, size_t ws_bytes) {
@@ -641,6 +649,12 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
         if (!d_B || !aligned16(d_B))
             return fail(LFAMD_ERR_INVALID, "mul_mat: the staged image must be 16-byte aligned%s", "");
         uses_ws = false;
+    } else if (Btype == LFAMD_TYPE_STAGED_Q80) { // a fused producer wrote the Q8_0-weight loader-wave body's image
+        if (!lfamd_mul_mat_takes_staged_q80(Atype, m, k, n, flags))
+            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run the Q8_0 loader-wave batch body (lfamd_mul_mat_takes_staged_q80)%s", "");
+        if (!d_B || !aligned16(d_B))
+            return fail(LFAMD_ERR_INVALID, "mul_mat: the staged image must be 16-byte aligned%s", "");
+        uses_ws = false;
     }
     if (p.body == mm_body::refused)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: FORCE_GENERIC needs RAW-layout weights; this type is packed%s", "");
@@ -688,6 +702,10 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
         const void *sT = p.body == mm_body::canon32 && vdt == LFAMD_TYPE_Q8_1 ? img + b32.sT : nullptr;
         HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, img, img + b32.d8T, sT, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s),
                "gemm_wide (staged input)");
+        return LFAMD_OK;
+    }
+    if (Btype == LFAMD_TYPE_STAGED_Q80) { // the GEMM alone on the image's parts
+        HIPCHK(lfamd_launch_gemm_lf_q80_staged(1, &d_A, &m, k, d_B, n, &d_C, &ldc, s), "gemm_lf (Q8_0, staged input)");
         return LFAMD_OK;
     }
     switch (p.body) {
@@ -826,6 +844,7 @@ enum class mm_route {
     i8_multi,     // the int8 body over the concatenated row blocks
     wide_multi,   // one staging, the wide body over the concatenated row blocks
     q80_lf_multi, // one staging, gemm_lf_q80 over the concatenated row blocks
+    staged_q80_lf, // LFAMD_TYPE_STAGED_Q80: gemm_lf_q80 over the concatenated row blocks, no staging
     gemv_dual,    // (multi_types) decode, a {Q4_K | Q5_K} group and a Q6_K group: one launch of the dual GEMV
     wide_dual,    // (multi_types) K-quants of mixed types on one scaled staging: both groups in one loader-wave launch
     wide_runs,    // (multi_types) K-quants of mixed types on one scaled staging: one wide launch per run of equal types
@@ -883,7 +902,11 @@ static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int
         g.route = mm_route::none;
     else if (Btype == LFAMD_TYPE_STAGED_B32) // one GEMM per matrix on the one image (check_group: every matrix must take it)
         g.route = mm_route::each;
-    else if (Btype == LFAMD_TYPE_STAGED_Q8K) // (check_group: every matrix must take the image, unless the group takes it together)
+    else if (Btype == LFAMD_TYPE_STAGED_Q80) { // the route the same call takes on f32 rows, minus the staging (check_group: every matrix must take it)
+        if (count > 1 && count <= 4 && Atype == LFAMD_TYPE_Q8_0 && k > 0 && plan_mul_mat(Atype, m[0], k, n, flags).body == mm_body::q80_lf &&
+            group_row_blocks(count, m, ldc) >= 0)
+            g.route = mm_route::staged_q80_lf;
+    } else if (Btype == LFAMD_TYPE_STAGED_Q8K) // (check_group: every matrix must take the image, unless the group takes it together)
         g.route = mm_route::staged_i8;
     else if (Btype == LFAMD_TYPE_STAGED_SCALED) { // the route the same call takes on f32 rows
         if (wide_group_ok(Atype, count, m, ldc, k, n, flags) && scaled_ok(Atype, flags))
@@ -933,6 +956,13 @@ static int check_group(const mm_group_plan &g, int Atype, int count, const long 
                 return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: a matrix of this call does not run the int8 batch body%s", "");
     if (Btype == LFAMD_TYPE_STAGED_SCALED && (!d_B || !aligned16(d_B)))
         return fail(LFAMD_ERR_INVALID, "mul_mat_multi: the staged image must be 16-byte aligned%s", "");
+    if (g.route == mm_route::staged_q80_lf) {
+        for (int j = 0; j < count; j++)
+            if (m[j] > 0 && !lfamd_mul_mat_takes_staged_q80(Atype, m[j], k, n, flags))
+                return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: a matrix of this call does not run the Q8_0 loader-wave batch body%s", "");
+        if (!d_B || !aligned16(d_B))
+            return fail(LFAMD_ERR_INVALID, "mul_mat_multi: the staged image must be 16-byte aligned%s", "");
+    }
     if (Btype == LFAMD_TYPE_STAGED_SCALED && g.i8_group)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: these matrices run the int8 batch body together (LFAMD_TYPE_STAGED_Q8K)%s", "");
     if (g.workspace && (ws_bytes < g.workspace || !d_ws))
@@ -989,6 +1019,9 @@ static int launch_group(const mm_group_plan &g, int Atype, int count, const void
     }
     case mm_route::q80_lf_multi:
         HIPCHK(lfamd_launch_gemm_lf_q80(count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, s), "gemm_lf (Q8_0, multi)");
+        return LFAMD_OK;
+    case mm_route::staged_q80_lf:
+        HIPCHK(lfamd_launch_gemm_lf_q80_staged(count, d_A, m, k, d_B, n, d_C, ldc, s), "gemm_lf (Q8_0, staged input, multi)");
         return LFAMD_OK;
     default: // (none)
         return LFAMD_OK;
@@ -1080,8 +1113,8 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
         return LFAMD_OK;
     if (!Atype || !d_A || !m || !d_C || !ldc)
         return fail(LFAMD_ERR_INVALID, "mul_mat_multi_types: null argument%s", "");
-    if (Btype == LFAMD_TYPE_STAGED_B32)
-        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: the 32-block staged image is taken by lfamd_mul_mat / lfamd_mul_mat_multi%s", "");
+    if (Btype == LFAMD_TYPE_STAGED_B32 || Btype == LFAMD_TYPE_STAGED_Q80)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: the 32-block staged images are taken by lfamd_mul_mat / lfamd_mul_mat_multi%s", "");
     const mm_group_plan p = plan_types(count, Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags);
     auto run_plan = [&](int j0, int j1) { return plan_group(Atype[j0], j1 - j0, m + j0, k, Btype, b_row_bytes, n, ldc + j0, flags); };
     if (p.route == mm_route::runs) { // every run is checked before the first one is launched
@@ -1185,7 +1218,7 @@ int lfamd_mul_mat_id_multi(int type, int count, const void *const *d_W, long row
     for (int j = 0; j < count; j++) // (the fused launch below goes straight into the kernel: a null stack or result would be a device fault)
         if (!d_W[j] || !d_result[j])
             return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: null expert stack or result%s", "");
-    if (Btype == LFAMD_TYPE_STAGED_B32)
+    if (Btype == LFAMD_TYPE_STAGED_B32 || Btype == LFAMD_TYPE_STAGED_Q80)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_id_multi: no staged image is taken here%s", "");
     if (tasks <= 0 || tasks > thinkers || !type_known(Btype))
         return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: bad shape or activation type%s", "");

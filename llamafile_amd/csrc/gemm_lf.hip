@@ -746,29 +746,17 @@ static int lf_nt(long row_blocks128, long n) {
 }
 
 extern "C" size_t lfamd_gemm_lf_workspace(long k, long n) { // Xh, then the staging and store factors of every token
-    const size_t n_pad = ((size_t)n + 127) / 128 * 128;
-    return n_pad * (size_t)k * 2 + n_pad * 8;
+    return lfamd_q80_image_of(k, n).bytes;
 }
 
-// B: f32 rows or Q8_0 blocks; ws: lfamd_gemm_lf_workspace(k, n) bytes; A[j]: P80 images of m[j] x k.
-extern "C" hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, const long *m, long k, int Btype, const void *B,
-                                               size_t b_row_bytes, long n, float *const *C, const long *ldc, void *ws, hipStream_t s) {
-    if (n <= 0 || count <= 0)
-        return hipSuccess;
-    if (count > GEMM_MAX_MATS || k % 128 || (Btype != LFAMD_TYPE_F32 && Btype != LFAMD_TYPE_Q8_0))
-        return hipErrorInvalidValue;
+extern "C" int lfamd_gemm_lf_q80_fits(long m, long k) { // (the loaders address a tile by a 32-bit byte offset)
+    return (size_t)((m + 7) / 8) * (size_t)(k / 128) * P80_TILE < ((size_t)1 << 32);
+}
+
+// "go": gemm_lf_q80_kernel alone on a staged image's parts (the in-call staging's, or a fused producer's); A[j]: P80 images of m[j] x k
+static hipError_t lf_q80_go(int count, const void *const *A, const long *m, long k, const _Float16 *Xh, const float *tok_scale, long n,
+                            long n_pad, float *const *C, const long *ldc, hipStream_t s) {
     const int nq = (int)(k / 128);
-    const long n_pad = (n + 127) / 128 * 128;
-    _Float16 *Xh = (_Float16 *)ws;
-    float *stage = (float *)((uint8_t *)ws + (size_t)n_pad * (size_t)k * 2), *tok_scale = stage + n_pad;
-    const dim3 pg((unsigned)n_pad, (unsigned)((nq * 16 + 255) / 256));
-    if (Btype == LFAMD_TYPE_F32) {
-        lf_tok_scale_kernel<true><<<(unsigned)n, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, k, stage, tok_scale);
-        prep_lf_kernel<true><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh, stage);
-    } else {
-        lf_tok_scale_kernel<false><<<(unsigned)n, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, k, stage, tok_scale);
-        prep_lf_kernel<false><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh, stage);
-    }
     gemm_mats mats;
     int n_rb = 0;
     mats.count = 0;
@@ -776,7 +764,7 @@ extern "C" hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, 
     for (int j = 0; j < count; j++) {
         if (m[j] <= 0)
             continue;
-        if ((size_t)((m[j] + 7) / 8) * (size_t)nq * P80_TILE >= ((size_t)1 << 32)) // (the loaders address a tile by a 32-bit byte offset)
+        if (!lfamd_gemm_lf_q80_fits(m[j], k))
             return hipErrorInvalidValue;
         const int q = mats.count++;
         mats.A[q] = (const uint8_t *)A[j], mats.C[q] = C[j], mats.m[q] = m[j], mats.ldc[q] = ldc[j];
@@ -795,4 +783,39 @@ extern "C" hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, 
         gemm_lf_q80_kernel<2><<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nq, Xh, n, n_pad, n_rb, n_ct, tok_scale);
     }
     return hipGetLastError();
+}
+
+// "stage", then "go".  B: f32 rows or Q8_0 blocks; ws: lfamd_gemm_lf_workspace(k, n) bytes, laid out as lfamd_q80_image_of
+extern "C" hipError_t lfamd_launch_gemm_lf_q80(int count, const void *const *A, const long *m, long k, int Btype, const void *B,
+                                               size_t b_row_bytes, long n, float *const *C, const long *ldc, void *ws, hipStream_t s) {
+    if (n <= 0 || count <= 0)
+        return hipSuccess;
+    if (count > GEMM_MAX_MATS || k % 128 || (Btype != LFAMD_TYPE_F32 && Btype != LFAMD_TYPE_Q8_0))
+        return hipErrorInvalidValue;
+    const int nq = (int)(k / 128);
+    const lfamd_q80_image im = lfamd_q80_image_of(k, n);
+    const long n_pad = (long)im.n_pad;
+    _Float16 *Xh = (_Float16 *)ws;
+    float *stage = (float *)((uint8_t *)ws + im.stage), *tok_scale = (float *)((uint8_t *)ws + im.tok_scale);
+    const dim3 pg((unsigned)n_pad, (unsigned)((nq * 16 + 255) / 256));
+    if (Btype == LFAMD_TYPE_F32) {
+        lf_tok_scale_kernel<true><<<(unsigned)n, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, k, stage, tok_scale);
+        prep_lf_kernel<true><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh, stage);
+    } else {
+        lf_tok_scale_kernel<false><<<(unsigned)n, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, k, stage, tok_scale);
+        prep_lf_kernel<false><<<pg, 256, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nq, Xh, stage);
+    }
+    return lf_q80_go(count, A, m, k, Xh, tok_scale, n, n_pad, C, ldc, s);
+}
+
+// "go" alone on the image a fused producer wrote (LFAMD_TYPE_STAGED_Q80: csrc/norm_quant.hip): no staging launch, no workspace
+extern "C" hipError_t lfamd_launch_gemm_lf_q80_staged(int count, const void *const *A, const long *m, long k, const void *image, long n,
+                                                      float *const *C, const long *ldc, hipStream_t s) {
+    if (n <= 0 || count <= 0)
+        return hipSuccess;
+    if (count > GEMM_MAX_MATS || k <= 0 || k % 128 || !image || ((uintptr_t)image & 15))
+        return hipErrorInvalidValue;
+    const lfamd_q80_image im = lfamd_q80_image_of(k, n);
+    const uint8_t *p = (const uint8_t *)image;
+    return lf_q80_go(count, A, m, k, (const _Float16 *)p, (const float *)(p + im.tok_scale), n, (long)im.n_pad, C, ldc, s);
 }

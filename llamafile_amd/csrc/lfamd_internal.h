@@ -102,6 +102,8 @@ hipError_t lfamd_launch_gemm_wide_moe(int, const void *, long, int, long, long, 
 size_t lfamd_gemm_lf_workspace(long, long);
 hipError_t lfamd_launch_gemm_lf_q80(int, const void *const *, const long *, long, int, const void *, size_t, long, float *const *, const long *,
                                     void *, hipStream_t);
+hipError_t lfamd_launch_gemm_lf_q80_staged(int, const void *const *, const long *, long, const void *, long, float *const *, const long *, hipStream_t);
+int lfamd_gemm_lf_q80_fits(long, long); // (m, k): the P80 image is below the 4 GiB the loaders address
 hipError_t lfamd_launch_gemm_lf_float(int, const void *, size_t, long, long, const void *, long, long, float *, long, hipStream_t);
 size_t lfamd_gemm_q80_workspace(long, long);
 hipError_t lfamd_launch_gemm_q80(const void *, long, long, int, const void *, size_t, long, float *, long, void *, int, int, hipStream_t);
@@ -155,4 +157,15 @@ static inline lfamd_b32_image lfamd_b32_image_of(long k, long n) {
     const size_t n_pad = ((size_t)n + 127) / 128 * 128, nb = (size_t)(k / 256), d8T = lfamd_up256(n_pad * (size_t)k * 2);
     const size_t sT = d8T + lfamd_up256(nb * 8 * n_pad * 4);
     return {n_pad, d8T, sT, sT + lfamd_up256(nb * 8 * n_pad * 4)};
+}
+
+// The image of the Q8_0-weight loader-wave body (LFAMD_TYPE_STAGED_Q80, and what lfamd_launch_gemm_lf_q80 stages per call; gemm_lf.hip):
+// Xh f16 [k / 128][n_pad][128], 256 bytes per token and quad in the chunk permutation of prep_lf_kernel, then stage f32 [n_pad], then
+// tok_scale f32 [n_pad], packed without padding.
+struct lfamd_q80_image {
+    size_t n_pad, stage, tok_scale, bytes;
+};
+static inline lfamd_q80_image lfamd_q80_image_of(long k, long n) {
+    const size_t n_pad = ((size_t)n + 127) / 128 * 128, stage = n_pad * (size_t)k * 2;
+    return {n_pad, stage, stage + n_pad * 4, stage + n_pad * 8};
 }

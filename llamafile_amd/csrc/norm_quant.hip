@@ -194,14 +194,18 @@ __device__ static inline void put_scaled_zero(const scaled_image &im, int b, lon
 }
 // the row's power-of-two normalisation from the largest |y| each wave saw (every wave reduces the partial maxima itself)
 template <int NWV>
-__device__ static inline float row_scale(float dmax, float *wmax, int wave, int lane, float *tok_scale_out) {
+__device__ static inline float row_max(float dmax, float *wmax, int wave, int lane) { // (holds a barrier)
     dmax = wave_max_f32(dmax);
     if (lane == 0)
         wmax[wave] = dmax;
     __syncthreads();
     float m = wmax[lane & (NWV - 1)];
     m = fmaxf(m, dpp_f32<DPP_XOR1>(m));
-    m = fmaxf(m, dpp_f32<DPP_XOR2>(m));
+    return fmaxf(m, dpp_f32<DPP_XOR2>(m));
+}
+template <int NWV>
+__device__ static inline float row_scale(float dmax, float *wmax, int wave, int lane, float *tok_scale_out) {
+    const float m = row_max<NWV>(dmax, wmax, wave, lane);
     const bool ok = m > 0.0f && m < 3.0e38f; // (zero / non-finite rows: no normalisation)
     if (tok_scale_out && wave == 0 && lane == 0)
         *tok_scale_out = ok ? ldexpf(1.0f, ilogbf(m) - 9) : 1.0f;
@@ -497,6 +501,141 @@ __global__ __launch_bounds__(256) void swiglu_b32_kernel(const float *__restrict
         put_b32_rows<FMT == B32_Q8_1>(yq + row * yq_row_bytes + (size_t)b * 8 * (FMT == B32_Q8_1 ? 36 : 34), y, lane, valid);
 }
 
+// ---- the image of the Q8_0-weight batch body (lfamd_q80_image_of): what lf_tok_scale_kernel and
+// prep_lf_kernel of gemm_lf.hip write per call.  Per token a power of two from D = f32(f16(rowmax |y| / 127)) * 127, the row's largest
+// block scale as the blocks store it: stage = 2^(9 - ilogb(D)), tok_scale = 2^(ilogb(D) - 9) (D zero or not finite: 1 and 1).  Per
+// 128-weight quad and token 256 bytes of f16(f32(f16(d)) * stage * code) of quantize_row_q8_0 — the f32 product is exact (11 + 7
+// significant bits), so it is rounded once — where block blk of the quad, elements 4 j .. 4 j + 3, sit at byte
+// (2 s + (j >> 2)) * 16 + (blk & 1) * 8, s = 2 (j & 3) + (blk >> 1).  A lane's four values are elements 4 j .. 4 j + 3 of block
+// (lane >> 3) & 3 of quad 2 b + (lane >> 5), j = lane & 7.  Rows need k % 128 == 0: lanes 32 .. 63 of a last half chunk hold zeros,
+// load and store nothing, and share no DPP step with lanes 0 .. 31 (rows of 16 lanes).
+struct q80_image {
+    _Float16 *Xh;
+    float *stage, *tok_scale;
+    long n_pad;
+};
+__device__ static inline int q80_chunk_byte(int lane) { // where the lane's half4 goes inside the 256 bytes of its quad and token
+    const int blk = (lane >> 3) & 3, j = lane & 7, s = 2 * (j & 3) + (blk >> 1);
+    return (2 * s + (j >> 2)) * 16 + (blk & 1) * 8;
+}
+__device__ static inline void put_q80_image(const q80_image &im, int b, long tok, const float (&y)[4], float stage, int lane, bool valid) {
+    typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+    int q[4], sum;
+    float d;
+    quantize_b32(y, q, d, sum); // (the code sum is not used: its three DPP steps fall away)
+    if (!valid)
+        return;
+    const float ds = h2f(f2h_bits(d)) * stage; // (exact: a power of two)
+    const half4_t h4 = {(_Float16)(ds * (float)q[0]), (_Float16)(ds * (float)q[1]), (_Float16)(ds * (float)q[2]), (_Float16)(ds * (float)q[3])};
+    uint8_t *dst = (uint8_t *)im.Xh + ((size_t)(2 * b + (lane >> 5)) * im.n_pad + tok) * 256;
+    *(half4_t *)(dst + q80_chunk_byte(lane)) = h4;
+}
+// a padding token of the image: zero operands, factors of 1
+__device__ static inline void put_q80_zero_row(const q80_image &im, long tok, long k, int wave, int lane) {
+    for (int b = wave; b < (int)((k + 255) / 256); b += 4)
+        if ((long)b * 256 + 4 * lane < k)
+            *(uint2 *)((uint8_t *)im.Xh + ((size_t)(2 * b + (lane >> 5)) * im.n_pad + tok) * 256 + 8 * (lane & 31)) = make_uint2(0u, 0u);
+    if (wave == 0 && lane == 0)
+        im.stage[tok] = 1.0f, im.tok_scale[tok] = 1.0f;
+}
+// the token's two factors from the largest |y| each lane saw (lf_tok_scale_kernel's rule; every wave reduces the partial maxima itself)
+__device__ static inline float q80_row_stage(float dmax, float *wmax, const q80_image &im, long tok, int wave, int lane) {
+    const float D = h2f(f2h_bits(row_max<4>(dmax, wmax, wave, lane) / 127.0f)) * 127.0f;
+    const bool ok = D > 0.0f && D < 3.0e38f; // (zero / non-finite rows: no normalisation)
+    const float stage = ok ? ldexpf(1.0f, 9 - ilogbf(D)) : 1.0f;
+    if (wave == 0 && lane == 0)
+        im.stage[tok] = stage, im.tok_scale[tok] = ok ? ldexpf(1.0f, ilogbf(D) - 9) : 1.0f;
+    return stage;
+}
+__device__ static inline float max_abs4(const float (&y)[4]) {
+    return fmaxf(fmaxf(fabsf(y[0]), fabsf(y[1])), fmaxf(fabsf(y[2]), fabsf(y[3])));
+}
+
+// RMS-norm x weight -> the Q8_0 body's image: pass 1 the sum of squares, pass 2 the largest |y| of the row, pass 3 the blocks (the
+// skeleton of rms_norm_scaled_kernel: one work-group of 4 waves per token of n_pad, the row re-read from L1 / L2, the same y bit for bit)
+__global__ __launch_bounds__(256) void rms_norm_q80_kernel(const float *__restrict__ x, size_t x_row_bytes, const float *__restrict__ w,
+                                                           float eps, long k, float *__restrict__ yf, size_t yf_row_bytes, long nrows,
+                                                           q80_image im) {
+    __shared__ double part[4];
+    __shared__ float wmax[4];
+    const long row = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nc = (int)((k + 255) / 256);
+    if (row >= nrows) { // (uniform) the image's padding tokens
+        put_q80_zero_row(im, row, k, wave, lane);
+        return;
+    }
+    const float *xr = (const float *)((const uint8_t *)x + row * x_row_bytes);
+    double s = 0.0;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        if (at < k)
+            s += squares4(*(const float4 *)(xr + at));
+    }
+    const float scale = rms_scale(s, part, wave, lane, k, eps);
+    auto y_of = [&](long at, float (&y)[4]) { norm_y(y, *(const float4 *)(xr + at), scale, w ? w + at : nullptr); };
+    float dmax = 0.0f;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        if (at < k) {
+            float y[4];
+            y_of(at, y);
+            dmax = fmaxf(dmax, max_abs4(y));
+        }
+    }
+    const float stage = q80_row_stage(dmax, wmax, im, row, wave, lane);
+    float *frow = yf ? (float *)((uint8_t *)yf + row * yf_row_bytes) : nullptr;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        const bool valid = at < k;
+        float y[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (valid) {
+            y_of(at, y); // (the same instructions on the same inputs: the same bits as in pass 2)
+            if (frow)
+                *(float4 *)(frow + at) = make_float4(y[0], y[1], y[2], y[3]);
+        }
+        put_q80_image(im, b, row, y, stage, lane, valid);
+    }
+}
+
+// silu(gate) * up -> the Q8_0 body's image: the skeleton of swiglu_scaled_kernel — pass 1 the largest |y|, pass 2 the blocks
+__global__ __launch_bounds__(256) void swiglu_q80_kernel(const float *__restrict__ gate, size_t gate_row_bytes, const float *__restrict__ up,
+                                                         size_t up_row_bytes, long k, float *__restrict__ yf, size_t yf_row_bytes, long nrows,
+                                                         q80_image im) {
+    __shared__ float wmax[4];
+    const long row = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nc = (int)((k + 255) / 256);
+    if (row >= nrows) {
+        put_q80_zero_row(im, row, k, wave, lane);
+        return;
+    }
+    const float *gr = (const float *)((const uint8_t *)gate + row * gate_row_bytes), *ur = (const float *)((const uint8_t *)up + row * up_row_bytes);
+    auto y_of = [&](long at, float (&y)[4]) { swiglu_y(y, *(const float4 *)(gr + at), *(const float4 *)(ur + at)); };
+    float dmax = 0.0f;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        if (at < k) {
+            float y[4];
+            y_of(at, y);
+            dmax = fmaxf(dmax, max_abs4(y));
+        }
+    }
+    const float stage = q80_row_stage(dmax, wmax, im, row, wave, lane);
+    float *frow = yf ? (float *)((uint8_t *)yf + row * yf_row_bytes) : nullptr;
+    for (int b = wave; b < nc; b += 4) {
+        const long at = (long)b * 256 + 4 * lane;
+        const bool valid = at < k;
+        float y[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (valid) {
+            y_of(at, y); // (the same instructions on the same inputs: the same bits as in pass 1)
+            if (frow)
+                *(float4 *)(frow + at) = make_float4(y[0], y[1], y[2], y[3]);
+        }
+        put_q80_image(im, b, row, y, stage, lane, valid);
+    }
+}
+
 } // namespace
 
 static scaled_image scaled_of(void *image, long k, long nrows) {
@@ -589,7 +728,7 @@ extern "C" int lfamd_swiglu_quantize(const float *d_gate, size_t gate_row_bytes,
     return LFAMD_OK;
 }
 
-// ---- the 32-block formats: Q8_0 / Q8_1 rows and LFAMD_TYPE_STAGED_B32 (entry points of their own: the two above keep refusing them)
+// ---- the 32-block formats: Q8_0 / Q8_1 rows, LFAMD_TYPE_STAGED_B32 and LFAMD_TYPE_STAGED_Q80 (entry points of their own: the two above keep refusing them)
 static b32_image b32_of(void *image, long k, long nrows) {
     const lfamd_b32_image l = lfamd_b32_image_of(k, nrows);
     uint8_t *p = (uint8_t *)image;
@@ -600,6 +739,16 @@ extern "C" size_t lfamd_staged_b32_size(long k, long nrows) { // = lfamd_mul_mat
     return k <= 0 || k % 256 || nrows < 0 ? 0 : lfamd_b32_image_of(k, nrows).bytes;
 }
 
+static q80_image q80_of(void *image, long k, long nrows) {
+    const lfamd_q80_image l = lfamd_q80_image_of(k, nrows);
+    uint8_t *p = (uint8_t *)image;
+    return {(_Float16 *)p, (float *)(p + l.stage), (float *)(p + l.tok_scale), (long)l.n_pad};
+}
+
+extern "C" size_t lfamd_staged_q80_size(long k, long nrows) { // = lfamd_gemm_lf_workspace(k, nrows)
+    return k <= 0 || k % 128 || nrows < 0 ? 0 : lfamd_q80_image_of(k, nrows).bytes;
+}
+
 // what both 32-block producers ask of their output arguments (the f32 operands: each entry point's own line)
 static bool b32_output_ok(long nrows, long k, int vec_dot_type, const void *d_yq, size_t yq_row_bytes, const float *d_yf, size_t yf_row_bytes) {
     if (nrows < 0 || k <= 0 || k % 32 || (!d_yq && !d_yf) || ((uintptr_t)d_yf & 15) || (yf_row_bytes & 15))
@@ -608,6 +757,8 @@ static bool b32_output_ok(long nrows, long k, int vec_dot_type, const void *d_yq
         return true;
     if (vec_dot_type == LFAMD_TYPE_STAGED_B32)
         return k % 256 == 0 && ((uintptr_t)d_yq & 15) == 0;
+    if (vec_dot_type == LFAMD_TYPE_STAGED_Q80)
+        return k % 128 == 0 && ((uintptr_t)d_yq & 15) == 0;
     if (vec_dot_type != LFAMD_TYPE_Q8_0 && vec_dot_type != LFAMD_TYPE_Q8_1)
         return false;
     const size_t a = vec_dot_type == LFAMD_TYPE_Q8_1 ? 3 : 1, row = (size_t)(k / 32) * (vec_dot_type == LFAMD_TYPE_Q8_1 ? 36 : 34);
@@ -628,14 +779,17 @@ extern "C" int lfamd_rms_norm_quantize_b32(const float *d_x, size_t x_row_bytes,
                                            void *stream) {
     if (!b32_output_ok(nrows, k, vec_dot_type, d_yq, yq_row_bytes, d_yf, yf_row_bytes) || !d_x || ((uintptr_t)d_x & 15) || (x_row_bytes & 15) ||
         ((uintptr_t)d_weight & 15)) {
-        lfamd_set_error("lfamd_rms_norm_quantize_b32: k must be a multiple of 32 (the staged image: of 256, 16-byte aligned), output format "
-                        "Q8_0 / Q8_1 rows (2- / 4-byte aligned, stride at least the row) or LFAMD_TYPE_STAGED_B32, 16-byte aligned f32 rows");
+        lfamd_set_error("lfamd_rms_norm_quantize_b32: k must be a multiple of 32 (the staged images: B32 of 256, Q80 of 128, 16-byte aligned), output "
+                        "format Q8_0 / Q8_1 rows (2- / 4-byte aligned, stride at least the row), LFAMD_TYPE_STAGED_B32 or _Q80, 16-byte aligned f32 rows");
         return LFAMD_ERR_INVALID;
     }
     if (nrows == 0)
         return LFAMD_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_B32) {
+    if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_Q80) {
+        const q80_image im = q80_of(d_yq, k, nrows);
+        rms_norm_q80_kernel<<<(unsigned)im.n_pad, 256, 0, s>>>(d_x, x_row_bytes, d_weight, eps, k, d_yf, yf_row_bytes, nrows, im);
+    } else if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_B32) {
         const b32_image im = b32_of(d_yq, k, nrows);
         rms_norm_b32_kernel<B32_IMAGE><<<(unsigned)im.n_pad, 256, 0, s>>>(d_x, x_row_bytes, d_weight, eps, k, nullptr, 0, d_yf, yf_row_bytes, nrows, im);
     } else if (d_yq && vec_dot_type == LFAMD_TYPE_Q8_1) {
@@ -653,16 +807,19 @@ extern "C" int lfamd_swiglu_quantize_b32(const float *d_gate, size_t gate_row_by
                                          void *stream) {
     if (!b32_output_ok(nrows, k, vec_dot_type, d_yq, yq_row_bytes, d_yf, yf_row_bytes) || !d_gate || !d_up || ((uintptr_t)d_gate & 15) ||
         (gate_row_bytes & 15) || ((uintptr_t)d_up & 15) || (up_row_bytes & 15) || nrows > 65535 - 127) {
-        lfamd_set_error("lfamd_swiglu_quantize_b32: k must be a multiple of 32 (the staged image: of 256, 16-byte aligned), output format "
-                        "Q8_0 / Q8_1 rows (2- / 4-byte aligned, stride at least the row) or LFAMD_TYPE_STAGED_B32, 16-byte aligned f32 rows, "
-                        "<= 65408 rows");
+        lfamd_set_error("lfamd_swiglu_quantize_b32: k must be a multiple of 32 (the staged images: B32 of 256, Q80 of 128, 16-byte aligned), output "
+                        "format Q8_0 / Q8_1 rows (2- / 4-byte aligned, stride at least the row), LFAMD_TYPE_STAGED_B32 or _Q80, 16-byte aligned f32 "
+                        "rows, <= 65408 rows");
         return LFAMD_ERR_INVALID;
     }
     if (nrows == 0)
         return LFAMD_OK;
     hipStream_t s = (hipStream_t)stream;
     const unsigned gx = (unsigned)(((k + 255) / 256 + 3) / 4);
-    if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_B32) {
+    if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_Q80) {
+        const q80_image im = q80_of(d_yq, k, nrows);
+        swiglu_q80_kernel<<<(unsigned)im.n_pad, 256, 0, s>>>(d_gate, gate_row_bytes, d_up, up_row_bytes, k, d_yf, yf_row_bytes, nrows, im);
+    } else if (d_yq && vec_dot_type == LFAMD_TYPE_STAGED_B32) {
         const b32_image im = b32_of(d_yq, k, nrows);
         swiglu_b32_kernel<B32_IMAGE><<<dim3(gx, (unsigned)im.n_pad), 256, 0, s>>>(d_gate, gate_row_bytes, d_up, up_row_bytes, k, nullptr, 0, d_yf,
                                                                                  yf_row_bytes, nrows, im);
