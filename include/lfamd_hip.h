@@ -52,8 +52,19 @@ enum lfamd_status {
 #define LFAMD_FLAG_Q80_EXACT 64u    /* Q8_0 batches (n > 8): the BIT-EXACT restatement of tinyBLAS_Q0's 8-lane chains (VALU, ~12x
                                        slower) instead of the default: this module's f16 MFMA body on the resident image, f16(d * q) x
                                        f16(d8 * code), <= 1e-3 (csrc/gemm_lf.hip; rows that are not whole 128-weight groups run the exact
-                                       kernel anyway).  n <= 8 — the Q8_0 vecdot of the north star — is always bit-exact;
-                                       LFAMD_FLAG_PRECISE implies this flag. */
+                                       kernel anyway).  n <= 8 — the Q8_0 vecdot of the north star — is bit-exact unless the caller
+                                       asks for LFAMD_FLAG_Q80_RELAXED; LFAMD_FLAG_PRECISE implies this flag. */
+#define LFAMD_FLAG_Q80_RELAXED 128u /* Q8_0 weights, n <= 8 (decode): the GEMV that splits K over the waves of a work-group
+                                       (csrc/gemv_q80r_impl.h).  The same integer block dots, added in f32 in this module's own fixed
+                                       order instead of tinyBLAS_Q0's chain: deterministic, within 2e-6 of the CPU reference, NOT its
+                                       bits (lfamd_mul_mat_is_bit_exact answers 0; lfamd_mul_mat_is_exact still 1).  The order depends
+                                       on k alone — not on m, n, the column's position, the sibling count or the activation format.
+                                       Ignored for every other type and for n > 8; LFAMD_FLAG_PRECISE, LFAMD_FLAG_Q80_EXACT and
+                                       LFAMD_FLAG_FORCE_GENERIC override it (their routes are unchanged), LFAMD_FLAG_Q0_VREGS32 has no
+                                       effect under it; rows too deep for the kernel's LDS run the bit-exact kernel.  lfamd_mul_mat
+                                       and lfamd_mul_mat_multi serve it (siblings stay one launch); lfamd_mul_mat_multi_types and the
+                                       MUL_MAT_ID calls pass `flags` on, so their per-matrix / per-expert calls of n <= 8 inherit it.
+                                       No workspace, no staged image; workspace sizes and refusals are those of the call without it. */
 
 int lfamd_abi_version(void);
 const char *lfamd_last_error(void);
@@ -153,7 +164,7 @@ static inline unsigned lfamd_exact_flag(int type) {
  * reference's CPU arithmetic, iqk_mul_mat.inc:601-643; within 2e-6 of it: only the order of the f32 sums differs); 0 = scaled
  * operands on the f16 matrix cores (one f16 rounding per operand, <= 1e-3, measured ~3e-4).  In order:
  *   LFAMD_FLAG_FORCE_GENERIC: 1 (the generic kernels; packed types refuse the flag);
- *   every call of up to 8 columns (the GEMVs; Q8_0 bit-exact): 1;
+ *   every call of up to 8 columns (the GEMVs; Q8_0 bit-exact, or this module's own order under LFAMD_FLAG_Q80_RELAXED): 1;
  *   F32 / F16 / BF16 weights: 1 — the activations are taken in, or rounded from F32 to, the weight's own type, as the
  *     reference's vec_dot_type conversion does, and the products of two 16-bit values are exact in f32;
  *   Q8_0 batches: 0 on the f16 MFMA body (rows of whole 128-weight quads, or the vendor GEMM), 1 on the bit-exact kernel
@@ -168,6 +179,11 @@ static inline unsigned lfamd_exact_flag(int type) {
  * that would run the int8 body alone shares the scaled f16 staging with its Q6_K sibling there).  A matrix that
  * lfamd_scaled_gemm_ok found out of range is asked about with lfamd_exact_flag(type) in `flags`.  No device call is made. */
 int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags);
+/* 1 where the call reproduces the CPU reference's BITS, 0 otherwise.  1: Q8_0 weights with n <= 8 (the vecdot) and Q8_0 batches on
+ * the bit-exact kernel (lfamd_mul_mat_is_exact answers 1 for them).  0: a Q8_0 call of n <= 8 that LFAMD_FLAG_Q80_RELAXED moves to
+ * the relaxed-order GEMV (1 again where that kernel declines the row, or a flag overrides it), and every other type — their bodies
+ * are held to a tolerance, not to bits.  Read from the plan the launch reads.  No device call is made. */
+int lfamd_mul_mat_is_bit_exact(int Atype, long m, long k, long n, unsigned flags);
 
 /* ---- activations --------------------------------------------------------------------------
  * f32 rows -> the reference's activation block format (vec_dot_type: Q8_0, Q8_1 or Q8_K in

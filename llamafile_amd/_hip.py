@@ -20,6 +20,7 @@ FLAG_GEMM_NARROW = 8
 FLAG_GEMM_WIDE = 16
 FLAG_GEMM_PLAIN = 32
 FLAG_Q80_EXACT = 64
+FLAG_Q80_RELAXED = 128
 TYPE_STAGED_Q8K = 0x1000  # the int8 batch body's staged activation image (lfamd_hip.h)
 TYPE_STAGED_SCALED = 0x1001  # the scaled-operand f16 batch bodies' staged activation image
 TYPE_STAGED_B32 = 0x1002  # the 32-block batch bodies' staged activation image (Q8_0 / Q8_1-quantised activations)
@@ -52,6 +53,7 @@ _SIGS = {
     "lfamd_get_rows": (_i, [_i, _vp, _l, _l, _vp, _l, _l, _i, _vp, _sz, _vp]),
     "lfamd_unpack_weights": (_i, [_i, _l, _l, _vp, _vp, _sz, _vp]),
     "lfamd_mul_mat_is_exact": (_i, [_i, _l, _l, _l, _u]),
+    "lfamd_mul_mat_is_bit_exact": (_i, [_i, _l, _l, _l, _u]),
     "lfamd_mul_mat_takes_staged": (_i, [_i, _l, _l, _l, _u]),
     "lfamd_staged_q8k_size": (_sz, [_l, _l]),
     "lfamd_mul_mat_takes_staged_scaled": (_i, [_i, _l, _l, _l, _u]),

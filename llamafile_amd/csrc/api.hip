@@ -402,13 +402,22 @@ struct mm_plan {
     mm_body body;
     bool scaled;      // wide: the activations are staged scaled (prep mode 2) for the scaled-operand loader-wave bodies
     bool exact;       // lfamd_mul_mat_is_exact
+    bool bit_exact;   // lfamd_mul_mat_is_bit_exact: the result reproduces the CPU reference's bits
+    bool relaxed;     // gemv on Q8_0: the relaxed-order kernel (LFAMD_FLAG_Q80_RELAXED where nothing overrides it and its plan accepts k)
     size_t workspace; // bytes lfamd_mul_mat asks for (generic: only when it quantises f32 activations)
 };
+
+// May a Q8_0 decode GEMV of this call run the relaxed-order kernel?  The flag, unless one of the flags that keep today's routes is
+// set, and only where the kernel's plan takes the row (deep rows: the bit-exact kernel).  The launch passes the answer down.
+static bool q80_relaxed(int Atype, long k, long n, unsigned flags) {
+    return Atype == LFAMD_TYPE_Q8_0 && n <= 8 && (flags & LFAMD_FLAG_Q80_RELAXED) &&
+           !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT | LFAMD_FLAG_FORCE_GENERIC)) && lfamd_gemv_q80_relaxed_cols(k) > 0;
+}
 
 static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
     const unsigned forced = flags & (LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN); // (a module body, by name)
     const bool f16_q80 = !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT));
-    mm_plan p = {mm_body::generic, false, true, 0};
+    mm_plan p = {mm_body::generic, false, true, false, false, 0};
     if (flags & LFAMD_FLAG_FORCE_GENERIC)
         p.body = packed(Atype, k) ? mm_body::refused : mm_body::generic;
     else if (sb_takes(Atype, m, k, n, flags))
@@ -447,8 +456,12 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
                  : f16_q80 && k % 128 == 0 && !lfamd_blaslt_ok() ? mm_body::q80_lf
                                                                  : mm_body::q80_exact;
         p.exact = p.body == mm_body::q80_exact;
-    } else if (n <= 8 && packed(Atype, k))
+    } else if (n <= 8 && packed(Atype, k)) {
         p.body = mm_body::gemv;
+        p.relaxed = q80_relaxed(Atype, k, n, flags);
+    }
+    // the CPU reference's bits: the Q8_0 chains, decode and the q80_exact batches (no float route is held to more than 2e-6 of it)
+    p.bit_exact = Atype == LFAMD_TYPE_Q8_0 && ((p.body == mm_body::gemv && !p.relaxed) || p.body == mm_body::q80_exact);
 
     const size_t n_pad = align_up((size_t)n, 128), act = lfamd_kq_image_of(k, n).parts; // (the staged K-quant image, lfamd_internal.h)
     switch (p.body) {
@@ -498,6 +511,14 @@ int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags) {
     if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
     return plan_mul_mat(Atype, m, k, n, flags).exact ? 1 : 0;
+}
+
+// Does the call reproduce the CPU reference's bits (tinyBLAS_Q0's f32 chain for Q8_0)?  Read from the plan the launch reads: 0 for
+// a Q8_0 decode call that LFAMD_FLAG_Q80_RELAXED moves to the relaxed-order kernel, 1 for the same call where that kernel declines.
+int lfamd_mul_mat_is_bit_exact(int Atype, long m, long k, long n, unsigned flags) {
+    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+        return 0;
+    return plan_mul_mat(Atype, m, k, n, flags).bit_exact ? 1 : 0;
 }
 
 // Does a call accept the scaled-operand staged image a fused producer wrote (LFAMD_TYPE_STAGED_SCALED)?  The K-quant batches whose
@@ -796,7 +817,7 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
         HIPCHK(lfamd_launch_gemm_q80(d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, vregs32, precise, s), "gemm_q80");
         return LFAMD_OK;
     case mm_body::gemv:
-        HIPCHK(lfamd_launch_gemv(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, vregs32, precise, s), "gemv");
+        HIPCHK(lfamd_launch_gemv(Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, vregs32, precise, p.relaxed ? 1 : 0, s), "gemv");
         return LFAMD_OK;
     case mm_body::gemv_float: // decode on float weights (16-byte loads)
         if (aligned16(d_A) && aligned16(d_B) && !(b_row_bytes & 15)) {
@@ -892,12 +913,13 @@ struct mm_group_plan {
     bool i8_group;    // 2 .. 4 matrices whose row blocks together make a grid the int8 body takes
     size_t workspace; // bytes the route stages into (0: it takes none)
     mm_side a, b;     // (plan_types) gemv_dual / wide_dual: the two groups
+    bool relaxed;     // gemv_multi on Q8_0: the relaxed-order kernel (q80_relaxed), decided here and read by the launch
 };
 
 // The route of sibling matrices of one type (a lfamd_mul_mat_multi call, or one run of a lfamd_mul_mat_multi_types call).
 static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int Btype, size_t b_row_bytes, long n, const long *ldc,
                                 unsigned flags) {
-    mm_group_plan g = {mm_route::each, count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags), 0, {}, {}};
+    mm_group_plan g = {mm_route::each, count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags), 0, {}, {}, false};
     if (count <= 0 || (staged_type(Btype) && n == 0))
         g.route = mm_route::none;
     else if (Btype == LFAMD_TYPE_STAGED_B32) // one GEMM per matrix on the one image (check_group: every matrix must take it)
@@ -928,7 +950,7 @@ static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int
         if (all_sb)
             g.route = mm_route::sb_shared, g.workspace = align_up(lfamd_gemm_sb_workspace(k), 256);
         else if (gemv)
-            g.route = n == 0 ? mm_route::none : mm_route::gemv_multi;
+            g.route = n == 0 ? mm_route::none : mm_route::gemv_multi, g.relaxed = q80_relaxed(Atype, k, n, flags);
         // Q4_K siblings whose tiles TOGETHER make a grid the int8 body takes (attn_q/k/v of an all-Q4_K layer: 48 row blocks at 512
         // tokens): one staging, one launch over the concatenated row blocks, exact integer dots (6144 x 4096 x 512: 47.5 us against 56.8)
         else if (rows_ok && g.i8_group)
@@ -999,7 +1021,7 @@ static int launch_group(const mm_group_plan &g, int Atype, int count, const void
         return LFAMD_OK;
     case mm_route::gemv_multi:
         HIPCHK(lfamd_launch_gemv_multi(Atype, count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0,
-                                       (flags & LFAMD_FLAG_PRECISE) ? 1 : 0, s),
+                                       (flags & LFAMD_FLAG_PRECISE) ? 1 : 0, g.relaxed ? 1 : 0, s),
                "gemv_multi");
         return LFAMD_OK;
     case mm_route::i8_multi:
@@ -1077,7 +1099,7 @@ template <class F> static int each_run(int count, const int *Atype, F fn) {
 static mm_group_plan plan_types(int count, const int *Atype, const void *const *d_A, const long *m, long k, int Btype, const void *d_B,
                                 size_t b_row_bytes, long n, float *const *d_C, const long *ldc, const void *d_ws, size_t ws_bytes,
                                 unsigned flags) {
-    mm_group_plan p = {mm_route::runs, false, 0, {}, {}};
+    mm_group_plan p = {mm_route::runs, false, 0, {}, {}, false};
     const bool paired = split_pair(count, Atype, d_A, m, d_C, ldc, p.a, p.b);
     const bool rows_ok = (Btype == LFAMD_TYPE_F32 || Btype == LFAMD_TYPE_Q8_K) && b_row_bytes >= lfamd_row_size(Btype, k);
     // decode (n = 1) with exactly two K-quant types {Q4_K | Q5_K, Q6_K}: ONE launch (gemv_kq_dual_kernel)

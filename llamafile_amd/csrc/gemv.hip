@@ -1,6 +1,7 @@
 // gemv.hip — the decode GEMVs' host side: the launch plan (which kernel form, how many waves, which grid, how much LDS), the
 // matrix tables and the launches.  No kernel is compiled here: the units gemv_q4k / q5k / q6k / q40 / q41 / q50 / q51 / q2k /
-// q3k / iq4xs / iq4nl / dual / q80 / q80b.hip instantiate them (gemv_impl.h, gemv_q80_impl.h) and hand out their addresses.
+// q3k / iq4xs / iq4nl / dual / q80 / q80b / q80r / q80rb.hip instantiate them (gemv_impl.h, gemv_q80_impl.h, gemv_q80r_impl.h) and hand out
+// their addresses.
 #include "gemv_launch.h"
 #include <stdlib.h>
 
@@ -55,6 +56,8 @@ static const kq_unit *kq_unit_of(int Atype) {
 static const void *kernel_of(int Atype, int f32in, const lfamd_gemv_plan &p, int q80_mode, bool early = false) {
     if (p.variant == LFAMD_GEMV_Q80)
         return Atype != LFAMD_TYPE_Q8_0 ? nullptr : f32in ? lfamd_gemv_kernel_q80_f32(p.nc, q80_mode) : lfamd_gemv_kernel_q80_q80(p.nc, q80_mode);
+    if (p.variant == LFAMD_GEMV_Q80R)
+        return Atype != LFAMD_TYPE_Q8_0 ? nullptr : f32in ? lfamd_gemv_kernel_q80r_f32(p.nc, p.nw, p.ch) : lfamd_gemv_kernel_q80r_q80(p.nc, p.nw, p.ch);
     const kq_unit *u = kq_unit_of(Atype);
     gemv_kernel_fn *fn = !u ? nullptr : p.variant == LFAMD_GEMV_TWO_TYPES ? u->with_q6k : u->kernel;
     int variant = p.variant;
@@ -94,6 +97,22 @@ extern "C" int lfamd_gemv_cols_per_launch(int Atype, long k) {
     return step;
 }
 
+// Columns one launch of the relaxed-order Q8_0 kernel takes (LFAMD_GEMV_MULTI_RELAXED): as many of eight as keep its LDS under the
+// cap; 0 = one column does not fit (or k is no row of whole blocks) and the call runs gemv_q80_kernel.
+extern "C" int lfamd_gemv_q80_relaxed_cols(long k) {
+    if (k <= 0 || k % 32 || k / 32 > (1 << 20))
+        return 0;
+    int nc = 8;
+    while (nc > 0 && q80r_lds_of(nc, q80_quads(k), Q80R_WAVES).bytes > IMAGE_CAP)
+        nc--;
+    return nc;
+}
+
+// the relaxed-order kernel's LDS for nc columns of a k-long row (the layout: gemv_launch.h, q80r_lds_of)
+extern "C" size_t lfamd_gemv_q80_relaxed_lds_bytes(int nc, long k) {
+    return q80r_lds_of(nc, q80_quads(k), Q80R_WAVES).bytes;
+}
+
 // every work-group the same number of items: the grid that covers `items` with at most max_wg work-groups
 static int even_grid(int items, int max_wg, int *per_wg = nullptr) {
     const int per = (items + max_wg - 1) / max_wg;
@@ -111,6 +130,17 @@ extern "C" int lfamd_gemv_plan_of(int kind, int Atype, int nc, long work, long w
     p->nc = nc;
     if (work <= 0 || cus <= 0 || (kind == LFAMD_GEMV_DUAL && work_b <= 0))
         return -1;
+    if (kind == LFAMD_GEMV_MULTI_RELAXED) {
+        // Q8_0 with K split over the waves of one persistent work-group per CU; work: the launch's 8-row groups, one item each.
+        // NW and the chunk depend on k alone, so the order in which an output's terms are added does too.
+        if (Atype != LFAMD_TYPE_Q8_0 || nc > lfamd_gemv_q80_relaxed_cols(k))
+            return -1;
+        const int nquads = q80_quads(k);
+        p->variant = LFAMD_GEMV_Q80R, p->nw = Q80R_WAVES, p->ch = q80r_chunk_quads(nquads), p->rows = 8;
+        p->grid = even_grid((int)work, cus);
+        p->lds = (int)q80r_lds_of(nc, nquads, Q80R_WAVES).bytes;
+        return 0;
+    }
     if (Atype == LFAMD_TYPE_Q8_0) {
         if (kind != LFAMD_GEMV_MULTI)
             return -1;
@@ -286,6 +316,14 @@ static hipError_t launch_q80(const void *kernel, const lfamd_gemv_plan &p, const
     return launch(kernel, p, args, s);
 }
 
+// gemv_q80r_kernel
+static hipError_t launch_q80r(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, long k, int n_items,
+                              q80_mats &mats, hipStream_t s) {
+    int nblocks = (int)(k / 32), nquads = q80_quads(k);
+    void *args[] = {&B, &brb, &col0, &nblocks, &nquads, &n_items, (void *)&p.grid, &mats};
+    return launch(kernel, p, args, s);
+}
+
 // ---- the matrix tables
 
 // The K-quant kernels' table of `count` matrices, rows m[j] <= 0 left out; returns its half-tiles.  ids != nullptr: matrix j is
@@ -318,9 +356,41 @@ static int fill_mats(gemv_mats &mats, int count, const void *const *A, const lon
 // `count` matrices (<= GEMV_MAX_MATS for the K-quants, any number for Q8_0) of the same type and k share B.
 extern "C" hipError_t lfamd_launch_gemv_multi(int Atype, int count, const void *const *A, const long *m, long k, int Btype,
                                               const void *B, size_t b_row_bytes, long n, float *const *C, const long *ldc,
-                                              int vregs32, int precise, hipStream_t s) {
+                                              int vregs32, int precise, int relaxed, hipStream_t s) {
     if (count <= 0 || n <= 0)
         return hipSuccess;
+    if (relaxed && Atype == LFAMD_TYPE_Q8_0 && lfamd_gemv_q80_relaxed_cols(k) > 0) {
+        // relaxed order: the 8-row groups of up to four matrices concatenated, one item each (no padding between matrices)
+        const int rstep = lfamd_gemv_q80_relaxed_cols(k), f32in = Btype == LFAMD_TYPE_F32, cus = lfamd_num_cus();
+        hipError_t e = hipSuccess;
+        for (int j0 = 0; j0 < count && e == hipSuccess; j0 += GEMV_MAX_MATS) {
+            q80_mats qm;
+            long rgs = 0;
+            qm.count = 0;
+            for (int j = j0; j < count && j < j0 + GEMV_MAX_MATS; j++) {
+                if (m[j] <= 0)
+                    continue;
+                const int i = qm.count++;
+                qm.A[i] = (const uint8_t *)A[j], qm.C[i] = C[j], qm.m[i] = m[j], qm.ldc[i] = ldc[j];
+                rgs += (m[j] + 7) / 8;
+                qm.rg_end[i] = rgs;
+            }
+            if (qm.count == 0)
+                continue;
+            if (rgs > 0x7fffffffL)
+                return hipErrorInvalidValue;
+            for (int i = qm.count; i < GEMV_MAX_MATS; i++)
+                qm.A[i] = qm.A[0], qm.C[i] = qm.C[0], qm.m[i] = 0, qm.ldc[i] = 0, qm.rg_end[i] = rgs;
+            for (long col0 = 0; col0 < n && e == hipSuccess; col0 += rstep) {
+                const int nc = (int)((n - col0) < rstep ? (n - col0) : rstep);
+                lfamd_gemv_plan p;
+                if (lfamd_gemv_plan_of(LFAMD_GEMV_MULTI_RELAXED, Atype, nc, rgs, 0, k, qm.count, cus, &p) != 0)
+                    return hipErrorInvalidValue;
+                e = launch_q80r(kernel_of(Atype, f32in, p, 0), p, B, b_row_bytes, col0, k, (int)rgs, qm, s);
+            }
+        }
+        return e;
+    }
     const int step = lfamd_gemv_cols_per_launch(Atype, k);
     if (step == 0)
         return hipErrorInvalidValue;
@@ -431,7 +501,7 @@ extern "C" hipError_t lfamd_launch_gemv_ids_pair(int Atype, const void *W, long 
 }
 
 extern "C" hipError_t lfamd_launch_gemv(int Atype, const void *A, long m, long k, int Btype, const void *B,
-                                        size_t b_row_bytes, long n, float *C, long ldc, int vregs32, int precise,
+                                        size_t b_row_bytes, long n, float *C, long ldc, int vregs32, int precise, int relaxed,
                                         hipStream_t s) {
-    return lfamd_launch_gemv_multi(Atype, 1, &A, &m, k, Btype, B, b_row_bytes, n, &C, &ldc, vregs32, precise, s);
+    return lfamd_launch_gemv_multi(Atype, 1, &A, &m, k, Btype, B, b_row_bytes, n, &C, &ldc, vregs32, precise, relaxed, s);
 }

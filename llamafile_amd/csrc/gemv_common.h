@@ -12,6 +12,51 @@ __device__ static inline void load_piece(float (&v)[16], const float *x, int p) 
     }
 }
 
+// The Q8_0 decode kernels' LDS image of the activations (X80_QUAD per quad, gemv_launch.h), written by both of them
+// (gemv_q80_impl.h, gemv_q80r_impl.h) through the two functions below, so the quantiser exists once.
+//
+// Piece p (16 floats, the lane pair (2i, 2i + 1) makes a 32-block; both lanes of a pair must call) of column c's f32 row, quantised
+// like quantize_row_q8_0 (upstream): d = amax / 127, id = 1 / d, q = roundf(x * id), d stored as f16.
+__device__ __forceinline__ void x80_quantise_piece(uint8_t *lds, int nquads, const float (&v)[16], int c, int p) {
+    float amax = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; e++)
+        amax = fmaxf(amax, fabsf(v[e]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    const float d = amax / 127.0f;
+    const float id = d != 0.0f ? 1.0f / d : 0.0f;
+    uint32_t y[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        int q = (int)roundf(v[e] * id);
+        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
+    }
+    const int l = p >> 1, hf = p & 1;
+    uint8_t *dst = lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+        *(uint32_t *)(dst + (4 * hf + e) * 16) = y[e];
+    if (hf == 0)
+        *(float *)(dst + X80_QD) = h2f(f2h_bits(d)); // the block stores d as f16
+}
+// Q8_0 rows of columns col0 .. col0 + nc - 1, copied by the nthr threads of the work-group (eight code dwords and the scale per block).
+__device__ __forceinline__ void x80_copy_blocks(uint8_t *lds, int nquads, const uint8_t *__restrict__ B, size_t b_row_bytes, long col0, int nc,
+                                                int nblocks, int nthr) {
+    for (int idx = threadIdx.x; idx < nc * nblocks * 9; idx += nthr) {
+        int c = idx / (nblocks * 9), rem = idx % (nblocks * 9);
+        int l = rem / 9, w = rem % 9;
+        const uint8_t *y = B + (col0 + c) * b_row_bytes + (size_t)l * 34;
+        uint32_t v;
+        if (w < 8) {
+            const uint16_t *p = (const uint16_t *)(y + 2 + 4 * w); // 34-byte blocks: 2-byte aligned
+            v = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
+        } else {
+            v = __builtin_bit_cast(uint32_t, h2f(*(const uint16_t *)y));
+        }
+        *(uint32_t *)(lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4 + (w < 8 ? w * 16 : X80_QD)) = v;
+    }
+}
+
 #ifndef GEMV_DIAG
 #define GEMV_DIAG 0
 #endif

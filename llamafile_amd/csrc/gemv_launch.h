@@ -1,6 +1,6 @@
 // gemv_launch.h — what the decode GEMV's dispatcher (gemv.hip) and its kernel units (gemv_<type>.hip) share: the by-value
 // matrix tables of the kernels' arguments, the byte layout of their LDS, and the prototype of each unit's kernel lookup.
-// No kernel text (gemv_common.h, gemv_impl.h, gemv_q80_impl.h) and no launch policy (gemv.hip: lfamd_gemv_plan_of).
+// No kernel text (gemv_common.h, gemv_impl.h, gemv_q80_impl.h, gemv_q80r_impl.h) and no launch policy (gemv.hip: lfamd_gemv_plan_of).
 #pragma once
 #include "../../include/lfamd_blocks.h"
 #include "lfamd_internal.h"
@@ -42,6 +42,23 @@ constexpr int q80_quads(long k) {
 }
 constexpr size_t q80_lds_bytes(int nc, int nquads) {
     return (size_t)nc * nquads * X80_QUAD;
+}
+
+// The relaxed-order Q8_0 GEMV (gemv_q80r_impl.h; LFAMD_FLAG_Q80_RELAXED): the same image [nc][nquads] X80_QUAD, then one quad of
+// zeros at `dummy` (what a wave reads for a quad past the row's last), then the two reduction buffers f32 [2][nw][nc][8] at `red`.
+// The plan sizes the launch with it and the kernel takes its offsets from it.
+#define Q80R_WAVES 16 // waves per work-group: K is split over them
+struct q80r_lds {
+    size_t dummy, red, bytes;
+};
+constexpr q80r_lds q80r_lds_of(int nc, int nquads, int nw) {
+    const size_t dummy = (size_t)nc * nquads * X80_QUAD, red = dummy + X80_QUAD;
+    return {dummy, red, red + 2 * (size_t)nw * nc * 8 * sizeof(float)};
+}
+// quads of one wave that are in flight together (a chunk): the wave's share of the row up to 4, deeper rows in chunks of 4
+constexpr int q80r_chunk_quads(int nquads) {
+    const int qpw = (nquads + Q80R_WAVES - 1) / Q80R_WAVES;
+    return qpw <= 1 ? 1 : qpw <= 2 ? 2 : 4;
 }
 
 // Up to GEMV_MAX_MATS weight matrices of one type and row length that consume the SAME activations
@@ -90,3 +107,6 @@ gemv_kernel_fn lfamd_gemv_kernel_q4k, lfamd_gemv_kernel_q5k, lfamd_gemv_kernel_q
 // Q8_0 (gemv_q80.hip: f32 activations, gemv_q80b.hip: Q8_0 blocks); mode = the summation form, see gemv_q80_kernel
 const void *lfamd_gemv_kernel_q80_f32(int nc, int mode);
 const void *lfamd_gemv_kernel_q80_q80(int nc, int mode);
+// Q8_0, relaxed order (gemv_q80r.hip: f32 activations, gemv_q80rb.hip: Q8_0 blocks); (nc, nw, ch) of the plan
+const void *lfamd_gemv_kernel_q80r_f32(int nc, int nw, int ch);
+const void *lfamd_gemv_kernel_q80r_q80(int nc, int nw, int ch);

@@ -67,9 +67,9 @@ __global__ __launch_bounds__(Q80_WAVES * 64) void gemv_q80_kernel(const uint8_t 
     };
 
     if constexpr (BT == LFAMD_TYPE_F32) {
-        // quantize_row_q8_0 (upstream): d = amax/127, id = 1/d, q = roundf(x*id); 16 floats per lane,
-        // two lanes per 32-block.  The first piece of each thread is fetched BEFORE the weights (vmcnt
-        // retires in order), the weights are issued, then the activations are quantised under their flight.
+        // quantize_row_q8_0 (x80_quantise_piece, gemv_common.h): 16 floats per lane, two lanes per 32-block.
+        // The first piece of each thread is fetched BEFORE the weights (vmcnt retires in order), the weights
+        // are issued, then the activations are quantised under their flight.
         const int pieces = nblocks * 2, nthr = Q80_WAVES * 64;
         for (int c = 0; c < NC; c++) {
             const float *x = (const float *)(B + (col0 + c) * b_row_bytes);
@@ -92,52 +92,18 @@ __global__ __launch_bounds__(Q80_WAVES * 64) void gemv_q80_kernel(const uint8_t 
                     for (int s = 0; s < Q80_DEPTH; s++)
                         issue(s, s);
                 }
-                auto quantise = [&](const float (&v)[16], int p) {
-                    float amax = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < 16; e++)
-                        amax = fmaxf(amax, fabsf(v[e]));
-                    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-                    const float d = amax / 127.0f;
-                    const float id = d != 0.0f ? 1.0f / d : 0.0f;
-                    uint32_t y[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int e = 0; e < 16; e++) {
-                        int q = (int)roundf(v[e] * id);
-                        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-                    }
-                    const int l = p >> 1, hf = p & 1;
-                    uint8_t *dst = lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4;
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-                        *(uint32_t *)(dst + (4 * hf + e) * 16) = y[e];
-                    if (hf == 0)
-                        *(float *)(dst + X80_QD) = h2f(f2h_bits(d)); // the block stores d as f16
-                };
                 // (pieces is even and nthr a multiple of 64: the lane pair (2i, 2i+1) of a block is either both in or out)
                 if (pa < pieces)
-                    quantise(va, pa);
+                    x80_quantise_piece(lds, nquads, va, c, pa);
                 if (pb < pieces)
-                    quantise(vb, pb);
+                    x80_quantise_piece(lds, nquads, vb, c, pb);
             }
         }
     } else {
 #pragma unroll
         for (int s = 0; s < Q80_DEPTH; s++)
             issue(s, s);
-        for (int idx = threadIdx.x; idx < NC * nblocks * 9; idx += Q80_WAVES * 64) {
-            int c = idx / (nblocks * 9), rem = idx % (nblocks * 9);
-            int l = rem / 9, w = rem % 9;
-            const uint8_t *y = B + (col0 + c) * b_row_bytes + (size_t)l * 34;
-            uint32_t v;
-            if (w < 8) {
-                const uint16_t *p = (const uint16_t *)(y + 2 + 4 * w); // 34-byte blocks: 2-byte aligned
-                v = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-            } else {
-                v = __builtin_bit_cast(uint32_t, h2f(*(const uint16_t *)y));
-            }
-            *(uint32_t *)(lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4 + (w < 8 ? w * 16 : X80_QD)) = v;
-        }
+        x80_copy_blocks(lds, nquads, B, b_row_bytes, col0, NC, nblocks, Q80_WAVES * 64);
     }
     GSTAMP();
     __syncthreads();

@@ -55,6 +55,13 @@ void logf(const char *fmt, const char *a = "", const char *b = "") {
     fprintf(stderr, fmt, a, b);
 }
 
+// What every mat-mul of the glue carries: the reference's AVX512 build of tinyBLAS_Q0, and — LFAMD_Q80_RELAXED=1 in the environment,
+// read once — the relaxed-order Q8_0 decode GEMV (lfamd_hip.h: LFAMD_FLAG_Q80_RELAXED; exact_only matrices override it).
+unsigned base_flags() {
+    static const unsigned relaxed = getenv("LFAMD_Q80_RELAXED") && atoi(getenv("LFAMD_Q80_RELAXED")) ? LFAMD_FLAG_Q80_RELAXED : 0u;
+    return LFAMD_FLAG_Q0_VREGS32 | relaxed;
+}
+
 struct type_row {
     int id;
     const char *name;
@@ -535,7 +542,7 @@ enum ggml_status run_mul_mat_split(backend_ctx *ctx, struct ggml_tensor *dst) {
                 if (!grow(ws, ws_cap, lfamd_mul_mat_workspace(a->type, rows, k, n)))
                     return GGML_STATUS_ALLOC_FAILED;
                 if (lfamd_mul_mat(a->type, w->d, rows, k, LFAMD_TYPE_F32, B, brb, n, C, c_ld, ws, ws_cap,
-                                  (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | LFAMD_FLAG_Q0_VREGS32, nullptr) != LFAMD_OK) {
+                                  (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | base_flags(), nullptr) != LFAMD_OK) {
                     logf("%s: lfamd_mul_mat (row slice): %s\n", "ggml_backend_lfamd", lfamd_last_error());
                     return GGML_STATUS_FAILED;
                 }
@@ -583,7 +590,7 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
             const uint8_t *bp = (const uint8_t *)b->data + i12 * b->nb[2] + i13 * b->nb[3];
             float *cp = (float *)((uint8_t *)dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]);
             if (lfamd_mul_mat(a->type, w->d, m, k, LFAMD_TYPE_F32, bp, b->nb[1], n, cp, (long)(dst->nb[1] / sizeof(float)), ctx->ws,
-                              ctx->ws_cap, (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | LFAMD_FLAG_Q0_VREGS32, nullptr) != LFAMD_OK) {
+                              ctx->ws_cap, (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | base_flags(), nullptr) != LFAMD_OK) {
                 logf("%s: lfamd_mul_mat: %s\n", "ggml_backend_lfamd", lfamd_last_error());
                 return GGML_STATUS_FAILED;
             }
@@ -661,7 +668,7 @@ enum ggml_status run_mul_mat_id(backend_ctx *ctx, struct ggml_tensor *const *dst
     std::lock_guard<std::mutex> lk(g_mu);
     const void *wp[4];
     float *rp[4];
-    unsigned flags = LFAMD_FLAG_Q0_VREGS32;
+    unsigned flags = base_flags();
     for (int j = 0; j < count; j++) {
         packed tmp;
         const packed *w = get_packed_stack(ctx, dsts[j]->src[0], &tmp);
@@ -745,7 +752,7 @@ enum ggml_status run_mul_mat_siblings(backend_ctx *ctx, struct ggml_tensor *cons
     long m[4], ldc[4];
     float *C[4];
     size_t wsb = 0;
-    unsigned flags = LFAMD_FLAG_Q0_VREGS32;
+    unsigned flags = base_flags();
     std::lock_guard<std::mutex> lk(g_mu);
     for (int j = 0; j < count; j++) {
         const struct ggml_tensor *a = dsts[j]->src[0];

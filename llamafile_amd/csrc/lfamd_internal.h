@@ -7,7 +7,7 @@
 #include <stdint.h>
 
 // A planned decode GEMV launch.  kind = the entry point that asks, variant = the kernel form it gets.
-enum { LFAMD_GEMV_MULTI, LFAMD_GEMV_IDS, LFAMD_GEMV_IDS_PAIR, LFAMD_GEMV_DUAL };
+enum { LFAMD_GEMV_MULTI, LFAMD_GEMV_IDS, LFAMD_GEMV_IDS_PAIR, LFAMD_GEMV_DUAL, LFAMD_GEMV_MULTI_RELAXED }; // (_RELAXED: Q8_0 under LFAMD_FLAG_Q80_RELAXED)
 enum {
     LFAMD_GEMV_PLAIN,       // gemv_kq_kernel
     LFAMD_GEMV_EARLY,       // ... one matrix, one column: first weight loads from the preloaded arguments
@@ -15,12 +15,13 @@ enum {
     LFAMD_GEMV_EXPERT,      // ... expert picked on the device (MUL_MAT_ID)
     LFAMD_GEMV_EXPERT_PAIR, // gemv_kq_ids_pair_kernel: two experts, two activation rows, two sub-grids
     LFAMD_GEMV_TWO_TYPES,   // gemv_kq_dual_kernel: {Q4_K | Q5_K} and Q6_K matrices, two sub-grids
-    LFAMD_GEMV_Q80          // gemv_q80_kernel
+    LFAMD_GEMV_Q80,         // gemv_q80_kernel
+    LFAMD_GEMV_Q80R         // gemv_q80r_kernel: Q8_0 with K split over the waves, this module's own summation order
 };
 struct lfamd_gemv_plan {
-    int variant, nc, nw, ch; // columns, waves per work-group, super-blocks per chunk (Q8_0: ch = 0)
+    int variant, nc, nw, ch; // columns, waves per work-group, super-blocks per chunk (Q8_0: ch = 0; Q80R: quads per chunk)
     int grid, grid_b;        // work-groups; grid_b: the second sub-grid of the two split launches, else 0
-    int rows;                // result rows per item (16, ROWS32: 32; Q8_0: 8 per wave)
+    int rows;                // result rows per item (16, ROWS32: 32; Q8_0: 8 per wave; Q80R: 8)
     int lds;                 // dynamic LDS bytes
 };
 
@@ -58,9 +59,10 @@ hipError_t lfamd_launch_prep_float(int, int, const void *, size_t, long, long, l
 hipError_t lfamd_launch_rows_to_16(int, const void *, size_t, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_q80_rows_to_f16(int, const void *, size_t, long, long, void *, hipStream_t);
 // decode GEMVs (gemv.hip, gemv_float.hip)
-hipError_t lfamd_launch_gemv(int, const void *, long, long, int, const void *, size_t, long, float *, long, int, int, hipStream_t);
+// (the three ints before the stream: Q0_VREGS32, PRECISE, and `relaxed` = Q8_0 may run the relaxed-order kernel where its plan accepts)
+hipError_t lfamd_launch_gemv(int, const void *, long, long, int, const void *, size_t, long, float *, long, int, int, int, hipStream_t);
 hipError_t lfamd_launch_gemv_multi(int, int, const void *const *, const long *, long, int, const void *, size_t, long, float *const *, const long *,
-                                   int, int, hipStream_t);
+                                   int, int, int, hipStream_t);
 hipError_t lfamd_launch_gemv_dual(int, int, const void *const *, const long *, float *const *, const long *, int, int, const void *const *,
                                   const long *, float *const *, const long *, long, int, const void *, size_t, hipStream_t);
 hipError_t lfamd_launch_gemv_ids(int, int, const void *const *, long, int, const int32_t *, const int *, long, long, int, const void *, size_t,
@@ -74,6 +76,8 @@ int lfamd_gemv_cols_per_launch(int, long);        // (Atype, k): activation colu
 size_t lfamd_gemv_lds_bytes(int, int, long, int, int); // (Atype, nc, k, nw, rows per item): the LDS layout's total
 int lfamd_gemv_plan_of(int, int, int, long, long, long, int, int, struct lfamd_gemv_plan *);
 int lfamd_gemv_has_kernel(int, int, const struct lfamd_gemv_plan *); // (Atype, f32in, plan): the type's unit instantiates it
+int lfamd_gemv_q80_relaxed_cols(long); // (k): columns one launch of the relaxed-order Q8_0 kernel takes, 0 = it declines the row
+size_t lfamd_gemv_q80_relaxed_lds_bytes(int, long); // (nc, k): that kernel's LDS layout's total
 int lfamd_gemv_float_ok(int, long, long);
 hipError_t lfamd_launch_gemv_float(int, const void *, long, long, int, const void *, size_t, long, float *, long, hipStream_t);
 // batch bodies (gemm_*.hip, generic.hip)

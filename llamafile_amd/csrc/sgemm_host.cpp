@@ -188,6 +188,9 @@ void load_module() {
     if (const char *e = getenv("LFAMD_Q80_EXACT")) // Q8_0 batches bit for bit like tinyBLAS_Q0 (default: library f16 GEMM, <= 1e-3; MFMA body, 2e-6, where hipBLASLt does not load)
         if (atoi(e))
             g.flags |= LFAMD_FLAG_Q80_EXACT;
+    if (const char *e = getenv("LFAMD_Q80_RELAXED")) // Q8_0 decode (n <= 8) on the relaxed-order GEMV: deterministic, within 2e-6, not the CPU chain's bits
+        if (atoi(e))
+            g.flags |= LFAMD_FLAG_Q80_RELAXED;
     g.ok = true;
     g.error.clear();
 }
