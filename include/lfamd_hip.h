@@ -25,6 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lfamd_blocks.h" /* the LFAMD_TYPE_* ids */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -44,8 +46,9 @@ enum lfamd_status {
                                     tinyBLAS_Q0: Kahan on 2x1/1x2/1x1 edge tiles (tinyblas_cpu.h:797-830) */
 #define LFAMD_FLAG_PRECISE 2u    /* FLAG_precise (--precise): Kahan everywhere in the Q0 kernels */
 #define LFAMD_FLAG_FORCE_GENERIC 4u /* debugging: the generic one-wave-per-row kernel — only for tensors kept as GGUF rows
-                                       (floats, legacy 32-block rows that are not whole 256-weight groups); packed types
-                                       answer LFAMD_ERR_UNSUPPORTED */
+                                       (floats, legacy 32-block rows that are not whole 256-weight groups: RAW rows, unless the
+                                       caller asked for the padded image, LFAMD_TYPE_PAD256); packed types answer
+                                       LFAMD_ERR_UNSUPPORTED */
 #define LFAMD_FLAG_GEMM_NARROW 8u   /* testing: force the 128x64 split-K MFMA body (default: chosen by grid size) */
 #define LFAMD_FLAG_GEMM_WIDE 16u    /* testing: force the 128x128 MFMA body */
 #define LFAMD_FLAG_GEMM_PLAIN 32u   /* testing: the 128x128 body without loader waves (Q4_K / Q5_K default to them) */
@@ -334,6 +337,33 @@ int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned f
 #define LFAMD_TYPE_STAGED_Q80 0x1003
 size_t lfamd_staged_q80_size(long k, long nrows);
 int lfamd_mul_mat_takes_staged_q80(int Atype, long m, long k, long n, unsigned flags);
+
+/* A layout modifier of the WEIGHT type, OR-ed into the type of any call that takes one: LFAMD_TYPE_Q4_0 | LFAMD_TYPE_PAD256 means "Q4_0
+ * weights, resident as the tile image with the last super-block padded".  The legacy 32-block types (Q4_0, IQ4_NL, Q4_1, Q5_0, Q5_1)
+ * reach the tuned kernels only as the tile image of rows of whole 256-weight groups; their unmodified ids keep any other row length as
+ * GGUF rows on the generic kernels.  With the modifier, and cols % 32 == 0, the resident image is the P40 (Q4_0, IQ4_NL) / PCL (Q4_1,
+ * Q5_0, Q5_1) image of a matrix of kp = 256 * ceil(cols / 256) columns, as if every GGUF row continued with all-zero-byte blocks
+ * (d = +0, m = +0, quants and fifth bits 0):
+ *   - lfamd_packed_size(T | PAD256, rows, cols) == lfamd_packed_size(T, rows, kp); lfamd_pack_weights reads cols / 32 blocks per raw
+ *     row and writes the zero tail itself; lfamd_unpack_weights and lfamd_get_rows read back `cols` columns, bit for bit, and touch
+ *     nothing beyond them;
+ *   - the mat-mul calls (lfamd_mul_mat, _multi, _multi_types, lfamd_mul_mat_id(_multi), lfamd_time_mul_mat) and their queries
+ *     (_workspace(_upto), _is_exact, _is_bit_exact) take the route the base type takes at k = kp and answer as it does there: the
+ *     decode GEMV up to 8 columns (siblings in one launch), the 128 x 128 MFMA body beyond, exact.  The ACTIVATIONS keep their true
+ *     length: f32 rows of k floats or k / 32 Q8_0 / Q8_1 blocks, b_row_bytes checked against k; nothing behind a row's k values is read;
+ *   - LFAMD_FLAG_FORCE_GENERIC is refused, as on any packed image; the lfamd_mul_mat_takes_staged_* answer 0 where k % 256 != 0 (the
+ *     fused producers write rows of whole groups only);
+ *   - where cols % 256 == 0 the modifier changes nothing: same size, same bytes, same routes, same results to the bit.
+ * On any other base type the modified id is unknown: lfamd_packed_size answers 0, every other call LFAMD_ERR_UNSUPPORTED. */
+#define LFAMD_TYPE_PAD256 0x2000
+/* The id a caller that packs its own resident copy of a `type` tensor of row length `cols` should use for every size, pack, unpack
+ * and mat-mul call on that copy: type | LFAMD_TYPE_PAD256 where that moves the tensor from the generic kernels to the tuned ones (the
+ * five types above, rows of whole 32-blocks that are not whole 256-weight groups), else the type unchanged. */
+static inline int lfamd_resident_type(int type, long cols) {
+    const int pads = type == LFAMD_TYPE_Q4_0 || type == LFAMD_TYPE_Q4_1 || type == LFAMD_TYPE_Q5_0 || type == LFAMD_TYPE_Q5_1 ||
+                     type == LFAMD_TYPE_IQ4_NL;
+    return pads && cols % 256 != 0 && cols % 32 == 0 ? type | LFAMD_TYPE_PAD256 : type;
+}
 
 /* ---- the step in front of the path, fused: RMS-norm x weight -> Q8_K -----------------------------
  * y[i] = (x[i] * 1/sqrtf(mean(x^2) + eps)) * weight[i] per row (ggml_compute_forward_rms_norm_f32 + the MUL node; GPU

@@ -25,6 +25,7 @@ TYPE_STAGED_Q8K = 0x1000  # the int8 batch body's staged activation image (lfamd
 TYPE_STAGED_SCALED = 0x1001  # the scaled-operand f16 batch bodies' staged activation image
 TYPE_STAGED_B32 = 0x1002  # the 32-block batch bodies' staged activation image (Q8_0 / Q8_1-quantised activations)
 TYPE_STAGED_Q80 = 0x1003  # the Q8_0-weight loader-wave batch body's staged activation image
+TYPE_PAD256 = 0x2000  # layout modifier OR-ed into a legacy 32-block weight type: the tile image with the last super-block padded
 
 
 class LfamdError(RuntimeError):

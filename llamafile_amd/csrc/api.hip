@@ -112,7 +112,24 @@ int lfamd_stream_sync(void *stream) {
 
 // ---------------------------------------------------------------------------------------------
 
+// LFAMD_TYPE_PAD256 (include/lfamd_hip.h): a layout modifier OR-ed into a legacy 32-block weight type.  This file is where it ends:
+// the launchers below it get the base type, the weight geometry (image_cols: the columns of the resident image) and the activation
+// length (the call's own k) as separate values.
+static int base_of(int t) {
+    return t & ~LFAMD_TYPE_PAD256;
+}
+static bool padded_id(int t) {
+    return (t & LFAMD_TYPE_PAD256) != 0;
+}
+static long image_cols(int t, long k) {
+    return padded_id(t) ? (k + 255) / 256 * 256 : k;
+}
+
 static bool type_known(int t) {
+    if (padded_id(t)) { // the types with a tile image to pad; on any other the modifier makes an unknown id
+        const int b = base_of(t);
+        return b == LFAMD_TYPE_Q4_0 || b == LFAMD_TYPE_IQ4_NL || b == LFAMD_TYPE_Q4_1 || b == LFAMD_TYPE_Q5_0 || b == LFAMD_TYPE_Q5_1;
+    }
     switch (t) {
     case LFAMD_TYPE_F32:
     case LFAMD_TYPE_F16:
@@ -141,8 +158,10 @@ static size_t q80_p80_bytes(long rows, long cols) {
 }
 
 size_t lfamd_packed_size(int type, long rows, long cols) {
-    if (!type_known(type) || rows < 0 || cols < 0 || cols % lfamd_blck_size(type))
+    if (!type_known(type) || rows < 0 || cols < 0 || cols % lfamd_blck_size(base_of(type)))
         return 0;
+    if (padded_id(type)) // the image of the rows continued with zero blocks to whole 256-weight groups
+        return lfamd_packed_size(base_of(type), rows, image_cols(type, cols));
     switch (type) {
     case LFAMD_TYPE_Q4_K:
         return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P4K_TILE;
@@ -183,6 +202,8 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
     if (!type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "pack_weights: unsupported ggml type%s", "");
+    const bool tiled = padded_id(type) || cols % 256 == 0; // (the 32-block types: the tile image; its launchers write a row's padded tail)
+    type = base_of(type);
     if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || raw_row_bytes < lfamd_row_size(type, cols))
         return fail(LFAMD_ERR_INVALID, "pack_weights: bad shape%s", "");
     if (rows == 0 || cols == 0)
@@ -194,7 +215,7 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
         break;
     case LFAMD_TYPE_Q4_0:
     case LFAMD_TYPE_IQ4_NL:
-        if (cols % 256 == 0) {
+        if (tiled) {
             HIPCHK(lfamd_launch_pack_q40(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q40");
         } else {
             HIPCHK(lfamd_launch_pack_raw(d_raw, raw_row_bytes, rows, lfamd_row_size(type, cols), d_packed, s), "pack_raw");
@@ -221,7 +242,7 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
     case LFAMD_TYPE_Q4_1:
     case LFAMD_TYPE_Q5_0:
     case LFAMD_TYPE_Q5_1:
-        if (cols % 256 == 0) {
+        if (tiled) {
             HIPCHK(lfamd_launch_wprep32(type, d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_pcl");
         } else {
             HIPCHK(lfamd_launch_pack_raw(d_raw, raw_row_bytes, rows, lfamd_row_size(type, cols), d_packed, s), "pack_raw");
@@ -240,6 +261,8 @@ int lfamd_get_rows(int type, const void *d_packed, long rows, long cols, const i
     (void)hipGetLastError(); // (as lfamd_pack_weights)
     if (!type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "get_rows: unsupported ggml type%s", "");
+    const int tiled = padded_id(type) ? 1 : 0;
+    type = base_of(type);
     if (out_type != LFAMD_TYPE_F32 && out_type != LFAMD_TYPE_F16)
         return fail(LFAMD_ERR_UNSUPPORTED, "get_rows: out_type must be F32 or F16%s", "");
     if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || n_ids < 0)
@@ -255,7 +278,7 @@ int lfamd_get_rows(int type, const void *d_packed, long rows, long cols, const i
         return fail(LFAMD_ERR_INVALID, "get_rows: null pointer%s", "");
     if ((uintptr_t)d_out % esz)
         return fail(LFAMD_ERR_INVALID, "get_rows: d_out %s", "not aligned to the element");
-    HIPCHK(lfamd_launch_get_rows(type, d_packed, rows, cols, d_ids, d_ids ? 0 : row0, n_ids, out_type, d_out, out_row_bytes, (hipStream_t)stream),
+    HIPCHK(lfamd_launch_get_rows(type, tiled, d_packed, rows, cols, d_ids, d_ids ? 0 : row0, n_ids, out_type, d_out, out_row_bytes, (hipStream_t)stream),
            "get_rows");
     return LFAMD_OK;
 }
@@ -264,13 +287,15 @@ int lfamd_unpack_weights(int type, long rows, long cols, const void *d_packed, v
     (void)hipGetLastError();
     if (!type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "unpack_weights: unsupported ggml type%s", "");
+    const int tiled = padded_id(type) ? 1 : 0;
+    type = base_of(type);
     if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || raw_row_bytes < lfamd_row_size(type, cols))
         return fail(LFAMD_ERR_INVALID, "unpack_weights: bad shape%s", "");
     if (rows == 0 || cols == 0)
         return LFAMD_OK;
     if (!d_packed || !d_raw)
         return fail(LFAMD_ERR_INVALID, "unpack_weights: null pointer%s", "");
-    HIPCHK(lfamd_launch_unpack(type, d_packed, rows, cols, d_raw, raw_row_bytes, (hipStream_t)stream), "unpack_weights");
+    HIPCHK(lfamd_launch_unpack(type, tiled, d_packed, rows, cols, d_raw, raw_row_bytes, (hipStream_t)stream), "unpack_weights");
     return LFAMD_OK;
 }
 
@@ -415,6 +440,8 @@ static bool q80_relaxed(int Atype, long k, long n, unsigned flags) {
 }
 
 static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
+    if (padded_id(Atype)) // the padded image: the route, the answers and the workspace of the base type on rows of whole groups
+        return plan_mul_mat(base_of(Atype), m, image_cols(Atype, k), n, flags);
     const unsigned forced = flags & (LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN); // (a module body, by name)
     const bool f16_q80 = !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT));
     mm_plan p = {mm_body::generic, false, true, false, false, 0};
@@ -542,6 +569,8 @@ int lfamd_mul_mat_takes_staged(int Atype, long m, long k, long n, unsigned flags
 int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned flags) {
     if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
+    if (image_cols(Atype, k) != k) // (the producers write rows of whole 256-weight groups)
+        return 0;
     const mm_body b = plan_mul_mat(Atype, m, k, n, flags).body;
     return b == mm_body::q40_wide || b == mm_body::canon32 ? 1 : 0;
 }
@@ -635,14 +664,14 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
                          size_t ws_bytes, unsigned flags, mm_plan &p) {
     if (!type_known(Atype))
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: unsupported weight type%s", "");
-    if (m < 0 || n < 0 || k < 0 || ldc < m || k % lfamd_blck_size(Atype))
+    if (m < 0 || n < 0 || k < 0 || ldc < m || k % lfamd_blck_size(base_of(Atype)))
         return fail(LFAMD_ERR_INVALID, "mul_mat: bad shape%s", "");
     const bool staged = staged_type(Btype);
     if (!staged) {
         if (float_type(Atype)) {
             if (!(Btype == LFAMD_TYPE_F32 || Btype == Atype))
                 return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: float weights need F32 or same-type activations%s", "");
-        } else if (Btype != lfamd_vec_dot_type(Atype) && Btype != LFAMD_TYPE_F32) {
+        } else if (Btype != lfamd_vec_dot_type(base_of(Atype)) && Btype != LFAMD_TYPE_F32) {
             // f32 activations (the GGML_OP_MUL_MAT boundary) are quantised on the device to the vec_dot type
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: activations must be F32 or the weight type's vec_dot format%s", "");
         }
@@ -665,7 +694,7 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
         need = lfamd_gemm_lw_ksplit_bytes(m, n); // partial tiles of a K-split launch: the only workspace left
         uses_ws = need != 0;
     } else if (Btype == LFAMD_TYPE_STAGED_B32) { // a fused producer wrote the 32-block bodies' staged image
-        if (p.body != mm_body::q40_wide && p.body != mm_body::canon32)
+        if ((p.body != mm_body::q40_wide && p.body != mm_body::canon32) || image_cols(Atype, k) != k)
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run a 32-block batch body (lfamd_mul_mat_takes_staged_b32)%s", "");
         if (!d_B || !aligned16(d_B))
             return fail(LFAMD_ERR_INVALID, "mul_mat: the staged image must be 16-byte aligned%s", "");
@@ -700,10 +729,14 @@ static int prep_kq(int Btype, const void *d_B, size_t b_row_bytes, long n, long 
 
 static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, long k, int Btype, const void *d_B, size_t b_row_bytes,
                           long n, float *d_C, long ldc, void *d_ws, size_t ws_bytes, unsigned flags, hipStream_t s) {
+    // A padded image (LFAMD_TYPE_PAD256): the weights and the staged image have kw columns, the activation rows k.  Only the bodies of
+    // the 32-block types see kw != k: the decode GEMV and prep80 take k and pad what they stage, gemm_wide reads whole super-blocks.
+    const long kw = image_cols(Atype, k);
+    Atype = base_of(Atype);
     const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
     const int vregs32 = (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0, precise = (flags & LFAMD_FLAG_PRECISE) ? 1 : 0;
     const int vdt = lfamd_vec_dot_type(Atype);
-    const lfamd_kq_image im = lfamd_kq_image_of(k, n);
+    const lfamd_kq_image im = lfamd_kq_image_of(kw, n);
     const size_t n_pad = im.n_pad;
     uint8_t *ws = (uint8_t *)d_ws; // the staging layout of the K-quant batch bodies: Xh, d8T, Xm
     void *Xh = ws, *d8T = ws + im.d8T, *Xm = ws + im.Xm;
@@ -738,7 +771,7 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
         return LFAMD_OK;
     case mm_body::q40_wide: // Q8_0-quantised activations, eight scales per 256 (they take the Xm area too)
         HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, d8T, nullptr, s), "prep80");
-        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, d8T, nullptr, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, kw, Xh, d8T, nullptr, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
         return LFAMD_OK;
     case mm_body::kq_narrow:
     case mm_body::wide: {
@@ -755,10 +788,10 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
         return LFAMD_OK;
     }
     case mm_body::canon32: {
-        const lfamd_b32_image b32 = lfamd_b32_image_of(k, n);
+        const lfamd_b32_image b32 = lfamd_b32_image_of(kw, n);
         void *sT = vdt == LFAMD_TYPE_Q8_1 ? ws + b32.sT : nullptr;
         HIPCHK(lfamd_launch_prep80(Btype, d_B, b_row_bytes, n, (long)n_pad, k, Xh, ws + b32.d8T, sT, s), "prep80");
-        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, k, Xh, ws + b32.d8T, sT, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
+        HIPCHK(lfamd_launch_gemm_wide(Atype, d_A, m, kw, Xh, ws + b32.d8T, sT, n, (long)n_pad, d_C, ldc, plain, nullptr, 0, s), "gemm_wide");
         return LFAMD_OK;
     }
     case mm_body::canon: {
@@ -919,6 +952,8 @@ struct mm_group_plan {
 // The route of sibling matrices of one type (a lfamd_mul_mat_multi call, or one run of a lfamd_mul_mat_multi_types call).
 static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int Btype, size_t b_row_bytes, long n, const long *ldc,
                                 unsigned flags) {
+    const long kw = image_cols(Atype, k); // a padded image: the base type's route at kw weight columns, activation rows of k
+    Atype = base_of(Atype);
     mm_group_plan g = {mm_route::each, count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags), 0, {}, {}, false};
     if (count <= 0 || (staged_type(Btype) && n == 0))
         g.route = mm_route::none;
@@ -943,8 +978,8 @@ static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int
         for (int j = 0; j < count && all_sb; j++) // (small siblings — attn_k / attn_v — are faster on the fused GEMV below 8 tokens)
             all_sb = (m[j] > 8192 || (i8_body && n >= 8)) && ldc[j] >= m[j] && sb_takes(Atype, m[j], k, n, flags);
         // one fused launch when the GEMV path applies to every matrix
-        const bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && packed(Atype, k) && rows_ok && k > 0 &&
-                          k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || k % 256 == 0) && group_row_blocks(count, m, ldc) >= 0;
+        const bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && packed(Atype, kw) && rows_ok && k > 0 &&
+                          k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || kw % 256 == 0) && group_row_blocks(count, m, ldc) >= 0;
         const bool q80_lf = count > 1 && count <= 4 && Atype == LFAMD_TYPE_Q8_0 && k > 0 && rows_ok &&
                             plan_mul_mat(Atype, m[0], k, n, flags).body == mm_body::q80_lf && group_row_blocks(count, m, ldc) >= 0;
         if (all_sb)
@@ -1020,7 +1055,7 @@ static int launch_group(const mm_group_plan &g, int Atype, int count, const void
             HIPCHK(lfamd_launch_gemm_sb(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, j > 0, s), "gemm_sb (multi)");
         return LFAMD_OK;
     case mm_route::gemv_multi:
-        HIPCHK(lfamd_launch_gemv_multi(Atype, count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0,
+        HIPCHK(lfamd_launch_gemv_multi(base_of(Atype), count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0,
                                        (flags & LFAMD_FLAG_PRECISE) ? 1 : 0, g.relaxed ? 1 : 0, s),
                "gemv_multi");
         return LFAMD_OK;
@@ -1054,6 +1089,8 @@ int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long
                         size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
                         unsigned flags, void *stream) {
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
+    if (count > 0 && !type_known(Atype)) // (plan_group strips the layout modifier: an unknown id must not be planned as its base type)
+        return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: unsupported weight type%s", "");
     const mm_group_plan g = plan_group(Atype, count, m, k, Btype, b_row_bytes, n, ldc, flags);
     int r = check_group(g, Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags);
     if (r == LFAMD_OK && g.route != mm_route::none && n > 0) {
@@ -1135,6 +1172,9 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
         return LFAMD_OK;
     if (!Atype || !d_A || !m || !d_C || !ldc)
         return fail(LFAMD_ERR_INVALID, "mul_mat_multi_types: null argument%s", "");
+    for (int j = 0; j < count; j++)
+        if (!type_known(Atype[j]))
+            return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: unsupported weight type%s", "");
     if (Btype == LFAMD_TYPE_STAGED_B32 || Btype == LFAMD_TYPE_STAGED_Q80)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: the 32-block staged images are taken by lfamd_mul_mat / lfamd_mul_mat_multi%s", "");
     const mm_group_plan p = plan_types(count, Atype, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, d_ws, ws_bytes, flags);
@@ -1198,7 +1238,7 @@ int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int expert
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
     if (!type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_id: unsupported weight type%s", "");
-    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || experts <= 0 || tasks <= 0 || thinkers <= 0 ||
+    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(base_of(type)) || experts <= 0 || tasks <= 0 || thinkers <= 0 ||
         tasks > thinkers || thinkers > experts)
         return fail(LFAMD_ERR_INVALID, "mul_mat_id: bad shape%s", "");
     // f32 activations (the GGML_OP_MUL_MAT_ID boundary) are served by the decode path, which quantises in-kernel
@@ -1206,7 +1246,7 @@ int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int expert
                             ((tokens <= 4 && (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K)) ||
                              (tokens > 4 && cols % 256 == 0 && experts < 255 && tokens * thinkers <= 60 * 1024 &&
                               (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K)));
-    if (Btype != lfamd_vec_dot_type(type) && !f32_decode)
+    if (Btype != lfamd_vec_dot_type(base_of(type)) && !f32_decode)
         return fail(LFAMD_ERR_UNSUPPORTED,
                     "mul_mat_id: activations must be in the weight type's vec_dot format (F32 only for Q4_K / Q5_K / Q6_K experts)%s", "");
     if (tokens == 0 || rows == 0)

@@ -473,8 +473,9 @@ __global__ __launch_bounds__(256) void unpack_raw_kernel(const uint8_t *__restri
 
 // ---------------------------------------------------------------------------------------------
 
-static int layout_of(int type, long cols) {
-    const bool g256 = cols % 256 == 0;
+// (tiled: the caller keeps the legacy 32-block rows as the tile image whatever their length, LFAMD_TYPE_PAD256)
+static int layout_of(int type, long cols, int tiled) {
+    const bool g256 = cols % 256 == 0 || tiled;
     switch (type) {
     case LFAMD_TYPE_Q4_K:
         return LY_P4K;
@@ -517,9 +518,11 @@ static int rows_per_group(const int32_t *ids, long n_ids) {
     return !ids && n_ids >= 32 ? 32 : 4;
 }
 
-extern "C" hipError_t lfamd_launch_get_rows(int type, const void *img, long rows, long cols, const int32_t *ids, long row0, long n_ids,
+// cols: the columns read back.  tiled: a 32-block type's image is the tile image of ceil(cols / 256) super-blocks per row whose last one
+// is padded with zero blocks; the kernels' column guards stop at cols, so nothing of the padding is written out.
+extern "C" hipError_t lfamd_launch_get_rows(int type, int tiled, const void *img, long rows, long cols, const int32_t *ids, long row0, long n_ids,
                                             int out_type, void *out, size_t out_row_bytes, hipStream_t s) {
-    const int ly = layout_of(type, cols);
+    const int ly = layout_of(type, cols, tiled);
     if (ly == LY_NONE || (out_type != LFAMD_TYPE_F32 && out_type != LFAMD_TYPE_F16))
         return hipErrorInvalidValue;
     if (n_ids <= 0 || cols <= 0)
@@ -565,8 +568,9 @@ extern "C" hipError_t lfamd_launch_get_rows(int type, const void *img, long rows
     return hipGetLastError();
 }
 
-extern "C" hipError_t lfamd_launch_unpack(int type, const void *img, long rows, long cols, void *raw, size_t raw_row_bytes, hipStream_t s) {
-    const int ly = layout_of(type, cols);
+extern "C" hipError_t lfamd_launch_unpack(int type, int tiled, const void *img, long rows, long cols, void *raw, size_t raw_row_bytes,
+                                          hipStream_t s) {
+    const int ly = layout_of(type, cols, tiled);
     if (ly == LY_NONE)
         return hipErrorInvalidValue;
     const size_t row_bytes = lfamd_row_size(type, cols);
@@ -577,7 +581,7 @@ extern "C" hipError_t lfamd_launch_unpack(int type, const void *img, long rows, 
     const dim3 grid((unsigned)rows, (unsigned)((row_bytes + 255) / 256));
     const uint8_t *in = (const uint8_t *)img;
     uint8_t *o = (uint8_t *)raw;
-    const int nb = type == LFAMD_TYPE_Q8_0 ? (int)((cols / 32 + 3) / 4) : (int)(cols / 256);
+    const int nb = type == LFAMD_TYPE_Q8_0 ? (int)((cols / 32 + 3) / 4) : (int)((cols + 255) / 256); // (a gather stops at row_bytes)
 #define UP(T)                                                                                                                              \
     case T:                                                                                                                                \
         unpack_kernel<T><<<grid, 256, 0, s>>>(in, cols, nb, row_bytes, o, raw_row_bytes);                                                  \

@@ -74,25 +74,37 @@ extern "C" int lfamd_gemv_has_kernel(int Atype, int f32in, const lfamd_gemv_plan
 
 // ---- the plan
 
+// Super-blocks of a row of k weights.  The 32-block types may come with rows that end inside the last one (LFAMD_TYPE_PAD256: the
+// image is padded with zero blocks); every other caller passes whole 256-weight groups.
+static int sb_of(long k) {
+    return (int)((k + 255) / 256);
+}
+// The kernels' `nb` argument (gemv_impl.h, kq_nb_of): the row's 32-blocks for the types on 32-block activations, else its super-blocks
+static int nb_arg(int Atype, long k) {
+    const bool b32 = Atype == LFAMD_TYPE_Q4_0 || Atype == LFAMD_TYPE_Q4_1 || Atype == LFAMD_TYPE_Q5_0 || Atype == LFAMD_TYPE_Q5_1 ||
+                     Atype == LFAMD_TYPE_IQ4_NL;
+    return b32 ? (int)(k / 32) : sb_of(k);
+}
+
 // LDS budget: keep one launch's activation image under 160 KiB; otherwise split the columns.
 static const size_t IMAGE_CAP = 150 * 1024;
 
 extern "C" int lfamd_gemv_depth_ok(long k) {
-    return (size_t)(k / 256) * XBLK <= IMAGE_CAP;
+    return (size_t)sb_of(k) * XBLK <= IMAGE_CAP;
 }
 
 extern "C" size_t lfamd_gemv_lds_bytes(int Atype, int nc, long k, int nw, int rows) {
-    return Atype == LFAMD_TYPE_Q8_0 ? q80_lds_bytes(nc, q80_quads(k)) : kq_lds_of(nc, (int)(k / 256), nw, rows).bytes;
+    return Atype == LFAMD_TYPE_Q8_0 ? q80_lds_bytes(nc, q80_quads(k)) : kq_lds_of(nc, sb_of(k), nw, rows).bytes;
 }
 
 extern "C" int lfamd_gemv_cols_per_launch(int Atype, long k) {
-    const size_t per_col = Atype == LFAMD_TYPE_Q8_0 ? q80_lds_bytes(1, q80_quads(k)) : (size_t)(k / 256) * XBLK;
+    const size_t per_col = Atype == LFAMD_TYPE_Q8_0 ? q80_lds_bytes(1, q80_quads(k)) : (size_t)sb_of(k) * XBLK;
     const int nc = (int)(IMAGE_CAP / (per_col ? per_col : 1));
     int step = nc < 1 ? 0 : (nc > 8 ? 8 : nc);
     // deep rows on the 8-wave x 4-block kernels: six and more columns per launch spill registers (256 VGPRs + 29..53
     // spilled).  Past 32 super-blocks two passes of at most five columns are faster (4096 x 14336, n = 8: Q4_K 47.9 -> 45.8
     // us, Q6_K 79.9 -> 67.0); at 32 the second pass costs more than the spills (4096 x 8192: 24.5 vs 29.7 us)
-    if (Atype != LFAMD_TYPE_Q8_0 && k / 256 > 32 && step > 5)
+    if (Atype != LFAMD_TYPE_Q8_0 && sb_of(k) > 32 && step > 5)
         step = 5;
     return step;
 }
@@ -152,7 +164,7 @@ extern "C" int lfamd_gemv_plan_of(int kind, int Atype, int nc, long work, long w
     const kq_unit *u = kq_unit_of(Atype);
     if (!u)
         return -1;
-    const int nb = (int)(k / 256), n_ht = (int)work;
+    const int nb = sb_of(k), n_ht = (int)work;
     p->rows = 16;
     switch (kind) {
     case LFAMD_GEMV_MULTI: {
@@ -257,9 +269,9 @@ static hipError_t launch(const void *kernel, const lfamd_gemv_plan &p, void **ar
 }
 
 // gemv_kq_kernel
-static hipError_t launch_kq(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nb, int n_ht,
+static hipError_t launch_kq(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nbk, int n_ht,
                             gemv_mats &mats, hipStream_t s) {
-    void *args[] = {&B, &brb, &col0, &nb, &n_ht, (void *)&p.grid, &mats};
+    void *args[] = {&B, &brb, &col0, &nbk, &n_ht, (void *)&p.grid, &mats};
     return launch(kernel, p, args, s);
 }
 
@@ -274,7 +286,7 @@ static int pre_boundary(const gemv_mats &mats, int i) {
 }
 
 // gemv_kq_early_kernel: the column is folded into the row pointer and into a copy of the table's result pointers
-static hipError_t launch_kq_early(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nb, int n_ht,
+static hipError_t launch_kq_early(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, long col0, int nbk, int n_ht,
                                   const gemv_mats &mats, hipStream_t s) {
     gemv_mats mc = mats;
     for (int i = 0; i < GEMV_MAX_MATS; i++)
@@ -282,29 +294,29 @@ static hipError_t launch_kq_early(const void *kernel, const lfamd_gemv_plan &p, 
             mc.C[i] += col0 * mc.ldc[i];
     const uint8_t *xrow = (const uint8_t *)B + col0 * (long)brb;
     int e0 = pre_boundary(mats, 0), e1 = pre_boundary(mats, 1);
-    void *args[] = {&xrow, &mc.A[0], &mc.A[1], &mc.A[2], &nb, &n_ht, (void *)&p.grid, &e0, &e1, &mc};
+    void *args[] = {&xrow, &mc.A[0], &mc.A[1], &mc.A[2], &nbk, &n_ht, (void *)&p.grid, &e0, &e1, &mc};
     return launch(kernel, p, args, s);
 }
 
 // gemv_kq_dual_kernel
-static hipError_t launch_kq_dual(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, int nb, int n_ht_a, int n_ht_b,
+static hipError_t launch_kq_dual(const void *kernel, const lfamd_gemv_plan &p, const void *B, size_t brb, int nbk, int n_ht_a, int n_ht_b,
                                  gemv_mats &ma, gemv_mats &mb, hipStream_t s) {
-    void *args[] = {&B, &brb, &nb, &n_ht_a, &n_ht_b, (void *)&p.grid, (void *)&p.grid_b, &ma, &mb};
+    void *args[] = {&B, &brb, &nbk, &n_ht_a, &n_ht_b, (void *)&p.grid, (void *)&p.grid_b, &ma, &mb};
     return launch(kernel, p, args, s);
 }
 
 // gemv_kq_dual_early_kernel (B: the one activation row)
-static hipError_t launch_kq_dual_early(const void *kernel, const lfamd_gemv_plan &p, const void *B, int nb, int n_ht_a, int n_ht_b,
+static hipError_t launch_kq_dual_early(const void *kernel, const lfamd_gemv_plan &p, const void *B, int nbk, int n_ht_a, int n_ht_b,
                                        gemv_mats &ma, gemv_mats &mb, hipStream_t s) {
     int ea0 = pre_boundary(ma, 0);
-    void *args[] = {&B, &ma.A[0], &ma.A[1], &mb.A[0], &nb, &n_ht_a, &n_ht_b, (void *)&p.grid, &ea0, (void *)&p.grid_b, &ma, &mb};
+    void *args[] = {&B, &ma.A[0], &ma.A[1], &mb.A[0], &nbk, &n_ht_a, &n_ht_b, (void *)&p.grid, &ea0, (void *)&p.grid_b, &ma, &mb};
     return launch(kernel, p, args, s);
 }
 
 // gemv_kq_ids_pair_kernel
-static hipError_t launch_kq_ids_pair(const void *kernel, const lfamd_gemv_plan &p, const void *Ba, const void *Bb, size_t brb, int nb, int n_ht,
+static hipError_t launch_kq_ids_pair(const void *kernel, const lfamd_gemv_plan &p, const void *Ba, const void *Bb, size_t brb, int nbk, int n_ht,
                                      gemv_mats &ma, gemv_mats &mb, hipStream_t s) {
-    void *args[] = {&Ba, &Bb, &brb, &nb, &n_ht, &n_ht, (void *)&p.grid, (void *)&p.grid_b, &ma, &mb};
+    void *args[] = {&Ba, &Bb, &brb, &nbk, &n_ht, &n_ht, (void *)&p.grid, (void *)&p.grid_b, &ma, &mb};
     return launch(kernel, p, args, s);
 }
 
@@ -435,9 +447,9 @@ extern "C" hipError_t lfamd_launch_gemv_multi(int Atype, int count, const void *
         const int nc = (int)((n - col0) < step ? (n - col0) : step);
         lfamd_gemv_plan_of(LFAMD_GEMV_MULTI, Atype, nc, n_ht, 0, k, mats.count, cus, &p);
         if (early_fits(p, mats))
-            e = launch_kq_early(kernel_of(Atype, f32in, p, 0, true), p, B, b_row_bytes, col0, (int)(k / 256), n_ht, mats, s);
+            e = launch_kq_early(kernel_of(Atype, f32in, p, 0, true), p, B, b_row_bytes, col0, nb_arg(Atype, k), n_ht, mats, s);
         else
-            e = launch_kq(kernel_of(Atype, f32in, p, 0), p, B, b_row_bytes, col0, (int)(k / 256), n_ht, mats, s);
+            e = launch_kq(kernel_of(Atype, f32in, p, 0), p, B, b_row_bytes, col0, nb_arg(Atype, k), n_ht, mats, s);
     }
     return e;
 }
@@ -458,8 +470,8 @@ extern "C" hipError_t lfamd_launch_gemv_dual(int type_a, int count_a, const void
         return hipErrorInvalidValue;
     const int f32in = Btype == LFAMD_TYPE_F32;
     if (ma.count <= 2 && mb.count == 1) // (every Q4_K_M / Q5_K_M layer: attn_q/k + attn_v)
-        return launch_kq_dual_early(kernel_of(type_a, f32in, p, 0, true), p, B, (int)(k / 256), n_ht_a, n_ht_b, ma, mb, s);
-    return launch_kq_dual(kernel_of(type_a, f32in, p, 0), p, B, b_row_bytes, (int)(k / 256), n_ht_a, n_ht_b, ma, mb, s);
+        return launch_kq_dual_early(kernel_of(type_a, f32in, p, 0, true), p, B, nb_arg(type_a, k), n_ht_a, n_ht_b, ma, mb, s);
+    return launch_kq_dual(kernel_of(type_a, f32in, p, 0), p, B, b_row_bytes, nb_arg(type_a, k), n_ht_a, n_ht_b, ma, mb, s);
 }
 
 // GGML_OP_MUL_MAT_ID for ONE activation row: `count` (<= GEMV_MAX_MATS) outputs C[j] = W[ids[id_idx[j]]] x B, the expert
@@ -479,7 +491,7 @@ extern "C" hipError_t lfamd_launch_gemv_ids(int Atype, int count, const void *co
     const void *kernel = kernel_of(Atype, Btype == LFAMD_TYPE_F32, p, 0);
     if (!kernel) // (a K-quant type whose unit holds no expert kernels)
         return hipErrorInvalidValue;
-    return launch_kq(kernel, p, B, b_row_bytes, 0, (int)(k / 256), n_ht, mats, s);
+    return launch_kq(kernel, p, B, b_row_bytes, 0, nb_arg(Atype, k), n_ht, mats, s);
 }
 
 // two experts of one tensor, each against its own activation row (ffn_down_exps at decode): one launch
@@ -497,7 +509,7 @@ extern "C" hipError_t lfamd_launch_gemv_ids_pair(int Atype, const void *W, long 
     const void *kernel = kernel_of(Atype, Btype == LFAMD_TYPE_F32, p, 0);
     if (!kernel)
         return hipErrorInvalidValue;
-    return launch_kq_ids_pair(kernel, p, Ba, Bb, b_row_bytes, (int)(k / 256), n_ht, ma, mb, s);
+    return launch_kq_ids_pair(kernel, p, Ba, Bb, b_row_bytes, nb_arg(Atype, k), n_ht, ma, mb, s);
 }
 
 extern "C" hipError_t lfamd_launch_gemv(int Atype, const void *A, long m, long k, int Btype, const void *B,

@@ -175,33 +175,54 @@ __device__ static inline void quantise_piece_q80(uint8_t *dst, const float (&v)[
     }
 }
 
-template <bool S1>
-__device__ static inline void stage_f32_as_q80(uint8_t *lds, const uint8_t *X, size_t x_row_bytes, long col0, int nc,
-                                               int nb) {
+// The rows of the 32-block types may end inside the last super-block (LFAMD_TYPE_PAD256: the weight image continues with all-zero
+// blocks to a whole 256-weight group).  kb = the row's 32-blocks, nb = ceil(kb / 8).  TAIL (kb != 8 nb): nothing behind block kb is
+// read — what lies there may be NaN, and NaN * 0 is not 0 — and the image's blocks from kb on are written as what a row of zeros
+// gives: codes, group and pair sums, d and s all 0.  Whole rows run the TAIL = false code, which is the code from before the layout.
+template <bool S1, bool TAIL>
+__device__ static inline void stage_f32_as_q80_rows(uint8_t *lds, const uint8_t *X, size_t x_row_bytes, long col0, int nc, int nb, int kb) {
     const int pieces = nb * 16;
     const int l16 = threadIdx.x & 15;
     for (int c = 0; c < nc; c++) {
         const float *x = (const float *)(X + (col0 + c) * x_row_bytes);
         for (int p = threadIdx.x; p < pieces; p += blockDim.x) {
             float v[16];
-            load_piece(v, x, p);
+            if (!TAIL || p < 2 * kb) { // (both pieces of a 32-block take the same side)
+                load_piece(v, x, p);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    v[e] = 0.0f;
+            }
             quantise_piece_q80<S1>(lds + (size_t)(c * nb + (p >> 4)) * XBLK, v, l16);
         }
     }
 }
 
+template <bool S1>
+__device__ static inline void stage_f32_as_q80(uint8_t *lds, const uint8_t *X, size_t x_row_bytes, long col0, int nc, int nb, int kb) {
+    if (kb == 8 * nb) // (uniform over the launch)
+        stage_f32_as_q80_rows<S1, false>(lds, X, x_row_bytes, col0, nc, nb, kb);
+    else
+        stage_f32_as_q80_rows<S1, true>(lds, X, x_row_bytes, col0, nc, nb, kb);
+}
+
 // already-quantised Q8_0 (34-byte blocks) / Q8_1 (36-byte blocks {d, s, qs}) rows: one 8-byte group per lane, 32
 // consecutive lanes per 256 codes
-template <bool S1>
-__device__ static inline void stage_q80_blocks(uint8_t *lds, const uint8_t *B, size_t b_row_bytes, long col0, int nc, int nb) {
+template <bool S1, bool TAIL>
+__device__ static inline void stage_q80_blocks_rows(uint8_t *lds, const uint8_t *B, size_t b_row_bytes, long col0, int nc, int nb, int kb) {
     constexpr int BS = S1 ? 36 : 34, QS = S1 ? 4 : 2;
     const int groups = nc * nb * 32;
     for (int gidx = threadIdx.x; gidx < groups; gidx += blockDim.x) {
         int c = gidx / (nb * 32), r = gidx % (nb * 32);
         int b = r >> 5, grp = r & 31;
         const uint8_t *blk = B + (col0 + c) * b_row_bytes + (size_t)(b * 8 + (grp >> 2)) * BS;
-        const uint16_t *src = (const uint16_t *)(blk + QS + 8 * (grp & 3));
-        const uint32_t y0 = (uint32_t)src[0] | ((uint32_t)src[1] << 16), y1 = (uint32_t)src[2] | ((uint32_t)src[3] << 16);
+        const bool in = !TAIL || b * 8 + (grp >> 2) < kb; // (the four groups of a 32-block take the same side)
+        uint32_t y0 = 0, y1 = 0;
+        if (in) {
+            const uint16_t *src = (const uint16_t *)(blk + QS + 8 * (grp & 3));
+            y0 = (uint32_t)src[0] | ((uint32_t)src[1] << 16), y1 = (uint32_t)src[2] | ((uint32_t)src[3] << 16);
+        }
         uint8_t *dst = lds + (size_t)(c * nb + b) * XBLK;
         const int hs = put_group(dst, grp, y0, y1);
         const int other = __shfl_xor(hs, 2, 64);
@@ -209,15 +230,24 @@ __device__ static inline void stage_q80_blocks(uint8_t *lds, const uint8_t *B, s
             put_pair(dst, grp, hs + other);
         if ((grp & 3) == 0) {
             if constexpr (S1)
-                *(uint32_t *)(dst + XBLK_D + 4 * (grp >> 2)) = (uint32_t)((const uint16_t *)blk)[0] | ((uint32_t)((const uint16_t *)blk)[1] << 16);
+                *(uint32_t *)(dst + XBLK_D + 4 * (grp >> 2)) = in ? (uint32_t)((const uint16_t *)blk)[0] | ((uint32_t)((const uint16_t *)blk)[1] << 16) : 0u;
             else
-                *(float *)(dst + XBLK_D + 4 * (grp >> 2)) = h2f(*(const uint16_t *)blk);
+                *(float *)(dst + XBLK_D + 4 * (grp >> 2)) = in ? h2f(*(const uint16_t *)blk) : 0.0f;
         }
     }
 }
 
+template <bool S1>
+__device__ static inline void stage_q80_blocks(uint8_t *lds, const uint8_t *B, size_t b_row_bytes, long col0, int nc, int nb, int kb) {
+    if (kb == 8 * nb)
+        stage_q80_blocks_rows<S1, false>(lds, B, b_row_bytes, col0, nc, nb, kb);
+    else
+        stage_q80_blocks_rows<S1, true>(lds, B, b_row_bytes, col0, nc, nb, kb);
+}
+
+// (kb: the row's 32-blocks, read by the 32-block formats only)
 template <int BT, int ACT>
-__device__ static inline void stage_x(uint8_t *lds, const uint8_t *B, size_t b_row_bytes, long col0, int nc, int nb) {
+__device__ static inline void stage_x(uint8_t *lds, const uint8_t *B, size_t b_row_bytes, long col0, int nc, int nb, int kb) {
     if constexpr (ACT == LFAMD_TYPE_Q8_K) {
         if constexpr (BT == LFAMD_TYPE_F32)
             stage_f32_as_q8k(lds, B, b_row_bytes, col0, nc, nb);
@@ -225,9 +255,9 @@ __device__ static inline void stage_x(uint8_t *lds, const uint8_t *B, size_t b_r
             stage_q8k(lds, B, b_row_bytes, col0, nc, nb);
     } else {
         if constexpr (BT == LFAMD_TYPE_F32)
-            stage_f32_as_q80<ACT == LFAMD_TYPE_Q8_1>(lds, B, b_row_bytes, col0, nc, nb);
+            stage_f32_as_q80<ACT == LFAMD_TYPE_Q8_1>(lds, B, b_row_bytes, col0, nc, nb, kb);
         else
-            stage_q80_blocks<ACT == LFAMD_TYPE_Q8_1>(lds, B, b_row_bytes, col0, nc, nb);
+            stage_q80_blocks<ACT == LFAMD_TYPE_Q8_1>(lds, B, b_row_bytes, col0, nc, nb, kb);
     }
 }
 
@@ -841,8 +871,10 @@ __device__ static inline void stage_f32_q80_wave2(uint8_t *dst, const float4 va,
 }
 
 // one block of already-quantised activations, staged by one wave (lanes 0..31: one 8-code group each)
-template <int ACT>
-__device__ static inline void stage_quantised_wave(uint8_t *dst, const uint8_t *row_generic, int b, int lane) {
+// TAIL (32-block formats, the row ends inside this super-block after kb 32-blocks): the blocks from kb on are not read and staged
+// as zeros (stage_f32_as_q80_rows has the rule)
+template <int ACT, bool TAIL = false>
+__device__ static inline void stage_quantised_wave(uint8_t *dst, const uint8_t *row_generic, int b, int lane, int kb = 0) {
     // (explicitly GLOBAL: the pointer went through an SGPR pin and would otherwise be read with FLAT loads, which make
     // hipcc's wait counts conservative for the whole kernel — tests/test_isa_hazards.py)
     typedef const __attribute__((address_space(1))) uint8_t *gptr;
@@ -859,14 +891,18 @@ __device__ static inline void stage_quantised_wave(uint8_t *dst, const uint8_t *
         } else {
             constexpr bool S1 = ACT == LFAMD_TYPE_Q8_1;
             const gptr blk = row + (size_t)(b * 8 + (grp >> 2)) * (S1 ? 36 : 34);
-            const __attribute__((address_space(1))) uint16_t *src = (const __attribute__((address_space(1))) uint16_t *)(blk + (S1 ? 4 : 2) + 8 * (grp & 3));
-            y0 = (uint32_t)src[0] | ((uint32_t)src[1] << 16), y1 = (uint32_t)src[2] | ((uint32_t)src[3] << 16);
+            const bool in = !TAIL || b * 8 + (grp >> 2) < kb;
+            y0 = y1 = 0;
+            if (in) {
+                const __attribute__((address_space(1))) uint16_t *src = (const __attribute__((address_space(1))) uint16_t *)(blk + (S1 ? 4 : 2) + 8 * (grp & 3));
+                y0 = (uint32_t)src[0] | ((uint32_t)src[1] << 16), y1 = (uint32_t)src[2] | ((uint32_t)src[3] << 16);
+            }
             if ((grp & 3) == 0) {
                 const __attribute__((address_space(1))) uint16_t *hdr = (const __attribute__((address_space(1))) uint16_t *)blk;
                 if constexpr (S1)
-                    *(uint32_t *)(dst + XBLK_D + 4 * (grp >> 2)) = (uint32_t)hdr[0] | ((uint32_t)hdr[1] << 16);
+                    *(uint32_t *)(dst + XBLK_D + 4 * (grp >> 2)) = in ? (uint32_t)hdr[0] | ((uint32_t)hdr[1] << 16) : 0u;
                 else
-                    *(float *)(dst + XBLK_D + 4 * (grp >> 2)) = h2f(hdr[0]);
+                    *(float *)(dst + XBLK_D + 4 * (grp >> 2)) = in ? h2f(hdr[0]) : 0.0f;
             }
         }
         put_group_pair(dst, grp, y0, y1);
@@ -877,11 +913,27 @@ __device__ static inline void stage_quantised_wave(uint8_t *dst, const uint8_t *
 #define KQ_F4(u) make_float4(__builtin_bit_cast(float, (u).x), __builtin_bit_cast(float, (u).y), __builtin_bit_cast(float, (u).z), \
                            __builtin_bit_cast(float, (u).w))
 
+// The kernels' `nb` argument.  Types on Q8_K activations: the row's super-blocks.  Types on 32-block activations (Q8_0 / Q8_1), whose
+// rows may end inside the last super-block of a padded image (LFAMD_TYPE_PAD256): the row's 32-blocks kb, so nb = ceil(kb / 8) and
+// a row of f32 activations is kb * 128 bytes long.  One argument either way: the early kernels' preloaded dwords stay 13.
+template <typename TR>
+__device__ __forceinline__ int kq_nb_of(int nbk) {
+    if constexpr (TR::ACT == LFAMD_TYPE_Q8_K)
+        return nbk;
+    else
+        return (nbk + 7) >> 3;
+}
+template <typename TR>
+__device__ __forceinline__ uint32_t kq_row_bytes_f32(int nbk) {
+    return (uint32_t)nbk * (TR::ACT == LFAMD_TYPE_Q8_K ? 1024u : 128u);
+}
+
 // The body of a GEMV work-group: work-group `bid` of `gdim` over the half-tiles of `mats` (the plain kernel passes its
 // block index and grid size; the two-type kernel gives each type its own sub-grid).
 template <typename TR, int NC, int BT, int NW, int GEMV_CH, bool IDS>
-__device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, const uint8_t *__restrict__ B, size_t b_row_bytes,
+__device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, const int nbk, const uint8_t *__restrict__ B, size_t b_row_bytes,
                                              long col0, int n_ht, const int bid, const int gdim, uint8_t *lds) {
+    const int nb = kq_nb_of<TR>(nbk), kb = nbk; // (kb: read by the 32-block types only)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i16 = lane & 15, h = (lane >> 4) & 1, gsel = lane >> 5;
     const kq_lds lay = kq_lds_of(NC, nb, NW, 16);
@@ -1016,7 +1068,7 @@ __device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, cons
         uint4 xv[NC][GEMV_CH];
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            const lfamd_rsrc rx = make_rsrc(B + (col0 + c) * b_row_bytes, (uint32_t)nb * 1024u);
+            const lfamd_rsrc rx = make_rsrc(B + (col0 + c) * b_row_bytes, kq_row_bytes_f32<TR>(nbk)); // (past the row: zeros)
 #pragma unroll
             for (int u = 0; u < GEMV_CH; u++)
                 xv[c][u] = buf_ld16(rx, (uint32_t)(wave_u + NW * u) * 1024u + (uint32_t)lane * 16u);
@@ -1041,7 +1093,7 @@ __device__ __forceinline__ void gemv_kq_body(const gemv_mats &mats, int nb, cons
             }
     } else {
         issue(bufA, 0); // in flight during the staging below
-        stage_x<BT, TR::ACT>(lds, B, b_row_bytes, col0, NC, nb);
+        stage_x<BT, TR::ACT>(lds, B, b_row_bytes, col0, NC, nb, kb);
     }
     __syncthreads();
     GSTAMP();
@@ -1155,14 +1207,15 @@ struct kq_pre {
 };
 
 template <typename TR, int BT, int NW, int GEMV_CH, bool IDS, bool EARLY = false, bool PAIR = false>
-__device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, const uint8_t *__restrict__ B,
+__device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nbk, const uint8_t *__restrict__ B,
                                               size_t b_row_bytes, long col0, int n_ht, const int bid, int gdim,
                                               uint8_t *lds, const kq_pre pre) {
     // (EARLY: B is the activation row itself, b_row_bytes and col0 are the literal 0 and fold away)
     if constexpr (EARLY)
-        asm volatile("" : "+s"(nb), "+s"(B), "+s"(n_ht), "+s"(gdim));
+        asm volatile("" : "+s"(nbk), "+s"(B), "+s"(n_ht), "+s"(gdim));
     else
-        asm volatile("" : "+s"(nb), "+s"(B), "+s"(b_row_bytes), "+s"(col0), "+s"(n_ht), "+s"(gdim)); // (one s_load round)
+        asm volatile("" : "+s"(nbk), "+s"(B), "+s"(b_row_bytes), "+s"(col0), "+s"(n_ht), "+s"(gdim)); // (one s_load round)
+    const int nb = kq_nb_of<TR>(nbk), kb = nbk; // (kb: read by the 32-block types only)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i16 = lane & 15, h = (lane >> 4) & 1, gsel = lane >> 5;
@@ -1181,7 +1234,7 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
     // group as two passes of two (lane l: eight values of block (l >> 5) of the pass), four loads per lane.
     constexpr int JX = GEMV_CH == 1 ? 1 : (NW == 8 ? 2 : 4);
     const uint8_t *xrow = B + col0 * b_row_bytes;
-    const lfamd_rsrc rx = make_rsrc(xrow, (uint32_t)nb * 1024u);
+    const lfamd_rsrc rx = make_rsrc(xrow, kq_row_bytes_f32<TR>(nbk)); // (a load past the row returns zeros: a padded tail stages as zeros)
     uint4 xv[JX];
     auto x_off = [&](int j0, int j) __attribute__((always_inline)) { // byte offset of load j of the group starting at block slot j0
         if constexpr (JX == 1)
@@ -1382,8 +1435,17 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
             for (int b = wave + 2 * NW; b < nb; b += NW)
                 stage_quantised_wave<TR::ACT>(lds + (size_t)b * XBLK, xrow, b, lane);
         } else {
-            for (int b = wave; b < nb; b += NW)
-                stage_quantised_wave<TR::ACT>(lds + (size_t)b * XBLK, xrow, b, lane);
+            if (TR::ACT != LFAMD_TYPE_Q8_K && kb != 8 * nb) { // a padded row (uniform over the launch): its last block stages the tail
+                for (int b = wave; b < nb; b += NW) {
+                    if (b * 8 + 8 > kb) // (b is wave-uniform: a scalar branch)
+                        stage_quantised_wave<TR::ACT, true>(lds + (size_t)b * XBLK, xrow, b, lane, kb);
+                    else
+                        stage_quantised_wave<TR::ACT>(lds + (size_t)b * XBLK, xrow, b, lane);
+                }
+            } else { // whole rows: the loop as it was before the layout
+                for (int b = wave; b < nb; b += NW)
+                    stage_quantised_wave<TR::ACT>(lds + (size_t)b * XBLK, xrow, b, lane);
+            }
         }
     }
     // the image blocks this wave reads are the ones it has just written: program order in the LDS queue is enough;
@@ -1421,27 +1483,27 @@ __device__ __forceinline__ void gemv_kq_body1(const gemv_mats &mats, int nb, con
 }
 
 template <typename TR, int NC, int BT, int NW, int GEMV_CH, bool IDS = false, bool PAIR = false>
-__global__ __launch_bounds__(NW * 64) void gemv_kq_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, long col0, int nb,
+__global__ __launch_bounds__(NW * 64) void gemv_kq_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, long col0, int nbk,
                                                           int n_ht, int gdim, const gemv_mats mats) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if constexpr (NC == 1)
-        gemv_kq_body1<TR, BT, NW, GEMV_CH, IDS, false, PAIR>(mats, nb, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds, kq_pre{});
+        gemv_kq_body1<TR, BT, NW, GEMV_CH, IDS, false, PAIR>(mats, nbk, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds, kq_pre{});
     else
-        gemv_kq_body<TR, NC, BT, NW, GEMV_CH, IDS>(mats, nb, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds);
+        gemv_kq_body<TR, NC, BT, NW, GEMV_CH, IDS>(mats, nbk, B, b_row_bytes, col0, n_ht, (int)blockIdx.x, gdim, lds);
 }
 
 // ONE activation row, one to three matrices: the 13 dwords the hardware preloads are exactly what work-group `bid` needs to
 // address its first item — the row (column offset and row stride folded in on the host, which folds the column into mats.C as
-// well), the three weight pointers, nb, n_ht, gdim and the two boundaries.  mats (and so the store path and every later item) is
+// well), the three weight pointers, nbk (kq_nb_of: the row's super-blocks, or its 32-blocks), n_ht, gdim and the two boundaries.  mats (and so the store path and every later item) is
 // what gemv_kq_kernel gets.
 template <typename TR, int NC, int BT, int NW, int GEMV_CH>
 __global__ __launch_bounds__(NW * 64) void gemv_kq_early_kernel(const uint8_t *__restrict__ xrow, const uint8_t *__restrict__ A0,
-                                                                const uint8_t *__restrict__ A1, const uint8_t *__restrict__ A2, int nb,
+                                                                const uint8_t *__restrict__ A1, const uint8_t *__restrict__ A2, int nbk,
                                                                 int n_ht, int gdim, int e0, int e1, const gemv_mats mats) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     static_assert(NC == 1, "one activation row (the parameter keeps the kernel's name in line with gemv_kq_kernel's)");
     asm volatile("" : "+s"(A0), "+s"(A1), "+s"(A2), "+s"(e0), "+s"(e1));
-    gemv_kq_body1<TR, BT, NW, GEMV_CH, false, true>(mats, nb, xrow, 0, 0, n_ht, (int)blockIdx.x, gdim, lds, kq_pre{A0, A1, A2, e0, e1});
+    gemv_kq_body1<TR, BT, NW, GEMV_CH, false, true>(mats, nbk, xrow, 0, 0, n_ht, (int)blockIdx.x, gdim, lds, kq_pre{A0, A1, A2, e0, e1});
 }
 
 // Two expert GEMVs on DIFFERENT activation rows in ONE decode launch (GGML_OP_MUL_MAT_ID ffn_down_exps: every chosen expert
@@ -1449,28 +1511,28 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq_early_kernel(const uint8_t *_
 // serves one of the two, so it stages one row, as in a single launch.
 template <typename TR, int BT, int NW, int GEMV_CH>
 __global__ __launch_bounds__(NW * 64) void gemv_kq_ids_pair_kernel(const uint8_t *__restrict__ Ba, const uint8_t *__restrict__ Bb,
-                                                                   size_t b_row_bytes, int nb, int n_ht_a, int n_ht_b, int grid_a, int grid_b,
+                                                                   size_t b_row_bytes, int nbk, int n_ht_a, int n_ht_b, int grid_a, int grid_b,
                                                                    const gemv_mats mats_a, const gemv_mats mats_b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if ((int)blockIdx.x < grid_a)
-        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_a, nb, Ba, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, kq_pre{});
+        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_a, nbk, Ba, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, kq_pre{});
     else
-        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_b, nb, Bb, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, kq_pre{});
+        gemv_kq_body1<TR, BT, NW, GEMV_CH, true>(mats_b, nbk, Bb, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, kq_pre{});
 }
 
 // Two weight types in ONE decode launch (sibling mat-muls on the same activations whose types differ: attn_q/k in Q4_K
 // with attn_v in Q6_K in a Q4_K_M file): work-groups [0, grid_a) run type A's body over mats_a, the rest type B's over
 // mats_b.  A work-group is of one type, so it stages the activations once, in the (shared) Q8_K image.
 template <typename TRA, typename TRB, int BT, int NW, int GEMV_CH>
-__global__ __launch_bounds__(NW * 64) void gemv_kq_dual_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, int nb, int n_ht_a,
+__global__ __launch_bounds__(NW * 64) void gemv_kq_dual_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, int nbk, int n_ht_a,
                                                                int n_ht_b, int grid_a, int grid_b, const gemv_mats mats_a,
                                                                const gemv_mats mats_b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    static_assert(TRA::ACT == TRB::ACT, "both types must share the activation image");
+    static_assert(TRA::ACT == TRB::ACT, "both types must share the activation image, and so the meaning of nbk (kq_nb_of)");
     if ((int)blockIdx.x < grid_a)
-        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false>(mats_a, nb, B, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, kq_pre{});
+        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false>(mats_a, nbk, B, b_row_bytes, 0, n_ht_a, (int)blockIdx.x, grid_a, lds, kq_pre{});
     else
-        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false>(mats_b, nb, B, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, kq_pre{});
+        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false>(mats_b, nbk, B, b_row_bytes, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds, kq_pre{});
 }
 
 // ... with the first item of BOTH sub-grids from preloaded arguments, for the launch every Q4_K_M / Q5_K_M layer makes: one or
@@ -1478,17 +1540,17 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq_dual_kernel(const uint8_t *__
 // (a fourteenth dword is all the hardware grants beside the kernel-argument pointer).
 template <typename TRA, typename TRB, int BT, int NW, int GEMV_CH>
 __global__ __launch_bounds__(NW * 64) void gemv_kq_dual_early_kernel(const uint8_t *__restrict__ xrow, const uint8_t *__restrict__ Aa0,
-                                                                     const uint8_t *__restrict__ Aa1, const uint8_t *__restrict__ Ab0, int nb,
+                                                                     const uint8_t *__restrict__ Aa1, const uint8_t *__restrict__ Ab0, int nbk,
                                                                      int n_ht_a, int n_ht_b, int grid_a, int ea0, int grid_b,
                                                                      const gemv_mats mats_a, const gemv_mats mats_b) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    static_assert(TRA::ACT == TRB::ACT, "both types must share the activation image");
+    static_assert(TRA::ACT == TRB::ACT, "both types must share the activation image, and so the meaning of nbk (kq_nb_of)");
     asm volatile("" : "+s"(Aa0), "+s"(Aa1), "+s"(Ab0), "+s"(ea0), "+s"(grid_a));
     if ((int)blockIdx.x < grid_a)
-        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false, true>(mats_a, nb, xrow, 0, 0, n_ht_a, (int)blockIdx.x, grid_a, lds,
+        gemv_kq_body1<TRA, BT, NW, GEMV_CH, false, true>(mats_a, nbk, xrow, 0, 0, n_ht_a, (int)blockIdx.x, grid_a, lds,
                                                          kq_pre{Aa0, Aa1, Aa1, ea0, KQ_NO_BOUNDARY});
     else
-        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false, true>(mats_b, nb, xrow, 0, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds,
+        gemv_kq_body1<TRB, BT, NW, GEMV_CH, false, true>(mats_b, nbk, xrow, 0, 0, n_ht_b, (int)blockIdx.x - grid_a, grid_b, lds,
                                                          kq_pre{Ab0, Ab0, Ab0, KQ_NO_BOUNDARY, KQ_NO_BOUNDARY});
 }
 

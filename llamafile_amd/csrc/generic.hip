@@ -264,8 +264,10 @@ __global__ void wprep16_kernel(const uint8_t *__restrict__ raw, size_t raw_row_b
 
 // Legacy 32-block types (Q4_1, Q5_0, Q5_1) -> PCL tiles.  Weight l of a block: low nibble of qs[l] (l < 16) or high
 // nibble of qs[l - 16], fifth bit = bit l of qh (iqk_mul_mat.inc:1241-1283).
+// kb: 32-blocks of a raw row.  kb < 8 nb (LFAMD_TYPE_PAD256): the blocks from kb on are not read and written as zero bytes (d = +0,
+// m = +0, nibbles and fifth bits 0), for every row of the tile.
 template <int TYPE>
-__global__ void wprep32_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb, uint8_t *__restrict__ out,
+__global__ void wprep32_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb, int kb, uint8_t *__restrict__ out,
                                long n_tiles) {
     constexpr bool HAS_M = TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr bool HAS_H = TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
@@ -289,7 +291,7 @@ __global__ void wprep32_kernel(const uint8_t *__restrict__ raw, size_t raw_row_b
             const int t = 4 * g + dd;
             for (int j = 0; j < 8; j++) {
                 const int k = 16 * t + 8 * h + j, bl = k >> 5, l = k & 31;
-                const uint8_t byte = blk0[bl * BS + QS_OFF + (l & 15)];
+                const uint8_t byte = b * 8 + bl < kb ? blk0[bl * BS + QS_OFF + (l & 15)] : (uint8_t)0;
                 v |= (uint32_t)(l < 16 ? (byte & 15) : (byte >> 4)) << (4 * NIBPOS(j));
             }
         }
@@ -299,8 +301,8 @@ __global__ void wprep32_kernel(const uint8_t *__restrict__ raw, size_t raw_row_b
         const long row = rt * 32 + i;
         if (row < rows && (!is_m || HAS_M)) {
             const uint8_t *blk0 = raw + row * raw_row_bytes + (size_t)b * 8 * BS;
-            const uint16_t lo = *(const uint16_t *)(blk0 + (2 * q) * BS + (is_m ? 2 : 0));
-            const uint16_t hi = *(const uint16_t *)(blk0 + (2 * q + 1) * BS + (is_m ? 2 : 0));
+            const uint16_t lo = b * 8 + 2 * q < kb ? *(const uint16_t *)(blk0 + (2 * q) * BS + (is_m ? 2 : 0)) : (uint16_t)0;
+            const uint16_t hi = b * 8 + 2 * q + 1 < kb ? *(const uint16_t *)(blk0 + (2 * q + 1) * BS + (is_m ? 2 : 0)) : (uint16_t)0;
             v = (uint32_t)lo | ((uint32_t)hi << 16);
         }
     } else {
@@ -314,7 +316,7 @@ __global__ void wprep32_kernel(const uint8_t *__restrict__ raw, size_t raw_row_b
                 for (int j = 0; j < 8; j++) {
                     const int k = 16 * t + 8 * h + j, bl = k >> 5, l = k & 31;
                     const uint8_t *qh = blk0 + bl * BS + QH_OFF;
-                    const uint32_t bit = (qh[l >> 3] >> (l & 7)) & 1u;
+                    const uint32_t bit = b * 8 + bl < kb ? (qh[l >> 3] >> (l & 7)) & 1u : 0u;
                     v |= bit << (4 * q5hpos(j) + dd);
                 }
             }
@@ -323,23 +325,23 @@ __global__ void wprep32_kernel(const uint8_t *__restrict__ raw, size_t raw_row_b
     dst[w] = v;
 }
 
-extern "C" size_t lfamd_wprep32_bytes(long rows, long cols) {
-    return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * PCL_TILE;
+extern "C" size_t lfamd_wprep32_bytes(long rows, long cols) { // (cols: a row's weights; a row that ends inside a super-block is padded)
+    return (size_t)((rows + 31) / 32) * (size_t)((cols + 255) / 256) * PCL_TILE;
 }
 
 extern "C" hipError_t lfamd_launch_wprep32(int type, const void *raw, size_t raw_row_bytes, long rows, long cols, void *out,
                                            hipStream_t s) {
-    const int nb = (int)(cols / 256);
+    const int nb = (int)((cols + 255) / 256), kb = (int)(cols / 32);
     const long n_tiles = ((rows + 31) / 32) * nb;
     const long threads = n_tiles * 1536;
     const size_t rrb = raw_row_bytes;
     const unsigned grid = (unsigned)((threads + 255) / 256);
     if (type == LFAMD_TYPE_Q4_1)
-        wprep32_kernel<LFAMD_TYPE_Q4_1><<<grid, 256, 0, s>>>((const uint8_t *)raw, rrb, rows, nb, (uint8_t *)out, n_tiles);
+        wprep32_kernel<LFAMD_TYPE_Q4_1><<<grid, 256, 0, s>>>((const uint8_t *)raw, rrb, rows, nb, kb, (uint8_t *)out, n_tiles);
     else if (type == LFAMD_TYPE_Q5_0)
-        wprep32_kernel<LFAMD_TYPE_Q5_0><<<grid, 256, 0, s>>>((const uint8_t *)raw, rrb, rows, nb, (uint8_t *)out, n_tiles);
+        wprep32_kernel<LFAMD_TYPE_Q5_0><<<grid, 256, 0, s>>>((const uint8_t *)raw, rrb, rows, nb, kb, (uint8_t *)out, n_tiles);
     else if (type == LFAMD_TYPE_Q5_1)
-        wprep32_kernel<LFAMD_TYPE_Q5_1><<<grid, 256, 0, s>>>((const uint8_t *)raw, rrb, rows, nb, (uint8_t *)out, n_tiles);
+        wprep32_kernel<LFAMD_TYPE_Q5_1><<<grid, 256, 0, s>>>((const uint8_t *)raw, rrb, rows, nb, kb, (uint8_t *)out, n_tiles);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

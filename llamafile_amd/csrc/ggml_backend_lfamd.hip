@@ -378,7 +378,15 @@ const uint8_t *weight_bytes(const struct ggml_tensor *a) {
     return is_split(a) ? (a->extra ? (const uint8_t *)((const split_extra *)a->extra)->d[0] : nullptr) : (const uint8_t *)a->data;
 }
 
+// The type id of this module's resident copy of a weight tensor, used in every size, pack and mat-mul call on that copy: a legacy
+// 32-block tensor whose rows are not whole 256-weight groups is kept as the padded tile image (LFAMD_TYPE_PAD256: the decode GEMV and
+// the MFMA batches instead of the generic kernel).  The tensor's own bytes, supports_op and the sizes the host sees keep a->type.
+int resident_type(const struct ggml_tensor *a) {
+    return lfamd_resident_type(a->type, (long)a->ne[0]);
+}
+
 // packed device copy of `rows` raw rows at `raw` (on the CURRENT device); kept under the raw address when `keep`
+// (type: the resident id, resident_type)
 const packed *get_packed_rows(void *&scratch, size_t &scratch_cap, int type, const uint8_t *raw, long rows, long cols, size_t row_bytes,
                               bool keep, packed *tmp) {
     const size_t need = lfamd_packed_size(type, rows, cols);
@@ -418,8 +426,8 @@ const packed *get_packed(backend_ctx *ctx, const struct ggml_tensor *a, int64_t 
     if (!base)
         return nullptr;
     const bool keep = a->buffer && g_api->ggml_backend_buffer_get_usage(a->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
-    return get_packed_rows(ctx->scratch, ctx->scratch_cap, a->type, base + i02 * a->nb[2] + i03 * a->nb[3], (long)a->ne[1], (long)a->ne[0],
-                           a->nb[1], keep, tmp);
+    return get_packed_rows(ctx->scratch, ctx->scratch_cap, resident_type(a), base + i02 * a->nb[2] + i03 * a->nb[3], (long)a->ne[1],
+                           (long)a->ne[0], a->nb[1], keep, tmp);
 }
 
 // The struct layouts this module reads (include/ggml_backend_lfamd.h, marked RECALLED: llama.cpp is not vendored in the reference
@@ -534,14 +542,15 @@ enum ggml_status run_mul_mat_split(backend_ctx *ctx, struct ggml_tensor *dst) {
                 packed tmp;
                 void *no_scratch = nullptr; // (split buffers hold weights: always kept)
                 size_t no_cap = 0;
-                const packed *w = get_packed_rows(no_scratch, no_cap, a->type, (const uint8_t *)e->d[d], rows, k, e->row_bytes, true, &tmp);
+                const int rt = resident_type(a);
+                const packed *w = get_packed_rows(no_scratch, no_cap, rt, (const uint8_t *)e->d[d], rows, k, e->row_bytes, true, &tmp);
                 if (!w)
                     return GGML_STATUS_ALLOC_FAILED;
                 void *&ws = own ? ctx->ws : ps.ws;
                 size_t &ws_cap = own ? ctx->ws_cap : ps.ws_cap;
-                if (!grow(ws, ws_cap, lfamd_mul_mat_workspace(a->type, rows, k, n)))
+                if (!grow(ws, ws_cap, lfamd_mul_mat_workspace(rt, rows, k, n)))
                     return GGML_STATUS_ALLOC_FAILED;
-                if (lfamd_mul_mat(a->type, w->d, rows, k, LFAMD_TYPE_F32, B, brb, n, C, c_ld, ws, ws_cap,
+                if (lfamd_mul_mat(rt, w->d, rows, k, LFAMD_TYPE_F32, B, brb, n, C, c_ld, ws, ws_cap,
                                   (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | base_flags(), nullptr) != LFAMD_OK) {
                     logf("%s: lfamd_mul_mat (row slice): %s\n", "ggml_backend_lfamd", lfamd_last_error());
                     return GGML_STATUS_FAILED;
@@ -571,7 +580,8 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
     const int64_t r2 = b->ne[2] / (a->ne[2] ? a->ne[2] : 1), r3 = b->ne[3] / (a->ne[3] ? a->ne[3] : 1);
     if (is_split(a) && a->ne[2] * a->ne[3] == 1)
         return run_mul_mat_split(ctx, dst);
-    const size_t wsb = lfamd_mul_mat_workspace(a->type, m, k, n);
+    const int rt = resident_type(a);
+    const size_t wsb = lfamd_mul_mat_workspace(rt, m, k, n);
     if (!grow(ctx->ws, ctx->ws_cap, wsb))
         return GGML_STATUS_ALLOC_FAILED;
     std::lock_guard<std::mutex> lk(g_mu);
@@ -589,7 +599,7 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
                 return GGML_STATUS_ALLOC_FAILED;
             const uint8_t *bp = (const uint8_t *)b->data + i12 * b->nb[2] + i13 * b->nb[3];
             float *cp = (float *)((uint8_t *)dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]);
-            if (lfamd_mul_mat(a->type, w->d, m, k, LFAMD_TYPE_F32, bp, b->nb[1], n, cp, (long)(dst->nb[1] / sizeof(float)), ctx->ws,
+            if (lfamd_mul_mat(rt, w->d, m, k, LFAMD_TYPE_F32, bp, b->nb[1], n, cp, (long)(dst->nb[1] / sizeof(float)), ctx->ws,
                               ctx->ws_cap, (w->exact_only ? lfamd_exact_flag(a->type) : 0u) | base_flags(), nullptr) != LFAMD_OK) {
                 logf("%s: lfamd_mul_mat: %s\n", "ggml_backend_lfamd", lfamd_last_error());
                 return GGML_STATUS_FAILED;
@@ -621,17 +631,17 @@ bool mul_mat_id_supported(const struct ggml_tensor *op) {
 // the whole expert stack packed back to back under the stack's address (g_mu held)
 const packed *get_packed_stack(backend_ctx *ctx, const struct ggml_tensor *as, packed *tmp) {
     const long rows = (long)as->ne[1], cols = (long)as->ne[0];
-    const int experts = (int)as->ne[2];
-    const size_t one = lfamd_packed_size(as->type, rows, cols);
+    const int experts = (int)as->ne[2], rt = resident_type(as);
+    const size_t one = lfamd_packed_size(rt, rows, cols);
     const uint8_t *as_bytes = weight_bytes(as); // (an expert stack of a row-split buffer stays whole on the first device)
     if (!as_bytes)
         return nullptr;
     const bool keep = as->buffer && g_api->ggml_backend_buffer_get_usage(as->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
     auto it = g_packed.find(as_bytes);
-    if (keep && it != g_packed.end() && it->second.type == as->type && it->second.rows == rows * experts && it->second.cols == cols)
+    if (keep && it != g_packed.end() && it->second.type == rt && it->second.rows == rows * experts && it->second.cols == cols)
         return &it->second;
     packed p;
-    p.bytes = one * experts, p.type = as->type, p.rows = rows * experts, p.cols = cols, p.row_bytes = as->nb[1];
+    p.bytes = one * experts, p.type = rt, p.rows = rows * experts, p.cols = cols, p.row_bytes = as->nb[1];
     if (keep) {
         if (hipMalloc(&p.d, p.bytes) != hipSuccess)
             return nullptr;
@@ -641,7 +651,7 @@ const packed *get_packed_stack(backend_ctx *ctx, const struct ggml_tensor *as, p
         p.d = ctx->scratch;
     }
     for (int e = 0; e < experts; e++)
-        if (lfamd_pack_weights(as->type, rows, cols, as_bytes + (size_t)e * as->nb[2], as->nb[1], (uint8_t *)p.d + (size_t)e * one,
+        if (lfamd_pack_weights(rt, rows, cols, as_bytes + (size_t)e * as->nb[2], as->nb[1], (uint8_t *)p.d + (size_t)e * one,
                                nullptr) != LFAMD_OK) {
             if (keep)
                 (void)hipFree(p.d);
@@ -688,12 +698,13 @@ enum ggml_status run_mul_mat_id(backend_ctx *ctx, struct ggml_tensor *const *dst
             return GGML_STATUS_FAILED;
         plan = (const int32_t *)ctx->plan;
     }
-    const size_t wsb = lfamd_mul_mat_id_workspace(as->type, rows, cols, experts, tokens, thinkers);
+    const int rt = resident_type(as);
+    const size_t wsb = lfamd_mul_mat_id_workspace(rt, rows, cols, experts, tokens, thinkers);
     if (!grow(ctx->ws, ctx->ws_cap, wsb))
         return GGML_STATUS_ALLOC_FAILED;
-    const int rc = count == 1 ? lfamd_mul_mat_id(as->type, wp[0], rows, cols, experts, LFAMD_TYPE_F32, b->data, b->nb[1], tasks, tokens, plan,
+    const int rc = count == 1 ? lfamd_mul_mat_id(rt, wp[0], rows, cols, experts, LFAMD_TYPE_F32, b->data, b->nb[1], tasks, tokens, plan,
                                                  thinkers, rp[0], ctx->ws, ctx->ws_cap, flags, nullptr)
-                              : lfamd_mul_mat_id_multi(as->type, count, wp, rows, cols, experts, LFAMD_TYPE_F32, b->data, b->nb[1], tasks,
+                              : lfamd_mul_mat_id_multi(rt, count, wp, rows, cols, experts, LFAMD_TYPE_F32, b->data, b->nb[1], tasks,
                                                        tokens, plan, thinkers, rp, ctx->ws, ctx->ws_cap, flags, nullptr);
     if (rc != LFAMD_OK) {
         logf("%s: lfamd_mul_mat_id: %s\n", "ggml_backend_lfamd", lfamd_last_error());
@@ -764,10 +775,10 @@ enum ggml_status run_mul_mat_siblings(backend_ctx *ctx, struct ggml_tensor *cons
         const packed *w = get_packed(ctx, a, 0, 0, &tmp);
         if (!w)
             return GGML_STATUS_ALLOC_FAILED;
-        types[j] = a->type, A[j] = w->d, m[j] = (long)a->ne[1], ldc[j] = (long)a->ne[1], C[j] = (float *)dsts[j]->data;
+        types[j] = resident_type(a), A[j] = w->d, m[j] = (long)a->ne[1], ldc[j] = (long)a->ne[1], C[j] = (float *)dsts[j]->data;
         if (w->exact_only)
             flags |= lfamd_exact_flag(a->type);
-        const size_t need = lfamd_mul_mat_workspace(a->type, m[j], k, n);
+        const size_t need = lfamd_mul_mat_workspace(types[j], m[j], k, n);
         wsb = need > wsb ? need : wsb;
     }
     if (!grow(ctx->ws, ctx->ws_cap, wsb))

@@ -48,8 +48,8 @@ hipError_t lfamd_launch_pk_expand(int, const void *, long, long, void *, hipStre
 hipError_t lfamd_launch_pk4x_pack(const void *, size_t, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_pk4x_expand(const void *, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_q80_image(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_get_rows(int, const void *, long, long, const int32_t *, long, long, int, void *, size_t, hipStream_t);
-hipError_t lfamd_launch_unpack(int, const void *, long, long, void *, size_t, hipStream_t);
+hipError_t lfamd_launch_get_rows(int, int, const void *, long, long, const int32_t *, long, long, int, void *, size_t, hipStream_t);
+hipError_t lfamd_launch_unpack(int, int, const void *, long, long, void *, size_t, hipStream_t);
 // activation staging (pack.hip, quantize.hip, blaslt.hip)
 hipError_t lfamd_launch_quantize(int, const float *, long, long, size_t, void *, size_t, hipStream_t);
 hipError_t lfamd_launch_prep_q8k(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);

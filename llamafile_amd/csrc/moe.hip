@@ -132,7 +132,7 @@ static size_t moe_grouped_ws(long cols, long tokens, int thinkers, int experts) 
 extern "C" size_t lfamd_moe_workspace(int type, long rows, long cols, int experts, long tokens, int thinkers) {
     (void)experts;
     const size_t nr = (size_t)tokens * thinkers;
-    const size_t brb = lfamd_row_size(lfamd_vec_dot_type(type), cols);
+    const size_t brb = lfamd_row_size(lfamd_vec_dot_type(type & ~LFAMD_TYPE_PAD256), cols); // (a padded image: activation rows of `cols`)
     const size_t inner = lfamd_mul_mat_workspace_upto(type, rows, cols, (long)nr); // (an expert's batch is any n <= nr)
     size_t host_path = align_up_(nr * brb, 256) + align_up_(nr * (size_t)rows * 4, 256) + align_up_(nr * 4, 256) * 2 +
                        align_up_(inner, 256);

@@ -54,11 +54,13 @@ __global__ void pack_q4k_kernel(const uint8_t *__restrict__ raw, size_t raw_row_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Q4_0 -> P40 (cols % 256 == 0): the P4K nibble image (K-step dword = the 8 codes of k = 16t + 8h + j) and, as
+// Q4_0 -> P40: the P4K nibble image (K-step dword = the 8 codes of k = 16t + 8h + j) and, as
 // header, the eight f16 block scales of the row's 256 weights.  block_q4_0 = {d, qs[16]}: weight l of a block is the
 // low nibble of qs[l] (l < 16) or the high nibble of qs[l - 16]; value d*(q - 8).
+// kb: 32-blocks of a raw row.  kb < 8 nb (LFAMD_TYPE_PAD256): the blocks from kb on are not read and written as zero bytes
+// (d = +0, nibbles 0), for every row of the tile.
 
-__global__ void pack_q40_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb,
+__global__ void pack_q40_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb, int kb,
                                 uint8_t *__restrict__ out, long n_tiles) {
     long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     long tile = tid / 1152;
@@ -79,7 +81,7 @@ __global__ void pack_q40_kernel(const uint8_t *__restrict__ raw, size_t raw_row_
             for (int j = 0; j < 8; j++) {
                 int k = 16 * t + 8 * h + j;
                 int bl = k >> 5, l = k & 31;
-                uint8_t byte = blk[bl].qs[l & 15];
+                uint8_t byte = b * 8 + bl < kb ? blk[bl].qs[l & 15] : (uint8_t)0;
                 uint32_t nib = l < 16 ? (byte & 15u) : (uint32_t)(byte >> 4);
                 v |= nib << (4 * NIBPOS(j));
             }
@@ -92,7 +94,8 @@ __global__ void pack_q40_kernel(const uint8_t *__restrict__ raw, size_t raw_row_
         uint32_t v = 0;
         if (row < rows) {
             const lfamd_block_q4_0 *blk = (const lfamd_block_q4_0 *)(raw + row * raw_row_bytes) + (size_t)b * 8;
-            v = (uint32_t)blk[2 * q].d | ((uint32_t)blk[2 * q + 1].d << 16);
+            const uint32_t lo = b * 8 + 2 * q < kb ? blk[2 * q].d : 0u, hi = b * 8 + 2 * q + 1 < kb ? blk[2 * q + 1].d : 0u;
+            v = lo | (hi << 16);
         }
         dst[1024 + s] = v;
     }
@@ -592,8 +595,11 @@ __global__ __launch_bounds__(NW * 64) void prep_scaled_kernel(const uint8_t *__r
 // quantize_row_q8_0: d = amax/127 stored as f16, q = roundf(x/d)) ->
 //   Xh  [nb][n_pad][256] f16 codes (as above);  d8T [nb*8][n_pad] f32 block scales.  One wave per (super-block, token).
 // Q81: Q8_1 activations (Q4_1 / Q5_1 weights): additionally sT [nb*8][n_pad] = the block's s = f16(d * sum(q)).
-template <bool F32IN, bool Q81>
-__global__ __launch_bounds__(256) void prep80_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long n, long n_pad, int nb,
+// kb: 32-blocks of an activation row.  kb < 8 nb (a padded weight image, LFAMD_TYPE_PAD256): the blocks from kb on are not read —
+// what lies behind the row may be NaN — and staged as a row of zeros: codes, d and s all 0.  The eight lanes of a 32-block take the
+// same side, so the shuffles below stay among lanes that all loaded.  TAIL = false (whole rows, kb = 8 nb): the kernel as it was.
+template <bool F32IN, bool Q81, bool TAIL>
+__global__ __launch_bounds__(256) void prep80_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long n, long n_pad, int nb, int kb,
                                                     _Float16 *__restrict__ Xh, float *__restrict__ d8T, float *__restrict__ sT) {
     typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
     long blk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -604,7 +610,7 @@ __global__ __launch_bounds__(256) void prep80_kernel(const uint8_t *__restrict__
     int t = threadIdx.x & 63; // codes 4t..4t+3 of the super-block: 32-block t >> 3
     int q[4] = {0, 0, 0, 0};
     float d = 0.0f, sv = 0.0f;
-    if (tok < n) {
+    if (tok < n && (!TAIL || b * 8 + (t >> 3) < kb)) {
         if constexpr (F32IN) {
             const float4 f = *(const float4 *)((const float *)(X + tok * x_row_bytes) + (size_t)b * 256 + 4 * t);
             const float v[4] = {f.x, f.y, f.z, f.w};
@@ -712,11 +718,12 @@ hipError_t lfamd_launch_pack_q4k(const void *raw, size_t raw_row_bytes, long row
     return hipGetLastError();
 }
 
+// (cols: of a raw row, whole 32-blocks; the image has ceil(cols / 256) super-blocks per row)
 hipError_t lfamd_launch_pack_q40(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
-    int nb = (int)(cols / 256);
+    int nb = (int)((cols + 255) / 256);
     long n_tiles = ((rows + 31) / 32) * nb;
     long threads = n_tiles * 1152;
-    pack_q40_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb,
+    pack_q40_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb, (int)(cols / 32),
                                                                         (uint8_t *)out, n_tiles);
     return hipGetLastError();
 }
@@ -791,25 +798,30 @@ hipError_t lfamd_launch_prep_f32(const void *X, size_t x_row_bytes, long n, long
     return hipGetLastError();
 }
 
+// (cols: of an activation row, whole 32-blocks; the image has ceil(cols / 256) super-blocks per token)
 hipError_t lfamd_launch_prep80(int Btype, const void *B, size_t b_row_bytes, long n, long n_pad, long cols, void *Xh, void *d8T,
                                void *sT, hipStream_t s) {
-    int nb = (int)(cols / 256);
+    int nb = (int)((cols + 255) / 256), kb = (int)(cols / 32);
     long blocks = n_pad * nb;
     if (blocks == 0)
         return hipSuccess;
     const unsigned grid = (unsigned)((blocks + 3) / 4);
     const uint8_t *X = (const uint8_t *)B;
+    const bool f32 = Btype == LFAMD_TYPE_F32, tail = kb != 8 * nb;
+#define PREP80_GO(F32IN, Q81, TAIL)                                                                                    \
+    prep80_kernel<F32IN, Q81, TAIL><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, kb, (_Float16 *)Xh, (float *)d8T, (float *)sT)
     if (sT) { // Q8_1 activations
-        if (Btype == LFAMD_TYPE_F32)
-            prep80_kernel<true, true><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (_Float16 *)Xh, (float *)d8T, (float *)sT);
+        if (f32)
+            tail ? PREP80_GO(true, true, true) : PREP80_GO(true, true, false);
         else
-            prep80_kernel<false, true><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (_Float16 *)Xh, (float *)d8T, (float *)sT);
+            tail ? PREP80_GO(false, true, true) : PREP80_GO(false, true, false);
     } else {
-        if (Btype == LFAMD_TYPE_F32)
-            prep80_kernel<true, false><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (_Float16 *)Xh, (float *)d8T, nullptr);
+        if (f32)
+            tail ? PREP80_GO(true, false, true) : PREP80_GO(true, false, false);
         else
-            prep80_kernel<false, false><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (_Float16 *)Xh, (float *)d8T, nullptr);
+            tail ? PREP80_GO(false, false, true) : PREP80_GO(false, false, false);
     }
+#undef PREP80_GO
     return hipGetLastError();
 }
 

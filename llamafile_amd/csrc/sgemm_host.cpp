@@ -359,6 +359,7 @@ struct DevWeights {
     bool exact_only;
 };
 
+// (type: the resident id, lfamd_resident_type)
 bool get_weights(int type, const void *A, long rows, long cols, size_t row_bytes, DevWeights *out) {
     const size_t total = (size_t)rows * row_bytes;
     const size_t packed = g.api.packed_size(type, rows, cols);
@@ -448,6 +449,10 @@ bool run_mul_mat(int Atype, const void *A, long m, long kelems, size_t a_row_byt
                  size_t b_row_bytes, long n, float *C, long ldc) {
     if (m == 0 || n == 0)
         return true;
+    // the device copy is this plug-in's own: legacy 32-block rows that are not whole 256-weight groups are kept as the padded tile
+    // image (LFAMD_TYPE_PAD256), which the decode GEMV and the MFMA batches serve instead of the generic kernel
+    const int host_type = Atype;
+    Atype = lfamd_resident_type(Atype, kelems);
     DevWeights w;
     if (!get_weights(Atype, A, m, kelems, a_row_bytes, &w))
         return false;
@@ -463,7 +468,7 @@ bool run_mul_mat(int Atype, const void *A, long m, long kelems, size_t a_row_byt
     if (n == 1 && zero_copy && reserve_host(g_hb, bbytes) && reserve_host(g_hc, cbytes)) {
         memcpy(g_hb.p, B, bbytes);
         if (g.api.mul_mat(Atype, w.d_packed, m, kelems, Btype, g_hb.p, b_row_bytes, n, (float *)g_hc.p, ldc, g.ws.p, g.ws.cap,
-                          flags_now() | (w.exact_only ? lfamd_exact_flag(Atype) : 0u), nullptr) != LFAMD_OK)
+                          flags_now() | (w.exact_only ? lfamd_exact_flag(host_type) : 0u), nullptr) != LFAMD_OK)
             return false;
         if (g.api.sync(nullptr) != LFAMD_OK)
             return false;
@@ -478,7 +483,7 @@ bool run_mul_mat(int Atype, const void *A, long m, long kelems, size_t a_row_byt
         if (g.api.h2d(g.c.p, C, cbytes, nullptr) != LFAMD_OK)
             return false;
     if (g.api.mul_mat(Atype, w.d_packed, m, kelems, Btype, g.b.p, b_row_bytes, n, (float *)g.c.p, ldc, g.ws.p, g.ws.cap,
-                      flags_now() | (w.exact_only ? lfamd_exact_flag(Atype) : 0u), nullptr) != LFAMD_OK)
+                      flags_now() | (w.exact_only ? lfamd_exact_flag(host_type) : 0u), nullptr) != LFAMD_OK)
         return false;
     if (g.api.d2h(C, g.c.p, cbytes, nullptr) != LFAMD_OK)
         return false;
@@ -670,7 +675,8 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
         return true;
 
     std::lock_guard<std::mutex> lk(g.mu);
-    const size_t packed = g.api.packed_size(wt, rows, cols);
+    const int rt = lfamd_resident_type(wt, cols); // (the id of the device copy: get_weights)
+    const size_t packed = g.api.packed_size(rt, rows, cols);
     // experts packed back to back in one device allocation; kept across calls only when the host bytes are immutable
     // (registered, or a read-only mapping), otherwise packed into scratch on every call — like get_weights
     DevWeights w{nullptr, false};
@@ -679,7 +685,7 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
         Origin origin;
         const bool keep = is_immutable(weights->data, span, &origin);
         auto it = g.cache.find(weights->data);
-        if (it != g.cache.end() && !(keep && it->second.type == wt && it->second.rows == rows * experts && it->second.cols == cols &&
+        if (it != g.cache.end() && !(keep && it->second.type == rt && it->second.rows == rows * experts && it->second.cols == cols &&
                                      it->second.row_bytes == weights->nb[1] && it->second.origin.same(origin))) {
             drop(it);
             it = g.cache.end();
@@ -707,7 +713,7 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
                 size_t ebytes = (size_t)rows * weights->nb[1];
                 if (!reserve(g.raw, ebytes) ||
                     g.api.h2d(g.raw.p, (const uint8_t *)weights->data + (size_t)e * weights->nb[2], ebytes, nullptr) ||
-                    g.api.pack_weights(wt, rows, cols, g.raw.p, weights->nb[1], (uint8_t *)dst + (size_t)e * packed, nullptr) ||
+                    g.api.pack_weights(rt, rows, cols, g.raw.p, weights->nb[1], (uint8_t *)dst + (size_t)e * packed, nullptr) ||
                     g.api.sync(nullptr))
                     die("expert weight upload failed");
             }
@@ -719,7 +725,7 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
                 die("expert weight range check failed");
             w = {dst, in_range == 0};
             if (keep) {
-                CachedWeights nw{wt, rows * experts, cols, weights->nb[1], dst, bytes, in_range == 0};
+                CachedWeights nw{rt, rows * experts, cols, weights->nb[1], dst, bytes, in_range == 0};
                 nw.origin = origin;
                 g.lru.push_front(weights->data);
                 nw.lru = g.lru.begin();
@@ -760,12 +766,12 @@ bool llamafile_mixmul(const struct ggml_compute_params *params, const struct ggm
             hplan[(size_t)t * thinkers + th] =
                 *(const int32_t *)((const uint8_t *)plan->data + (size_t)t * plan->nb[1] + (size_t)th * plan->nb[0]);
     size_t rbytes = (size_t)tokens * thinkers * rows * 4;
-    size_t wsb = g.api.mul_mat_id_workspace(wt, rows, cols, experts, tokens, thinkers);
+    size_t wsb = g.api.mul_mat_id_workspace(rt, rows, cols, experts, tokens, thinkers);
     if (!reserve(g.plan, hplan.size() * 4) || !reserve(g.c, rbytes) || !reserve(g.ws, wsb))
         die("device allocation failed");
     if (g.api.h2d(g.plan.p, hplan.data(), hplan.size() * 4, nullptr) || g.api.sync(nullptr))
         die("plan upload failed");
-    if (g.api.mul_mat_id(wt, w.d_packed, rows, cols, experts, bt, g.b.p, brow, tasks, tokens, (const int32_t *)g.plan.p,
+    if (g.api.mul_mat_id(rt, w.d_packed, rows, cols, experts, bt, g.b.p, brow, tasks, tokens, (const int32_t *)g.plan.p,
                          thinkers, (float *)g.c.p, g.ws.p, g.ws.cap, flags_now() | (w.exact_only ? lfamd_exact_flag(wt) : 0u), nullptr))
         die("device mul_mat_id failed");
     std::vector<float> &hres = g.h_out;

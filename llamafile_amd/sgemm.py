@@ -69,7 +69,7 @@ class PackedWeights:
     def nbytes(self) -> int:
         """ALGORITHMIC bytes: the tensor's size in the GGUF file (what one pass over the weights has to read at least).  The
         resident image may be larger (Q3_K, IQ4_XS, Q4_1 / Q5_0 / Q5_1; Q8_0 only in a process that opted into the vendor GEMM): `resident_bytes`."""
-        return self.rows * T.row_size(self.type, self.cols)
+        return self.rows * T.row_size(self.type & ~_hip.TYPE_PAD256, self.cols)
 
     @property
     def resident_bytes(self) -> int:
@@ -82,7 +82,8 @@ def init(device: int = 0) -> None:
 
 
 def upload_weights(t: int, raw, rows: int, cols: int, device="cuda") -> PackedWeights:
-    """raw: uint8 [rows, row_bytes] (numpy or torch) in GGUF layout -> packed device tensor."""
+    """raw: uint8 [rows, row_bytes] (numpy or torch) in GGUF layout -> packed device tensor.  t may carry _hip.TYPE_PAD256 (a legacy
+    32-block type kept as the tile image at any row length of whole 32-blocks); every call on the result then passes it on."""
     L = _hip.lib()
     if isinstance(raw, np.ndarray):
         raw = torch.from_numpy(np.ascontiguousarray(raw))
@@ -135,7 +136,7 @@ def dequantize(W: PackedWeights, out_dtype: torch.dtype = torch.float32) -> torc
 
 def unpack_weights(W: PackedWeights) -> torch.Tensor:
     """The inverse of upload_weights: uint8 [rows, row_bytes], the tensor's GGUF bytes (lfamd_unpack_weights)."""
-    rb = T.row_size(W.type, W.cols)
+    rb = T.row_size(W.type & ~_hip.TYPE_PAD256, W.cols)  # (a padded image, _hip.TYPE_PAD256: the rows come back at their own length)
     raw = torch.empty((W.rows, rb), dtype=torch.uint8, device=W.data.device)
     _hip.check(_hip.lib().lfamd_unpack_weights(W.type, W.rows, W.cols, _ptr(W.data), _ptr(raw), rb, _stream()), "lfamd_unpack_weights")
     return raw

@@ -21,17 +21,19 @@ EXTRA_FLAGS = 0
 
 
 def run(tname, m, k, n, copies, iters, f32in=True, graph=True):
-    t = T.BY_NAME[tname]
+    # "<type>+PAD256": the legacy 32-block type resident as the padded tile image (lfamd_hip.h, LFAMD_TYPE_PAD256)
+    base = T.BY_NAME[tname.split("+")[0]]
+    t = base | (_hip.TYPE_PAD256 if tname.endswith("+PAD256") else 0)
     L = _hip.lib()
-    per = m * T.row_size(t, k)
+    per = m * T.row_size(base, k)
     if copies <= 0:
         copies = max(1, min(64, int(600e6 // per) + 1))
     Ws = []
-    raw = synth.random_weights_torch(t, m, k, 1)
+    raw = synth.random_weights_torch(base, m, k, 1)
     for c in range(copies):
         Ws.append(sgemm.upload_weights(t, raw, m, k))
     x = torch.rand((n, k), device="cuda") * 2 - 1
-    vdt = T.VEC_DOT[t]
+    vdt = T.VEC_DOT[base]
     if f32in:
         B, bt, brb = x, T.F32, k * 4
     else:
@@ -68,7 +70,7 @@ def run(tname, m, k, n, copies, iters, f32in=True, graph=True):
     us = e0.elapsed_time(e1) * 1e3 / (iters * copies)
     byts = per + n * k * 4 + n * m * 4
     flops = 2.0 * m * k * n
-    print(f"{tname:6s} m={m:6d} k={k:6d} n={n:4d} copies={copies:3d}: {us:9.2f} us/launch  "
+    print(f"{tname:13s} m={m:6d} k={k:6d} n={n:4d} copies={copies:3d}: {us:9.2f} us/launch  "
           f"{byts / us / 1e3:8.1f} GB/s  {flops / us / 1e6:8.1f} TFLOP/s", flush=True)
     return us
 
