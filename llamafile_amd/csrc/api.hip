@@ -113,144 +113,40 @@ int lfamd_stream_sync(void *stream) {
 // ---------------------------------------------------------------------------------------------
 
 // LFAMD_TYPE_PAD256 (include/lfamd_hip.h): a layout modifier OR-ed into a legacy 32-block weight type.  This file is where it ends:
-// the launchers below it get the base type, the weight geometry (image_cols: the columns of the resident image) and the activation
-// length (the call's own k) as separate values.
-static int base_of(int t) {
-    return t & ~LFAMD_TYPE_PAD256;
-}
-static bool padded_id(int t) {
-    return (t & LFAMD_TYPE_PAD256) != 0;
-}
-static long image_cols(int t, long k) {
-    return padded_id(t) ? (k + 255) / 256 * 256 : k;
-}
-
-static bool type_known(int t) {
-    if (padded_id(t)) { // the types with a tile image to pad; on any other the modifier makes an unknown id
-        const int b = base_of(t);
-        return b == LFAMD_TYPE_Q4_0 || b == LFAMD_TYPE_IQ4_NL || b == LFAMD_TYPE_Q4_1 || b == LFAMD_TYPE_Q5_0 || b == LFAMD_TYPE_Q5_1;
-    }
-    switch (t) {
-    case LFAMD_TYPE_F32:
-    case LFAMD_TYPE_F16:
-    case LFAMD_TYPE_BF16:
-    case LFAMD_TYPE_Q4_0:
-    case LFAMD_TYPE_Q4_1:
-    case LFAMD_TYPE_Q5_0:
-    case LFAMD_TYPE_Q5_1:
-    case LFAMD_TYPE_Q8_0:
-    case LFAMD_TYPE_Q2_K:
-    case LFAMD_TYPE_Q3_K:
-    case LFAMD_TYPE_Q4_K:
-    case LFAMD_TYPE_Q5_K:
-    case LFAMD_TYPE_Q6_K:
-    case LFAMD_TYPE_IQ4_XS:
-    case LFAMD_TYPE_IQ4_NL:
-        return true;
-    default:
-        return false;
-    }
-}
+// lfamd_image_of (lfamd_internal.h) splits an id into the base type and the weight geometry (the columns of the resident image); the
+// launchers below this file get those and the activation length (the call's own k) as separate values.
 
 // Q8_0: bytes of the P80 image (256-aligned: the PC8 image starts behind it)
 static size_t q80_p80_bytes(long rows, long cols) {
     return align_up((size_t)((rows + 7) / 8) * (size_t)((cols / 32 + 3) / 4) * P80_TILE, 256);
 }
 
+// Tiles x tile bytes, or rows x row size.  Q8_0, P80, is the ONE resident image (1.0625 bytes per weight, the file's): the bit-exact
+// vecdot GEMV, the exact batch kernel and the f16 MFMA batch body (gemm_lf.hip) all read it.  A host that opted into the vendor GEMM
+// (LFAMD_USE_BLASLT=1) also keeps the plain f16(d * q) rows that library needs behind it (3.1 bytes per weight).
 size_t lfamd_packed_size(int type, long rows, long cols) {
-    if (!type_known(type) || rows < 0 || cols < 0 || cols % lfamd_blck_size(base_of(type)))
+    const lfamd_image im = lfamd_image_of(type, cols);
+    if (im.ly == LY_NONE || rows < 0 || cols < 0 || cols % lfamd_blck_size(im.type))
         return 0;
-    if (padded_id(type)) // the image of the rows continued with zero blocks to whole 256-weight groups
-        return lfamd_packed_size(base_of(type), rows, image_cols(type, cols));
-    switch (type) {
-    case LFAMD_TYPE_Q4_K:
-        return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P4K_TILE;
-    case LFAMD_TYPE_Q4_0:
-    case LFAMD_TYPE_IQ4_NL: // (Q4_0's block shape: the same image, the nibbles are codebook indices)
-        if (cols % 256 == 0) // P40; other row lengths stay RAW (generic kernels)
-            return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P4K_TILE;
-        return (size_t)rows * lfamd_row_size(type, cols);
-    case LFAMD_TYPE_Q5_K:
-        return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P5K_TILE;
-    case LFAMD_TYPE_Q6_K:
-        return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P6K_TILE;
-    case LFAMD_TYPE_Q8_0: // P80, the ONE resident image (1.0625 bytes per weight, the file's): the bit-exact vecdot GEMV, the exact
-                          // batch kernel and the f16 MFMA batch body (gemm_lf.hip) all read it.  A host that opted into the vendor GEMM
-                          // (LFAMD_USE_BLASLT=1) also keeps the plain f16(d * q) rows that library needs (3.1 bytes per weight)
-        if (lfamd_blaslt_ok())
-            return q80_p80_bytes(rows, cols) + (size_t)rows * (size_t)cols * 2;
-        return q80_p80_bytes(rows, cols);
-    case LFAMD_TYPE_Q2_K:
-    case LFAMD_TYPE_Q3_K: // PK2 / PK3: compact images (84 / 116 bytes per 256 weights) the decode GEMV reads; batches expand them
-        return lfamd_pk_bytes(type, rows, cols); // into the canonical PCK image in the workspace, per call
-    case LFAMD_TYPE_IQ4_XS: // codebook indices on the P4K nibble lattice + 16 header bytes per row (144 bytes per 256 weights, 1.06 x
-                            // the file); batches expand it per call into the PC8 byte image in the workspace
-        return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * P4K_TILE;
-    case LFAMD_TYPE_Q4_1:
-    case LFAMD_TYPE_Q5_0:
-    case LFAMD_TYPE_Q5_1:
-        if (cols % 256 == 0) // PCL; other row lengths stay RAW (generic kernels)
-            return lfamd_wprep32_bytes(rows, cols);
-        return (size_t)rows * lfamd_row_size(type, cols);
-    default:
-        return (size_t)rows * lfamd_row_size(type, cols);
-    }
+    if (im.ly == LY_P80)
+        return q80_p80_bytes(rows, cols) + (lfamd_blaslt_ok() ? (size_t)rows * (size_t)cols * 2 : 0);
+    return im.tile ? im.tiles(rows) * (size_t)im.tile : (size_t)rows * lfamd_row_size(im.type, cols);
 }
 
 int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t raw_row_bytes, void *d_packed,
                        void *stream) {
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
-    if (!type_known(type))
+    const lfamd_image im = lfamd_image_of(type, cols); // (the 32-block types' tile image: its packer writes a row's padded tail)
+    if (im.ly == LY_NONE)
         return fail(LFAMD_ERR_UNSUPPORTED, "pack_weights: unsupported ggml type%s", "");
-    const bool tiled = padded_id(type) || cols % 256 == 0; // (the 32-block types: the tile image; its launchers write a row's padded tail)
-    type = base_of(type);
-    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || raw_row_bytes < lfamd_row_size(type, cols))
+    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(im.type) || raw_row_bytes < lfamd_row_size(im.type, cols))
         return fail(LFAMD_ERR_INVALID, "pack_weights: bad shape%s", "");
     if (rows == 0 || cols == 0)
         return LFAMD_OK;
     hipStream_t s = (hipStream_t)stream;
-    switch (type) {
-    case LFAMD_TYPE_Q4_K:
-        HIPCHK(lfamd_launch_pack_q4k(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q4k");
-        break;
-    case LFAMD_TYPE_Q4_0:
-    case LFAMD_TYPE_IQ4_NL:
-        if (tiled) {
-            HIPCHK(lfamd_launch_pack_q40(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q40");
-        } else {
-            HIPCHK(lfamd_launch_pack_raw(d_raw, raw_row_bytes, rows, lfamd_row_size(type, cols), d_packed, s), "pack_raw");
-        }
-        break;
-    case LFAMD_TYPE_Q5_K:
-        HIPCHK(lfamd_launch_pack_q5k(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q5k");
-        break;
-    case LFAMD_TYPE_Q6_K:
-        HIPCHK(lfamd_launch_pack_q6k(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q6k");
-        break;
-    case LFAMD_TYPE_Q8_0:
-        HIPCHK(lfamd_launch_pack_q80(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_q80");
-        if (lfamd_blaslt_ok())
-            HIPCHK(lfamd_launch_q80_image(d_raw, raw_row_bytes, rows, cols, (uint8_t *)d_packed + q80_p80_bytes(rows, cols), s), "pack_f16 (Q8_0)");
-        break;
-    case LFAMD_TYPE_Q2_K:
-    case LFAMD_TYPE_Q3_K:
-        HIPCHK(lfamd_launch_pk_pack(type, d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_pk");
-        break;
-    case LFAMD_TYPE_IQ4_XS:
-        HIPCHK(lfamd_launch_pk4x_pack(d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_pk4x");
-        break;
-    case LFAMD_TYPE_Q4_1:
-    case LFAMD_TYPE_Q5_0:
-    case LFAMD_TYPE_Q5_1:
-        if (tiled) {
-            HIPCHK(lfamd_launch_wprep32(type, d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_pcl");
-        } else {
-            HIPCHK(lfamd_launch_pack_raw(d_raw, raw_row_bytes, rows, lfamd_row_size(type, cols), d_packed, s), "pack_raw");
-        }
-        break;
-    default:
-        HIPCHK(lfamd_launch_pack_raw(d_raw, raw_row_bytes, rows, lfamd_row_size(type, cols), d_packed, s), "pack_raw");
-    }
+    HIPCHK(lfamd_launch_pack(im, d_raw, raw_row_bytes, rows, cols, d_packed, s), "pack_weights");
+    if (im.ly == LY_P80 && lfamd_blaslt_ok())
+        HIPCHK(lfamd_launch_q80_image(d_raw, raw_row_bytes, rows, cols, (uint8_t *)d_packed + q80_p80_bytes(rows, cols), s), "pack_f16 (Q8_0)");
     return LFAMD_OK;
 }
 
@@ -259,10 +155,10 @@ int lfamd_pack_weights(int type, long rows, long cols, const void *d_raw, size_t
 int lfamd_get_rows(int type, const void *d_packed, long rows, long cols, const int32_t *d_ids, long row0, long n_ids, int out_type,
                    void *d_out, size_t out_row_bytes, void *stream) {
     (void)hipGetLastError(); // (as lfamd_pack_weights)
-    if (!type_known(type))
+    const lfamd_image im = lfamd_image_of(type, cols);
+    if (im.ly == LY_NONE)
         return fail(LFAMD_ERR_UNSUPPORTED, "get_rows: unsupported ggml type%s", "");
-    const int tiled = padded_id(type) ? 1 : 0;
-    type = base_of(type);
+    type = im.type;
     if (out_type != LFAMD_TYPE_F32 && out_type != LFAMD_TYPE_F16)
         return fail(LFAMD_ERR_UNSUPPORTED, "get_rows: out_type must be F32 or F16%s", "");
     if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || n_ids < 0)
@@ -278,30 +174,30 @@ int lfamd_get_rows(int type, const void *d_packed, long rows, long cols, const i
         return fail(LFAMD_ERR_INVALID, "get_rows: null pointer%s", "");
     if ((uintptr_t)d_out % esz)
         return fail(LFAMD_ERR_INVALID, "get_rows: d_out %s", "not aligned to the element");
-    HIPCHK(lfamd_launch_get_rows(type, tiled, d_packed, rows, cols, d_ids, d_ids ? 0 : row0, n_ids, out_type, d_out, out_row_bytes, (hipStream_t)stream),
+    HIPCHK(lfamd_launch_get_rows(im, d_packed, rows, cols, d_ids, d_ids ? 0 : row0, n_ids, out_type, d_out, out_row_bytes, (hipStream_t)stream),
            "get_rows");
     return LFAMD_OK;
 }
 
 int lfamd_unpack_weights(int type, long rows, long cols, const void *d_packed, void *d_raw, size_t raw_row_bytes, void *stream) {
     (void)hipGetLastError();
-    if (!type_known(type))
+    const lfamd_image im = lfamd_image_of(type, cols);
+    if (im.ly == LY_NONE)
         return fail(LFAMD_ERR_UNSUPPORTED, "unpack_weights: unsupported ggml type%s", "");
-    const int tiled = padded_id(type) ? 1 : 0;
-    type = base_of(type);
+    type = im.type;
     if (rows < 0 || cols < 0 || cols % lfamd_blck_size(type) || raw_row_bytes < lfamd_row_size(type, cols))
         return fail(LFAMD_ERR_INVALID, "unpack_weights: bad shape%s", "");
     if (rows == 0 || cols == 0)
         return LFAMD_OK;
     if (!d_packed || !d_raw)
         return fail(LFAMD_ERR_INVALID, "unpack_weights: null pointer%s", "");
-    HIPCHK(lfamd_launch_unpack(type, tiled, d_packed, rows, cols, d_raw, raw_row_bytes, (hipStream_t)stream), "unpack_weights");
+    HIPCHK(lfamd_launch_unpack(im, d_packed, rows, cols, d_raw, raw_row_bytes, (hipStream_t)stream), "unpack_weights");
     return LFAMD_OK;
 }
 
 int lfamd_scaled_gemm_ok(int type, long rows, long cols, const void *d_packed, void *stream) {
     (void)hipGetLastError();
-    if (!type_known(type))
+    if (!lfamd_type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "scaled_gemm_ok: unsupported ggml type%s", "");
     if ((type != LFAMD_TYPE_Q4_K && type != LFAMD_TYPE_Q5_K && type != LFAMD_TYPE_Q6_K && type != LFAMD_TYPE_Q8_0) || rows <= 0 || cols <= 0)
         return 1;
@@ -341,24 +237,11 @@ int lfamd_quantize_rows(int vec_dot_type, const float *d_x, long nrows, long col
 // _takes_staged, _takes_staged_scaled, _takes_staged_b32, _takes_staged_q80 and _workspace read the same plan.  DESIGN.md "Dispatch" has the table.  The plan makes no
 // HIP call (lfamd_blaslt_ok() touches the device only when a host opted into the vendor library, LFAMD_USE_BLASLT=1).
 
-// Q4_0 / IQ4_NL rows that are whole 256-weight groups are kept in the P40 layout and served by the tuned kernels
-static bool packed40(int Atype, long k) {
-    return (Atype == LFAMD_TYPE_Q4_0 || Atype == LFAMD_TYPE_IQ4_NL) && k % 256 == 0;
-}
-// legacy 32-block types whose rows are whole 256-weight groups (Q4_1, Q5_0, Q5_1): resident PCL image
-static bool packed_pcl(int Atype, long k) {
-    return k % 256 == 0 && (Atype == LFAMD_TYPE_Q4_1 || Atype == LFAMD_TYPE_Q5_0 || Atype == LFAMD_TYPE_Q5_1);
-}
 static bool kquant(int Atype) {
     return Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K;
 }
 static bool float_type(int Atype) {
     return Atype == LFAMD_TYPE_F32 || Atype == LFAMD_TYPE_F16 || Atype == LFAMD_TYPE_BF16;
-}
-// weights in a layout only the tuned kernels read: the decode GEMVs take them, the generic kernels do not
-static bool packed(int Atype, long k) {
-    return kquant(Atype) || Atype == LFAMD_TYPE_Q8_0 || Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K || Atype == LFAMD_TYPE_IQ4_XS ||
-           packed40(Atype, k) || packed_pcl(Atype, k);
 }
 // F16 / BF16 matrices the loader-wave body can address (32-bit byte offsets)
 static bool float_lf_fits(int Atype, long m, long k) {
@@ -440,16 +323,17 @@ static bool q80_relaxed(int Atype, long k, long n, unsigned flags) {
 }
 
 static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
-    if (padded_id(Atype)) // the padded image: the route, the answers and the workspace of the base type on rows of whole groups
-        return plan_mul_mat(base_of(Atype), m, image_cols(Atype, k), n, flags);
+    const lfamd_image im = lfamd_image_of(Atype, k);
+    if (im.type != Atype) // the padded image: the route, the answers and the workspace of the base type on rows of whole groups
+        return plan_mul_mat(im.type, m, im.cols, n, flags);
     const unsigned forced = flags & (LFAMD_FLAG_GEMM_NARROW | LFAMD_FLAG_GEMM_WIDE | LFAMD_FLAG_GEMM_PLAIN); // (a module body, by name)
     const bool f16_q80 = !(flags & (LFAMD_FLAG_PRECISE | LFAMD_FLAG_Q80_EXACT));
     mm_plan p = {mm_body::generic, false, true, false, false, 0};
     if (flags & LFAMD_FLAG_FORCE_GENERIC)
-        p.body = packed(Atype, k) ? mm_body::refused : mm_body::generic;
+        p.body = im.tuned() ? mm_body::refused : mm_body::generic;
     else if (sb_takes(Atype, m, k, n, flags))
         p.body = mm_body::sb;
-    else if (n > 8 && (kquant(Atype) || packed40(Atype, k))) {
+    else if (n > 8 && (kquant(Atype) || im.p40())) {
         if (i8_takes(Atype, k, n, flags, (m + 127) / 128))
             p.body = mm_body::i8;
         else if (Atype == LFAMD_TYPE_Q4_0 || Atype == LFAMD_TYPE_IQ4_NL)
@@ -473,7 +357,7 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
                                          : mm_body::float_wide;
     else if (n <= 8 && float_type(Atype) && lfamd_gemv_float_ok(Atype, k, n))
         p.body = mm_body::gemv_float;
-    else if (n > 8 && packed_pcl(Atype, k))
+    else if (n > 8 && im.pcl())
         p.body = mm_body::canon32;
     else if (n > 8 && (Atype == LFAMD_TYPE_Q2_K || Atype == LFAMD_TYPE_Q3_K || Atype == LFAMD_TYPE_IQ4_XS)) {
         p.body = mm_body::canon;
@@ -483,7 +367,7 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
                  : f16_q80 && k % 128 == 0 && !lfamd_blaslt_ok() ? mm_body::q80_lf
                                                                  : mm_body::q80_exact;
         p.exact = p.body == mm_body::q80_exact;
-    } else if (n <= 8 && packed(Atype, k)) {
+    } else if (n <= 8 && im.tuned()) {
         p.body = mm_body::gemv;
         p.relaxed = q80_relaxed(Atype, k, n, flags);
     }
@@ -535,7 +419,7 @@ static mm_plan plan_mul_mat(int Atype, long m, long k, long n, unsigned flags) {
 }
 
 int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+    if (!lfamd_type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
     return plan_mul_mat(Atype, m, k, n, flags).exact ? 1 : 0;
 }
@@ -543,7 +427,7 @@ int lfamd_mul_mat_is_exact(int Atype, long m, long k, long n, unsigned flags) {
 // Does the call reproduce the CPU reference's bits (tinyBLAS_Q0's f32 chain for Q8_0)?  Read from the plan the launch reads: 0 for
 // a Q8_0 decode call that LFAMD_FLAG_Q80_RELAXED moves to the relaxed-order kernel, 1 for the same call where that kernel declines.
 int lfamd_mul_mat_is_bit_exact(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+    if (!lfamd_type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
     return plan_mul_mat(Atype, m, k, n, flags).bit_exact ? 1 : 0;
 }
@@ -551,7 +435,7 @@ int lfamd_mul_mat_is_bit_exact(int Atype, long m, long k, long n, unsigned flags
 // Does a call accept the scaled-operand staged image a fused producer wrote (LFAMD_TYPE_STAGED_SCALED)?  The K-quant batches whose
 // body reads it: what lfamd_mul_mat would stage with prep_scaled_kernel itself.
 int lfamd_mul_mat_takes_staged_scaled(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+    if (!lfamd_type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
     const mm_plan p = plan_mul_mat(Atype, m, k, n, flags);
     return p.body == mm_body::wide && p.scaled ? 1 : 0;
@@ -559,7 +443,7 @@ int lfamd_mul_mat_takes_staged_scaled(int Atype, long m, long k, long n, unsigne
 
 // Does a call accept the staged image a fused producer wrote (LFAMD_TYPE_STAGED_Q8K)?  Exactly the calls that run the int8 body.
 int lfamd_mul_mat_takes_staged(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+    if (!lfamd_type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
     return plan_mul_mat(Atype, m, k, n, flags).body == mm_body::i8 ? 1 : 0;
 }
@@ -567,9 +451,9 @@ int lfamd_mul_mat_takes_staged(int Atype, long m, long k, long n, unsigned flags
 // Does a call accept the 32-block staged image a fused producer wrote (LFAMD_TYPE_STAGED_B32)?  The batches of the legacy 32-block
 // types on the 128 x 128 body: what lfamd_mul_mat would stage with prep80_kernel itself.
 int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+    if (!lfamd_type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
-    if (image_cols(Atype, k) != k) // (the producers write rows of whole 256-weight groups)
+    if (lfamd_image_of(Atype, k).cols != k) // (the producers write rows of whole 256-weight groups)
         return 0;
     const mm_body b = plan_mul_mat(Atype, m, k, n, flags).body;
     return b == mm_body::q40_wide || b == mm_body::canon32 ? 1 : 0;
@@ -578,14 +462,14 @@ int lfamd_mul_mat_takes_staged_b32(int Atype, long m, long k, long n, unsigned f
 // Does a call accept the image of the Q8_0-weight loader-wave body a fused producer wrote (LFAMD_TYPE_STAGED_Q80)?  The Q8_0 batches
 // on gemm_lf_q80 (what lfamd_mul_mat would stage with lf_tok_scale_kernel and prep_lf_kernel itself) whose P80 image the loaders can address.
 int lfamd_mul_mat_takes_staged_q80(int Atype, long m, long k, long n, unsigned flags) {
-    if (!type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
+    if (!lfamd_type_known(Atype) || m <= 0 || k <= 0 || n <= 0)
         return 0;
     return plan_mul_mat(Atype, m, k, n, flags).body == mm_body::q80_lf && lfamd_gemm_lf_q80_fits(m, k) ? 1 : 0;
 }
 
 // The largest workspace of the bodies this call can run: the default one and any a testing flag can force.
 size_t lfamd_mul_mat_workspace(int Atype, long m, long k, long n) {
-    if (!type_known(Atype))
+    if (!lfamd_type_known(Atype))
         return 0;
     size_t best = 0;
     for (unsigned f : {0u, (unsigned)LFAMD_FLAG_PRECISE, (unsigned)LFAMD_FLAG_Q80_EXACT, (unsigned)LFAMD_FLAG_GEMM_NARROW,
@@ -662,16 +546,16 @@ static int check_operands(const char *who, bool quantised, int Btype, const void
 // Everything lfamd_mul_mat checks before its first launch: LFAMD_OK and the plan, or the error the call returns.
 static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, size_t b_row_bytes, long n, long ldc, const void *d_ws,
                          size_t ws_bytes, unsigned flags, mm_plan &p) {
-    if (!type_known(Atype))
+    if (!lfamd_type_known(Atype))
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: unsupported weight type%s", "");
-    if (m < 0 || n < 0 || k < 0 || ldc < m || k % lfamd_blck_size(base_of(Atype)))
+    if (m < 0 || n < 0 || k < 0 || ldc < m || k % lfamd_blck_size(lfamd_base_type(Atype)))
         return fail(LFAMD_ERR_INVALID, "mul_mat: bad shape%s", "");
     const bool staged = staged_type(Btype);
     if (!staged) {
         if (float_type(Atype)) {
             if (!(Btype == LFAMD_TYPE_F32 || Btype == Atype))
                 return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: float weights need F32 or same-type activations%s", "");
-        } else if (Btype != lfamd_vec_dot_type(base_of(Atype)) && Btype != LFAMD_TYPE_F32) {
+        } else if (Btype != lfamd_vec_dot_type(lfamd_base_type(Atype)) && Btype != LFAMD_TYPE_F32) {
             // f32 activations (the GGML_OP_MUL_MAT boundary) are quantised on the device to the vec_dot type
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: activations must be F32 or the weight type's vec_dot format%s", "");
         }
@@ -694,7 +578,7 @@ static int check_mul_mat(int Atype, long m, long k, int Btype, const void *d_B, 
         need = lfamd_gemm_lw_ksplit_bytes(m, n); // partial tiles of a K-split launch: the only workspace left
         uses_ws = need != 0;
     } else if (Btype == LFAMD_TYPE_STAGED_B32) { // a fused producer wrote the 32-block bodies' staged image
-        if ((p.body != mm_body::q40_wide && p.body != mm_body::canon32) || image_cols(Atype, k) != k)
+        if ((p.body != mm_body::q40_wide && p.body != mm_body::canon32) || lfamd_image_of(Atype, k).cols != k)
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat: this call does not run a 32-block batch body (lfamd_mul_mat_takes_staged_b32)%s", "");
         if (!d_B || !aligned16(d_B))
             return fail(LFAMD_ERR_INVALID, "mul_mat: the staged image must be 16-byte aligned%s", "");
@@ -731,8 +615,8 @@ static int launch_mul_mat(const mm_plan &p, int Atype, const void *d_A, long m, 
                           long n, float *d_C, long ldc, void *d_ws, size_t ws_bytes, unsigned flags, hipStream_t s) {
     // A padded image (LFAMD_TYPE_PAD256): the weights and the staged image have kw columns, the activation rows k.  Only the bodies of
     // the 32-block types see kw != k: the decode GEMV and prep80 take k and pad what they stage, gemm_wide reads whole super-blocks.
-    const long kw = image_cols(Atype, k);
-    Atype = base_of(Atype);
+    const long kw = lfamd_image_of(Atype, k).cols;
+    Atype = lfamd_base_type(Atype);
     const int plain = (flags & LFAMD_FLAG_GEMM_PLAIN) ? 1 : 0;
     const int vregs32 = (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0, precise = (flags & LFAMD_FLAG_PRECISE) ? 1 : 0;
     const int vdt = lfamd_vec_dot_type(Atype);
@@ -952,8 +836,9 @@ struct mm_group_plan {
 // The route of sibling matrices of one type (a lfamd_mul_mat_multi call, or one run of a lfamd_mul_mat_multi_types call).
 static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int Btype, size_t b_row_bytes, long n, const long *ldc,
                                 unsigned flags) {
-    const long kw = image_cols(Atype, k); // a padded image: the base type's route at kw weight columns, activation rows of k
-    Atype = base_of(Atype);
+    const lfamd_image im = lfamd_image_of(Atype, k); // a padded image: the base type's route at kw weight columns, activation rows of k
+    const long kw = im.cols;
+    Atype = im.type;
     mm_group_plan g = {mm_route::each, count > 1 && count <= 4 && multi_i8_ok(Atype, count, m, ldc, k, n, flags), 0, {}, {}, false};
     if (count <= 0 || (staged_type(Btype) && n == 0))
         g.route = mm_route::none;
@@ -978,7 +863,7 @@ static mm_group_plan plan_group(int Atype, int count, const long *m, long k, int
         for (int j = 0; j < count && all_sb; j++) // (small siblings — attn_k / attn_v — are faster on the fused GEMV below 8 tokens)
             all_sb = (m[j] > 8192 || (i8_body && n >= 8)) && ldc[j] >= m[j] && sb_takes(Atype, m[j], k, n, flags);
         // one fused launch when the GEMV path applies to every matrix
-        const bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && packed(Atype, kw) && rows_ok && k > 0 &&
+        const bool gemv = count <= 4 && n <= 8 && !(flags & LFAMD_FLAG_FORCE_GENERIC) && im.tuned() && rows_ok && k > 0 &&
                           k % lfamd_blck_size(Atype) == 0 && (Atype == LFAMD_TYPE_Q8_0 || kw % 256 == 0) && group_row_blocks(count, m, ldc) >= 0;
         const bool q80_lf = count > 1 && count <= 4 && Atype == LFAMD_TYPE_Q8_0 && k > 0 && rows_ok &&
                             plan_mul_mat(Atype, m[0], k, n, flags).body == mm_body::q80_lf && group_row_blocks(count, m, ldc) >= 0;
@@ -1055,7 +940,7 @@ static int launch_group(const mm_group_plan &g, int Atype, int count, const void
             HIPCHK(lfamd_launch_gemm_sb(Atype, d_A[j], m[j], k, Btype, d_B, b_row_bytes, n, d_C[j], ldc[j], d_ws, j > 0, s), "gemm_sb (multi)");
         return LFAMD_OK;
     case mm_route::gemv_multi:
-        HIPCHK(lfamd_launch_gemv_multi(base_of(Atype), count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0,
+        HIPCHK(lfamd_launch_gemv_multi(lfamd_base_type(Atype), count, d_A, m, k, Btype, d_B, b_row_bytes, n, d_C, ldc, (flags & LFAMD_FLAG_Q0_VREGS32) ? 1 : 0,
                                        (flags & LFAMD_FLAG_PRECISE) ? 1 : 0, g.relaxed ? 1 : 0, s),
                "gemv_multi");
         return LFAMD_OK;
@@ -1089,7 +974,7 @@ int lfamd_mul_mat_multi(int Atype, int count, const void *const *d_A, const long
                         size_t b_row_bytes, long n, float *const *d_C, const long *ldc, void *d_ws, size_t ws_bytes,
                         unsigned flags, void *stream) {
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
-    if (count > 0 && !type_known(Atype)) // (plan_group strips the layout modifier: an unknown id must not be planned as its base type)
+    if (count > 0 && !lfamd_type_known(Atype)) // (plan_group strips the layout modifier: an unknown id must not be planned as its base type)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi: unsupported weight type%s", "");
     const mm_group_plan g = plan_group(Atype, count, m, k, Btype, b_row_bytes, n, ldc, flags);
     int r = check_group(g, Atype, count, m, k, Btype, d_B, b_row_bytes, n, ldc, d_ws, ws_bytes, flags);
@@ -1173,7 +1058,7 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
     if (!Atype || !d_A || !m || !d_C || !ldc)
         return fail(LFAMD_ERR_INVALID, "mul_mat_multi_types: null argument%s", "");
     for (int j = 0; j < count; j++)
-        if (!type_known(Atype[j]))
+        if (!lfamd_type_known(Atype[j]))
             return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: unsupported weight type%s", "");
     if (Btype == LFAMD_TYPE_STAGED_B32 || Btype == LFAMD_TYPE_STAGED_Q80)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_multi_types: the 32-block staged images are taken by lfamd_mul_mat / lfamd_mul_mat_multi%s", "");
@@ -1236,9 +1121,9 @@ int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int expert
                      size_t b_row_bytes, int tasks, long tokens, const int32_t *d_plan, int thinkers, float *d_result,
                      void *d_ws, size_t ws_bytes, unsigned flags, void *stream) {
     (void)hipGetLastError(); // a stale error of an earlier call (e.g. an invalidated stream capture) must not fail this one
-    if (!type_known(type))
+    if (!lfamd_type_known(type))
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_id: unsupported weight type%s", "");
-    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(base_of(type)) || experts <= 0 || tasks <= 0 || thinkers <= 0 ||
+    if (rows < 0 || cols < 0 || cols % lfamd_blck_size(lfamd_base_type(type)) || experts <= 0 || tasks <= 0 || thinkers <= 0 ||
         tasks > thinkers || thinkers > experts)
         return fail(LFAMD_ERR_INVALID, "mul_mat_id: bad shape%s", "");
     // f32 activations (the GGML_OP_MUL_MAT_ID boundary) are served by the decode path, which quantises in-kernel
@@ -1246,7 +1131,7 @@ int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int expert
                             ((tokens <= 4 && (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K)) ||
                              (tokens > 4 && cols % 256 == 0 && experts < 255 && tokens * thinkers <= 60 * 1024 &&
                               (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K)));
-    if (Btype != lfamd_vec_dot_type(base_of(type)) && !f32_decode)
+    if (Btype != lfamd_vec_dot_type(lfamd_base_type(type)) && !f32_decode)
         return fail(LFAMD_ERR_UNSUPPORTED,
                     "mul_mat_id: activations must be in the weight type's vec_dot format (F32 only for Q4_K / Q5_K / Q6_K experts)%s", "");
     if (tokens == 0 || rows == 0)
@@ -1282,14 +1167,14 @@ int lfamd_mul_mat_id_multi(int type, int count, const void *const *d_W, long row
             return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: null expert stack or result%s", "");
     if (Btype == LFAMD_TYPE_STAGED_B32 || Btype == LFAMD_TYPE_STAGED_Q80)
         return fail(LFAMD_ERR_UNSUPPORTED, "mul_mat_id_multi: no staged image is taken here%s", "");
-    if (tasks <= 0 || tasks > thinkers || !type_known(Btype))
+    if (tasks <= 0 || tasks > thinkers || !lfamd_type_known(Btype))
         return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: bad shape or activation type%s", "");
     if ((uintptr_t)d_plan % 4)
         return fail(LFAMD_ERR_INVALID, "mul_mat_id_multi: the routing table is not 4-byte aligned%s", "");
     if (tokens > 0 && rows > 0)
         if (const int r = check_operands("mul_mat_id_multi", true, Btype, d_thought, b_row_bytes, count, d_result, d_ws, ws_bytes))
             return r;
-    if (count <= 4 && type_known(type) && rows > 0 && cols > 0 && experts > 0 && thinkers > 0 && thinkers <= experts && tokens > 0 &&
+    if (count <= 4 && lfamd_type_known(type) && rows > 0 && cols > 0 && experts > 0 && thinkers > 0 && thinkers <= experts && tokens > 0 &&
         b_row_bytes >= lfamd_row_size(Btype, cols) && lfamd_moe_decode_multi_ok(type, cols, Btype, tasks, tokens, flags)) {
         HIPCHK(lfamd_launch_moe_decode_multi(type, count, d_W, rows, cols, experts, lfamd_packed_size(type, rows, cols), Btype, d_thought,
                                              b_row_bytes, tokens, d_plan, thinkers, d_result, (hipStream_t)stream),

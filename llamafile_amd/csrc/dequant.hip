@@ -1,6 +1,6 @@
 // dequant.hip — the READ side of the resident weight images: rows of a packed matrix as F32 / F16 (GGML_OP_GET_ROWS and the
 // to_fp16 / to_fp32 converters of the reference's GPU module, ggml-cuda.cu.patch:10687-10860, 3929-4040), and the image back to
-// GGUF rows byte for byte (its buffer_get_tensor, :16890-17027).  Nothing here writes an image: pack.hip / generic.hip own that.
+// GGUF rows byte for byte (its buffer_get_tensor, :16890-17027).  Nothing here writes an image: pack.hip does; which image a type has: lfamd_internal.h.
 //
 // ARITHMETIC.  Exactly oracle/oracle.c: ora_dequantize_row, in f32, in this order and with no contraction:
 //   K-quants, IQ4_XS   ((d * (float)sc) * (float)q) - (dmin * (float)mn)        (dmin = +0, mn = 0 where the type has no mins)
@@ -26,27 +26,10 @@
 
 #pragma clang fp contract(off)
 
-enum dq_layout {
-    LY_P4K, LY_P5K, LY_P6K, LY_P40, LY_PK2, LY_PK3, LY_PX4, // PX4: the compact IQ4_XS image
-    LY_PCL41, LY_PCL50, LY_PCL51, LY_P80, LY_P4N, // P4N: the P40 image of IQ4_NL (nibbles = codebook indices)
-    LY_RAW40, LY_RAW41, LY_RAW50, LY_RAW51, LY_RAW4N, LY_F32, LY_F16, LY_BF16, // GGUF rows
-    LY_NONE
-};
-
 // ---------------------------------------------------------------------------------------------
-// layout traits: tile bytes, and the arithmetic forms of lfamd_device.h's position tables (NIBPOS, q5hpos, qhbit) — the tables
+// layout traits (tile bytes: lfamd_ly_tile, lfamd_internal.h): the arithmetic forms of lfamd_device.h's position tables (NIBPOS, q5hpos, qhbit) — the tables
 // themselves are arrays, and an array indexed by a lane-dependent j would go through scratch memory.
 
-__host__ __device__ static constexpr int ly_tile(int ly) {
-    return ly == LY_P4K || ly == LY_P40 || ly == LY_PX4 || ly == LY_P4N ? P4K_TILE
-           : ly == LY_P5K                                ? P5K_TILE
-           : ly == LY_P6K                                ? P6K_TILE
-           : ly == LY_PK2                                ? PK2_TILE
-           : ly == LY_PK3                                ? PK3_TILE
-           : ly == LY_PCL41 || ly == LY_PCL50 || ly == LY_PCL51 ? PCL_TILE
-           : ly == LY_P80                                ? P80_TILE
-                                                         : 0;
-}
 __host__ __device__ static constexpr int ly_raw_block(int ly) { // bytes of one 32-block of the RAW legacy layouts
     return ly == LY_RAW40 || ly == LY_RAW4N ? 18 : ly == LY_RAW41 ? 20 : ly == LY_RAW50 ? 22 : ly == LY_RAW51 ? 24 : 0;
 }
@@ -131,7 +114,7 @@ template <int LY>
 __device__ static inline void decode4(const uint8_t *__restrict__ img, long row, long cols, int nb, int b, int L, float v[4]) {
     const int t = L >> 2, h = (L >> 1) & 1, j0 = (L & 1) * 4, i = (int)(row & 31);
     if constexpr (LY == LY_P4K || LY == LY_P5K) {
-        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * ly_tile(LY);
+        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * lfamd_ly_tile(LY);
         const uint32_t x = lat_dword(tile, i, t, h);
         const uint4 H = *(const uint4 *)(tile + P4K_HDR + i * 16); // {d, dmin, scales[12]} as in the file
         uint32_t sc03, sc47, mn03, mn47;
@@ -160,7 +143,7 @@ __device__ static inline void decode4(const uint8_t *__restrict__ img, long row,
             v[e] = kq_value(d, sc, c - 32, 0.0f, 0);
         }
     } else if constexpr (LY == LY_PK2 || LY == LY_PK3) {
-        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * ly_tile(LY);
+        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * lfamd_ly_tile(LY);
         const uint32_t x = pk_dword(tile, i, t, h) >> (2 * (t & 1));
         if constexpr (LY == LY_PK2) {
             const int sb = tile[PK2_SC + i * 16 + t]; // the block's scale byte: scale | min << 4
@@ -189,7 +172,7 @@ __device__ static inline void decode4(const uint8_t *__restrict__ img, long row,
         for (int e = 0; e < 4; e++)
             v[e] = kq_value(d, sc, (int)kvalues_iq4nl_dq[(x >> (4 * nibpos(j0 + e))) & 15], 0.0f, 0);
     } else if constexpr (LY == LY_P40 || LY == LY_P4N || LY == LY_PCL41 || LY == LY_PCL50 || LY == LY_PCL51) {
-        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * ly_tile(LY);
+        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * lfamd_ly_tile(LY);
         const uint32_t x = lat_dword(tile, i, t, h);
         const int bl = L >> 3; // 32-block of the 256-weight group
         const float d = h2f((uint16_t)ld16(tile + P4K_HDR + i * 16 + bl * 2)); // (PCL_D == P4K_HDR)
@@ -336,7 +319,7 @@ __device__ static inline uint8_t raw_byte(const uint8_t *__restrict__ img, long 
         constexpr int LY = TYPE == LFAMD_TYPE_Q4_K ? LY_P4K : LY_P5K;
         constexpr int BS = TYPE == LFAMD_TYPE_Q4_K ? 144 : 176, QS = BS - 128;
         const int b = (int)(o / BS), p = (int)(o % BS);
-        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * ly_tile(LY);
+        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * lfamd_ly_tile(LY);
         if (p < 16)
             return tile[P4K_HDR + i * 16 + p];
         if (p < QS) { // Q5_K qh[l]: bit s = fifth bit of weight 32 s + l
@@ -431,7 +414,7 @@ __device__ static inline uint8_t raw_byte(const uint8_t *__restrict__ img, long 
         constexpr bool HAS_M = TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_1, HAS_H = TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
         constexpr int QH_OFF = HAS_M ? 4 : 2, QS_OFF = QH_OFF + (HAS_H ? 4 : 0), BS = QS_OFF + 16;
         const int blk = (int)(o / BS), p = (int)(o % BS), b = blk >> 3, bl = blk & 7;
-        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * ly_tile(LY);
+        const uint8_t *tile = img + ((size_t)(row >> 5) * nb + b) * lfamd_ly_tile(LY);
         if (p < 2)
             return tile[P4K_HDR + i * 16 + bl * 2 + p];
         if (HAS_M && p < 4)
@@ -473,56 +456,17 @@ __global__ __launch_bounds__(256) void unpack_raw_kernel(const uint8_t *__restri
 
 // ---------------------------------------------------------------------------------------------
 
-// (tiled: the caller keeps the legacy 32-block rows as the tile image whatever their length, LFAMD_TYPE_PAD256)
-static int layout_of(int type, long cols, int tiled) {
-    const bool g256 = cols % 256 == 0 || tiled;
-    switch (type) {
-    case LFAMD_TYPE_Q4_K:
-        return LY_P4K;
-    case LFAMD_TYPE_Q5_K:
-        return LY_P5K;
-    case LFAMD_TYPE_Q6_K:
-        return LY_P6K;
-    case LFAMD_TYPE_Q2_K:
-        return LY_PK2;
-    case LFAMD_TYPE_Q3_K:
-        return LY_PK3;
-    case LFAMD_TYPE_IQ4_XS:
-        return LY_PX4;
-    case LFAMD_TYPE_Q8_0:
-        return LY_P80;
-    case LFAMD_TYPE_Q4_0:
-        return g256 ? LY_P40 : LY_RAW40;
-    case LFAMD_TYPE_IQ4_NL:
-        return g256 ? LY_P4N : LY_RAW4N;
-    case LFAMD_TYPE_Q4_1:
-        return g256 ? LY_PCL41 : LY_RAW41;
-    case LFAMD_TYPE_Q5_0:
-        return g256 ? LY_PCL50 : LY_RAW50;
-    case LFAMD_TYPE_Q5_1:
-        return g256 ? LY_PCL51 : LY_RAW51;
-    case LFAMD_TYPE_F32:
-        return LY_F32;
-    case LFAMD_TYPE_F16:
-        return LY_F16;
-    case LFAMD_TYPE_BF16:
-        return LY_BF16;
-    default:
-        return LY_NONE;
-    }
-}
-
 // rows per work-group: a whole tile's 32 rows for a range of rows (every image byte from HBM once), one row per wave for an index
 // list or a range shorter than a tile (1 index x 16 super-blocks = 16 work-groups, 512 indices = 2048)
 static int rows_per_group(const int32_t *ids, long n_ids) {
     return !ids && n_ids >= 32 ? 32 : 4;
 }
 
-// cols: the columns read back.  tiled: a 32-block type's image is the tile image of ceil(cols / 256) super-blocks per row whose last one
-// is padded with zero blocks; the kernels' column guards stop at cols, so nothing of the padding is written out.
-extern "C" hipError_t lfamd_launch_get_rows(int type, int tiled, const void *img, long rows, long cols, const int32_t *ids, long row0, long n_ids,
+// im: lfamd_image_of(the call's type id, cols).  cols: the columns read back.  A 32-block type's tile image may have more (im.cols: its
+// last super-block is padded with zero blocks); the kernels' column guards stop at cols, so nothing of the padding is written out.
+extern "C" hipError_t lfamd_launch_get_rows(const lfamd_image &im, const void *img, long rows, long cols, const int32_t *ids, long row0, long n_ids,
                                             int out_type, void *out, size_t out_row_bytes, hipStream_t s) {
-    const int ly = layout_of(type, cols, tiled);
+    const int ly = im.ly;
     if (ly == LY_NONE || (out_type != LFAMD_TYPE_F32 && out_type != LFAMD_TYPE_F16))
         return hipErrorInvalidValue;
     if (n_ids <= 0 || cols <= 0)
@@ -568,9 +512,9 @@ extern "C" hipError_t lfamd_launch_get_rows(int type, int tiled, const void *img
     return hipGetLastError();
 }
 
-extern "C" hipError_t lfamd_launch_unpack(int type, int tiled, const void *img, long rows, long cols, void *raw, size_t raw_row_bytes,
+extern "C" hipError_t lfamd_launch_unpack(const lfamd_image &im, const void *img, long rows, long cols, void *raw, size_t raw_row_bytes,
                                           hipStream_t s) {
-    const int ly = layout_of(type, cols, tiled);
+    const int ly = im.ly, type = im.type;
     if (ly == LY_NONE)
         return hipErrorInvalidValue;
     const size_t row_bytes = lfamd_row_size(type, cols);

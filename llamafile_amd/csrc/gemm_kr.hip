@@ -508,7 +508,7 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
             const long tok = n0 + nt * 32 + i;
             if (MOE ? nt * 32 + i >= moe_left : tok >= n)
                 continue;
-            const float ts = d8T[tok]; // 2^e of the token's normalised staging (pack.hip, prep_scaled_kernel): exact
+            const float ts = d8T[tok]; // 2^e of the token's normalised staging (prep.hip, prep_scaled_kernel): exact
             const long crow = MOE ? (long)mats.moe_slot_row[tok] : tok;
 #pragma unroll
             for (int g = 0; g < 4; g++) {

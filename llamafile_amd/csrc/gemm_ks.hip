@@ -528,7 +528,7 @@ __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int 
             const long tok = n0 + kh * 32 + i;
             if (tok < n) {
                 const bool vec = (ldc & 3) == 0 && (m & 3) == 0 && (((uintptr_t)C) & 15) == 0;
-                const float ts = d8T[tok]; // 2^e of the token's normalised staging (pack.hip, prep_scaled_kernel): exact
+                const float ts = d8T[tok]; // 2^e of the token's normalised staging (prep.hip, prep_scaled_kernel): exact
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
                     const long row0 = rt * 32 + 8 * g + 4 * h;

@@ -376,7 +376,7 @@ __device__ __forceinline__ void gemm_lw_body(const gemm_mats &mats, int nb, cons
     using H1 = std::integral_constant<int, 1>;
     asm volatile("s_barrier" ::: "memory"); // stage 0 landed (loaders waited before their arrival)
     if constexpr (FAST) {
-        // ---- scaled operands (pack.hip prep mode 2): Xh = f16(d8 * code), the weight fragment = f16(d * sc * q), the
+        // ---- scaled operands (prep.hip prep mode 2): Xh = f16(d8 * code), the weight fragment = f16(d * sc * q), the
         // mins one more MFMA per token tile with f16(d8 * S_j) x f16(-dmin * m_j): everything accumulates straight into
         // acc, nothing is scaled per super-block.  The K-step pipeline runs ACROSS the half-step barriers: the first
         // operands of the next stage are fetched during K-steps 6 and 7 of this one (see the loader's protocol).
@@ -609,7 +609,7 @@ __device__ __forceinline__ void gemm_lw_body(const gemm_mats &mats, int nb, cons
                 } else if (tok >= n) {
                     continue;
                 }
-                const float ts = part ? 1.0f : d8T[tok]; // 2^e of the token's normalised staging (pack.hip, prep_scaled_kernel): exact
+                const float ts = part ? 1.0f : d8T[tok]; // 2^e of the token's normalised staging (prep.hip, prep_scaled_kernel): exact
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
                     const long row0 = rt * 32 + 8 * g + 4 * h;

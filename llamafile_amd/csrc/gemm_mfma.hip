@@ -10,7 +10,7 @@
 // exact in f16), the activation operand is the int8 code (exact in f16), products and their sums over
 // one 256-wide super-block stay below 2^24 in the f32 accumulator.  The two f32 scales are applied
 // once per super-block on the VALU.  The mins term is one extra MFMA per super-block with the pair
-// sums of bsums split into two exact f16 parts (pack.hip, prep_q8k_kernel).
+// sums of bsums split into two exact f16 parts (prep.hip, prep_q8k_kernel).
 //
 // Orientation: MFMA A operand = activations (rows = tokens), B operand = weights (cols = weight
 // rows), so a lane owns one weight row (its d/dmin are per-lane scalars) and the C store is 32

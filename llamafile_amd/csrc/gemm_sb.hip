@@ -51,7 +51,7 @@ __global__ __launch_bounds__(64) void sb_prep_kernel(const uint8_t *__restrict__
     float d;
     if constexpr (F32IN) {
         // quantize_row_q8_K: the FIRST element of largest magnitude gives the sign of iscale = -128 / max; nearest-even codes
-        // clamped at 127; d = 1 / iscale  (pack.hip: prep_f32_kernel, the same arithmetic)
+        // clamped at 127; d = 1 / iscale  (prep.hip: prep_f32_kernel, the same arithmetic)
         const float4 f = *(const float4 *)((const float *)(B + (size_t)tok * b_row_bytes) + (size_t)b * 256 + 4 * t);
         const float v[4] = {f.x, f.y, f.z, f.w};
         // block maximum by DPP (no LDS round trips), then the FIRST lane / element that reaches it (gemv_impl.h: stage_f32_q8k_wave)

@@ -44,7 +44,7 @@ static int lw_ksplit(int tiles2, int nb) {
 }
 
 // Q4_K / Q5_K without K split run the loader-wave body (gemm_lw.hip) unless the caller asks for the plain one.
-// `mode` (an argument of every launcher here) bit 0: plain body; bit 1: the activations were staged SCALED (pack.hip, prep mode 2) for the scaled-operand
+// `mode` (an argument of every launcher here) bit 0: plain body; bit 1: the activations were staged SCALED (prep.hip, prep mode 2) for the scaled-operand
 // loader-wave body — only set when lfamd_gemm_wide_scaled_ok() said that body will run.
 // 128 x 128 tiles from which the scaled-operand body uses them instead of 128 x 64: a 128 x 64 work-group takes ~0.73 of a
 // 128 x 128 one (2720 vs 3680 cycles per super-block), so two rounds of the small tile (129 .. 256 big tiles = 258 .. 512

@@ -137,17 +137,17 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
                                                         long n_pad, int n_rb, int n_ct, int ks_n, int nbs) {
     __shared__ __attribute__((aligned(16))) uint8_t xs[2][WD_XSTAGE];     // activation codes, XOR-swizzled rows
     // 32-blocks: f16 scale per block, Q8_0 / Q8_1 activations (8 d8 per 256).  Q4_0 and IQ4_NL (nibbles = codebook indices) are
-    // resident in P40; Q4_1 / Q5_0 / Q5_1 come as a per-call PCL image (generic.hip, wprep32): L5 = fifth bits, L1 = w = d*q + m
+    // resident in P40; Q4_1 / Q5_0 / Q5_1 are resident as the PCL image (pack.hip): L5 = fifth bits, L1 = w = d*q + m
     // with the s = d8*sum(q8) term
     constexpr bool P40 = TYPE == LFAMD_TYPE_Q4_0 || TYPE == LFAMD_TYPE_IQ4_NL;
     constexpr bool LEGACY = P40 || TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr bool L5 = TYPE == LFAMD_TYPE_Q5_0 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr bool L1 = TYPE == LFAMD_TYPE_Q4_1 || TYPE == LFAMD_TYPE_Q5_1;
     constexpr float LOFF = TYPE == LFAMD_TYPE_Q4_0 ? 8.0f : TYPE == LFAMD_TYPE_Q5_0 ? 16.0f : 0.0f;
-    // PCK image built per call (generic.hip, wprep16): 16-wide sub-blocks, int8 scale each; Q2_K also 16 mins
+    // PCK image built per call (pack.hip, pk_expand): 16-wide sub-blocks, int8 scale each; Q2_K also 16 mins
     constexpr bool CANON16 = TYPE == LFAMD_TYPE_Q2_K || TYPE == LFAMD_TYPE_Q3_K;
     constexpr bool MINS16 = TYPE == LFAMD_TYPE_Q2_K;
-    constexpr bool BYTES8 = TYPE == LFAMD_TYPE_IQ4_XS; // PC8 byte image built per call (generic.hip, wprep8)
+    constexpr bool BYTES8 = TYPE == LFAMD_TYPE_IQ4_XS; // PC8 byte image built per call (pack.hip, pk4x_expand)
     constexpr bool BLK8 = LEGACY; // eight 32-blocks per super-block: d8 per block
     // float tinyBLAS types (tinyblas_cpu.h:419-613): no dequantisation, no scales — the lane's 8 consecutive halves of a
     // K-step are 16 contiguous bytes of the RAW row; f32 accumulate on the matrix cores like the reference's fmaf chains

@@ -81,9 +81,7 @@ static int sb_of(long k) {
 }
 // The kernels' `nb` argument (gemv_impl.h, kq_nb_of): the row's 32-blocks for the types on 32-block activations, else its super-blocks
 static int nb_arg(int Atype, long k) {
-    const bool b32 = Atype == LFAMD_TYPE_Q4_0 || Atype == LFAMD_TYPE_Q4_1 || Atype == LFAMD_TYPE_Q5_0 || Atype == LFAMD_TYPE_Q5_1 ||
-                     Atype == LFAMD_TYPE_IQ4_NL;
-    return b32 ? (int)(k / 32) : sb_of(k);
+    return lfamd_image_of(Atype, k).block32() ? (int)(k / 32) : sb_of(k);
 }
 
 // LDS budget: keep one launch's activation image under 160 KiB; otherwise split the columns.

@@ -673,7 +673,7 @@ struct pk_traits {
     }
 };
 
-// IQ4_XS on the RESIDENT compact image (generic.hip: pk4x_pack_kernel): codebook indices on the P4K nibble lattice, so a dword's
+// IQ4_XS on the RESIDENT compact image (pack.hip: pack_tiles_kernel<LY_PX4>): codebook indices on the P4K nibble lattice, so a dword's
 // nibbles already sit in the order of the staged activation codes; the 16-entry int8 codebook (kvalues_iq4nl,
 // iqk_mul_mat.inc:601-628 looks it up with a byte shuffle too) is looked up by kvalues_lut4 (above, shared with IQ4_NL).
 struct iq4c_traits {

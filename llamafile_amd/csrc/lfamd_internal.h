@@ -1,10 +1,82 @@
-// lfamd_internal.h — what the module's translation units share on the host side: every extern "C" function that one csrc unit
-// defines and another calls (declared once here, so that the defining unit's compiler checks each prototype against its definition;
-// the definitions name the parameters), and the byte layouts of the staged activation images.  Public functions: include/lfamd_hip.h.
+// lfamd_internal.h — what the module's translation units share on the host side: the table of the resident weight images (which
+// layout a weight type id has at a row length), every extern "C" function that one csrc unit defines and another calls (declared once
+// here, so that the defining unit's compiler checks each prototype against its definition; the definitions name the parameters), and
+// the byte layouts of the staged activation images.  Public functions: include/lfamd_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "../../include/lfamd_hip.h"
+#include "lfamd_device.h"
+
+// ---- the resident weight images (DESIGN.md sections 3 and 24).  pack.hip writes them, dequant.hip reads them back, the mat-mul
+// bodies read them; which one a (type id, row length) has is answered here and nowhere else.
+enum lfamd_layout {
+    LY_P4K, LY_P5K, LY_P6K, LY_P40, LY_PK2, LY_PK3, LY_PX4, // PX4: the compact IQ4_XS image
+    LY_PCL41, LY_PCL50, LY_PCL51, LY_P80, LY_P4N, // P4N: the P40 image of IQ4_NL (nibbles = codebook indices)
+    LY_RAW40, LY_RAW41, LY_RAW50, LY_RAW51, LY_RAW4N, LY_F32, LY_F16, LY_BF16, // GGUF rows
+    LY_NONE
+};
+__host__ __device__ static constexpr int lfamd_ly_tile(int ly) { // bytes of a tile; 0: GGUF rows
+    return ly == LY_P4K || ly == LY_P40 || ly == LY_PX4 || ly == LY_P4N ? P4K_TILE
+           : ly == LY_P5K                                ? P5K_TILE
+           : ly == LY_P6K                                ? P6K_TILE
+           : ly == LY_PK2                                ? PK2_TILE
+           : ly == LY_PK3                                ? PK3_TILE
+           : ly == LY_PCL41 || ly == LY_PCL50 || ly == LY_PCL51 ? PCL_TILE
+           : ly == LY_P80                                ? P80_TILE
+                                                         : 0;
+}
+struct lfamd_image {
+    int ly;   // LY_NONE: an unknown id, or LFAMD_TYPE_PAD256 on a type that has no tile image to pad
+    int type; // the id without the modifier
+    long cols; // columns of the image: 256 * ceil(cols / 256) under LFAMD_TYPE_PAD256, else the row's
+    int tile; // bytes of a tile (32 rows x 256 weights; P80: 8 rows x 4 blocks); 0: GGUF rows at lfamd_row_size(type, cols)
+    bool tuned() const { // a layout only the tuned kernels read: the decode GEMVs take it, the generic kernels do not
+        return tile != 0;
+    }
+    bool p40() const {
+        return ly == LY_P40 || ly == LY_P4N;
+    }
+    bool pcl() const {
+        return ly == LY_PCL41 || ly == LY_PCL50 || ly == LY_PCL51;
+    }
+    bool block32() const { // a legacy 32-block type (Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL), tiles or GGUF rows: activations in 32-blocks
+        return p40() || pcl() || (ly >= LY_RAW40 && ly <= LY_RAW4N);
+    }
+    size_t tiles(long rows) const {
+        return ly == LY_P80 ? (size_t)((rows + 7) / 8) * (size_t)((cols / 32 + 3) / 4) : (size_t)((rows + 31) / 32) * (size_t)(cols / 256);
+    }
+};
+static inline int lfamd_base_type(int id) { // the id without the layout modifier
+    return id & ~LFAMD_TYPE_PAD256;
+}
+// id: a public weight type id, with or without LFAMD_TYPE_PAD256.  The legacy 32-block types keep rows of whole 256-weight groups,
+// and any row under the modifier, as tiles (the last super-block continued with zero blocks); their other rows stay GGUF rows.
+static inline lfamd_image lfamd_image_of(int id, long cols) {
+    static const struct {
+        int type, ly, raw_ly; // raw_ly: the layout of rows that are not whole groups, LY_NONE = the type has whole groups only
+    } tab[] = {
+        {LFAMD_TYPE_Q4_K, LY_P4K, LY_NONE},    {LFAMD_TYPE_Q5_K, LY_P5K, LY_NONE},     {LFAMD_TYPE_Q6_K, LY_P6K, LY_NONE},
+        {LFAMD_TYPE_Q2_K, LY_PK2, LY_NONE},    {LFAMD_TYPE_Q3_K, LY_PK3, LY_NONE},     {LFAMD_TYPE_IQ4_XS, LY_PX4, LY_NONE},
+        {LFAMD_TYPE_Q8_0, LY_P80, LY_NONE},    {LFAMD_TYPE_Q4_0, LY_P40, LY_RAW40},    {LFAMD_TYPE_IQ4_NL, LY_P4N, LY_RAW4N},
+        {LFAMD_TYPE_Q4_1, LY_PCL41, LY_RAW41}, {LFAMD_TYPE_Q5_0, LY_PCL50, LY_RAW50},  {LFAMD_TYPE_Q5_1, LY_PCL51, LY_RAW51},
+        {LFAMD_TYPE_F32, LY_F32, LY_NONE},     {LFAMD_TYPE_F16, LY_F16, LY_NONE},      {LFAMD_TYPE_BF16, LY_BF16, LY_NONE},
+    };
+    const int type = lfamd_base_type(id);
+    const bool pad = id != type;
+    for (const auto &e : tab)
+        if (e.type == type) {
+            const bool whole = e.raw_ly == LY_NONE; // (no tile image to pad: the modifier makes an unknown id)
+            const int ly = whole ? (pad ? (int)LY_NONE : e.ly) : (pad || cols % 256 == 0) ? e.ly : e.raw_ly;
+            return {ly, type, whole || ly == e.raw_ly ? cols : (cols + 255) / 256 * 256, lfamd_ly_tile(ly)};
+        }
+    return {LY_NONE, type, cols, 0};
+}
+static inline bool lfamd_type_known(int id) { // (at every row length: cols only picks between a type's layouts)
+    return lfamd_image_of(id, 0).ly != LY_NONE;
+}
 
 // A planned decode GEMV launch.  kind = the entry point that asks, variant = the kernel form it gets.
 enum { LFAMD_GEMV_MULTI, LFAMD_GEMV_IDS, LFAMD_GEMV_IDS_PAIR, LFAMD_GEMV_DUAL, LFAMD_GEMV_MULTI_RELAXED }; // (_RELAXED: Q8_0 under LFAMD_FLAG_Q80_RELAXED)
@@ -28,29 +100,21 @@ struct lfamd_gemv_plan {
 extern "C" {
 void lfamd_set_error(const char *); // (api.hip: sets lfamd_last_error)
 size_t lfamd_mul_mat_workspace_upto(int, long, long, long);
-// weight images (pack.hip, generic.hip, blaslt.hip)
-hipError_t lfamd_launch_pack_q4k(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q40(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q5k(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q6k(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_q80(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pack_raw(const void *, size_t, long, size_t, void *, hipStream_t);
+// weight images (pack.hip: every packer, expander and image size; dequant.hip: the read-back; blaslt.hip)
+// (lfamd_launch_pack: the image of `im` from GGUF rows of `cols` weights; wprep16 / wprep8: the canonical per-call images, from GGUF
+// rows, pk_expand / pk4x_expand: from the resident compact image)
+hipError_t lfamd_launch_pack(const lfamd_image &, const void *, size_t, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_scaled_ok(int, long, long, const void *, int *, hipStream_t);
-size_t lfamd_wprep32_bytes(long, long);
-hipError_t lfamd_launch_wprep32(int, const void *, size_t, long, long, void *, hipStream_t);
 size_t lfamd_wprep16_bytes(long, long);
 hipError_t lfamd_launch_wprep16(int, const void *, size_t, long, long, void *, hipStream_t);
 size_t lfamd_wprep8_bytes(long, long);
 hipError_t lfamd_launch_wprep8(int, const void *, size_t, long, long, void *, hipStream_t);
-size_t lfamd_pk_bytes(int, long, long);
-hipError_t lfamd_launch_pk_pack(int, const void *, size_t, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_pk_expand(int, const void *, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_pk4x_pack(const void *, size_t, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_pk4x_expand(const void *, long, long, void *, hipStream_t);
 hipError_t lfamd_launch_q80_image(const void *, size_t, long, long, void *, hipStream_t);
-hipError_t lfamd_launch_get_rows(int, int, const void *, long, long, const int32_t *, long, long, int, void *, size_t, hipStream_t);
-hipError_t lfamd_launch_unpack(int, int, const void *, long, long, void *, size_t, hipStream_t);
-// activation staging (pack.hip, quantize.hip, blaslt.hip)
+hipError_t lfamd_launch_get_rows(const lfamd_image &, const void *, long, long, const int32_t *, long, long, int, void *, size_t, hipStream_t);
+hipError_t lfamd_launch_unpack(const lfamd_image &, const void *, long, long, void *, size_t, hipStream_t);
+// activation staging (prep.hip, quantize.hip, blaslt.hip)
 hipError_t lfamd_launch_quantize(int, const float *, long, long, size_t, void *, size_t, hipStream_t);
 hipError_t lfamd_launch_prep_q8k(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);
 hipError_t lfamd_launch_prep_f32(const void *, size_t, long, long, long, void *, void *, void *, int, const int32_t *, hipStream_t);

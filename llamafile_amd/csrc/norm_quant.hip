@@ -136,7 +136,7 @@ __device__ static inline void put_staged_zero(const staged_image &im, int b, lon
         im.d8T[o] = 0.0f;
 }
 
-// The staged image of the scaled-operand f16 batch bodies (gemm_lw / gemm_ks / gemm_kr; what prep_scaled_kernel of pack.hip writes):
+// The staged image of the scaled-operand f16 batch bodies (gemm_lw / gemm_ks / gemm_kr; what prep_scaled_kernel of prep.hip writes):
 //   Xh [nb][n_pad][256] f16 = q8 * d8 * 2^-e(token), d8T [n_pad] f32 = 2^e(token) (the store multiplies the column by it),
 //   Xm [nb][n_pad][16] f16 = the eight 32-code sums times d8 * 2^-e (the mins operand), then eight zeros;
 // e(token) from the largest |y| of the whole row, so that every operand sits in f16's normal range: that maximum must be known
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(256) void swiglu_scaled_kernel(const float *__restr
 }
 
 // ---- the 32-block formats: Q8_0 / Q8_1 rows, what the decode GEMVs of the legacy types and of Q8_0 read, and
-// the staged image of the 32-block batch bodies (lfamd_b32_image_of; what prep80_kernel<true, true> of pack.hip writes).
+// the staged image of the 32-block batch bodies (lfamd_b32_image_of; what prep80_kernel<true, true> of prep.hip writes).
 // quantize_row_q8_0 / quantize_row_q8_1 as csrc/quantize.hip has them: d = amax / 127, id = d ? 1 / d : 0, codes roundf(v * id)
 // (half away from zero — Q8_K's are nearest-even), d stored as f16, s = f16(sum * d) with d not yet rounded.
 // A 256-chunk is four values per lane, so 32-block j of the chunk is lanes 8 j .. 8 j + 7: maximum and code sum are reduced over

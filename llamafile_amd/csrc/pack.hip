@@ -1,171 +1,58 @@
-// pack.hip — device-side re-layout of GGUF weight tensors into the packed tile formats
-// (lfamd_device.h) and preparation of quantised activations for the MFMA GEMM.
+// pack.hip — the WRITE side of the weight images (lfamd_device.h; DESIGN.md section 24 has the dword ranges of every tile): every
+// packer, expander and image size.  dequant.hip is the read side, lfamd_internal.h says which image a type has.
 //
 // Counterpart of the reference's weight upload, ggml_backend_cuda_buffer_set_tensor
 // (ggml-cuda.cu.patch:16971-16977): the backend owns the device copy, so it may choose its layout.
+//
+// Every image of 32 rows x 256 weights but P6K (pack_q6k_kernel, kept for its speed) is written by ONE kernel, pack_tiles_kernel<IMG>,
+// the mirror of dequant.hip's tile_code<LY>: one thread per output dword; a tile is a list of sections (sections_of), and each kind of section is written once for all the
+// images that have it.  What differs per type is where weight k of a super-block sits in the GGUF block (gguf_code) and what the
+// header holds (hdr_word, row_word).
 #include "lfamd_device.h"
 #include "lfamd_internal.h"
 
-// ---------------------------------------------------------------------------------------------
-// Q4_K -> P4K.  One thread per output dword of the qs part, one per 16-byte header.
+__device__ static const int8_t kvalues_iq4nl_dev[16] = {-127, -104, -83, -65, -49, -35, -22, -10,
+                                                        1,    13,   25,  38,  53,  69,  89,  113};
 
-__global__ void pack_q4k_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb,
-                                uint8_t *__restrict__ out, long n_tiles) {
-    long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    // per tile: 1024 qs dwords + 32 header slots (4 dwords each) = 1152 dwords
-    long tile = tid / 1152;
-    int w = (int)(tid % 1152);
-    if (tile >= n_tiles)
-        return;
-    long rt = tile / nb;
-    int b = (int)(tile % nb);
-    uint32_t *dst = (uint32_t *)(out + tile * P4K_TILE);
-    if (w < 1024) {
-        int g = w >> 8, lane = (w >> 2) & 63, dd = w & 3;
-        int i = lane & 31, h = lane >> 5;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const lfamd_block_q4_K *blk = (const lfamd_block_q4_K *)(raw + row * raw_row_bytes) + b;
-            int t = 4 * g + dd;
-            for (int j = 0; j < 8; j++) {
-                int k = 16 * t + 8 * h + j;
-                int c = k >> 6, wi = k & 63;
-                uint8_t byte = blk->qs[32 * c + (wi & 31)];
-                uint32_t nib = wi < 32 ? (byte & 15u) : (uint32_t)(byte >> 4);
-                v |= nib << (4 * NIBPOS(j));
-            }
-        }
-        dst[w] = v;
+// ---------------------------------------------------------------------------------------------
+// Sources: the integer code of weight k (0..255) of super-block b of a GGUF row, as the file stores it.
+
+// Q2_K / Q3_K in units of 16 consecutive weights (unit s of a super-block): w = d*sc*q - dmin*mn.
+// Formulas: ggml-cuda.cu.patch:3217-3471, 3684-3699.
+template <int TYPE>
+__device__ static inline int code16(const uint8_t *blk, int s, int l) { // q of weight l of unit s
+    const int n = s >> 3, j = (s >> 1) & 3, l0 = (s & 1) * 16;
+    if constexpr (TYPE == LFAMD_TYPE_Q2_K) {
+        const uint8_t *qs = blk + 16;
+        return (qs[32 * n + l0 + l] >> (2 * j)) & 3;
     } else {
-        int s = w - 1024; // 0..127: header dword
-        int i = s >> 2, q = s & 3;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const uint8_t *blk = raw + row * raw_row_bytes + (size_t)b * sizeof(lfamd_block_q4_K);
-            // raw blocks are only 2-byte aligned in general (row strides are multiples of 144, so
-            // 4-byte here, but stay safe)
-            const uint16_t *p = (const uint16_t *)(blk + 4 * q);
-            v = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-        }
-        dst[1024 + s] = v;
+        const uint8_t *hmask = blk, *qs = blk + 32;
+        const uint8_t m = (uint8_t)(1 << (4 * n + j));
+        const int v = (qs[32 * n + l0 + l] >> (2 * j)) & 3;
+        return v - ((hmask[l0 + l] & m) ? 0 : 4);
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// Q4_0 -> P40: the P4K nibble image (K-step dword = the 8 codes of k = 16t + 8h + j) and, as
-// header, the eight f16 block scales of the row's 256 weights.  block_q4_0 = {d, qs[16]}: weight l of a block is the
-// low nibble of qs[l] (l < 16) or the high nibble of qs[l - 16]; value d*(q - 8).
-// kb: 32-blocks of a raw row.  kb < 8 nb (LFAMD_TYPE_PAD256): the blocks from kb on are not read and written as zero bytes
-// (d = +0, nibbles 0), for every row of the tile.
-
-__global__ void pack_q40_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb, int kb,
-                                uint8_t *__restrict__ out, long n_tiles) {
-    long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long tile = tid / 1152;
-    int w = (int)(tid % 1152);
-    if (tile >= n_tiles)
-        return;
-    long rt = tile / nb;
-    int b = (int)(tile % nb);
-    uint32_t *dst = (uint32_t *)(out + tile * P4K_TILE);
-    if (w < 1024) {
-        int g = w >> 8, lane = (w >> 2) & 63, dd = w & 3;
-        int i = lane & 31, h = lane >> 5;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const lfamd_block_q4_0 *blk = (const lfamd_block_q4_0 *)(raw + row * raw_row_bytes) + (size_t)b * 8;
-            int t = 4 * g + dd;
-            for (int j = 0; j < 8; j++) {
-                int k = 16 * t + 8 * h + j;
-                int bl = k >> 5, l = k & 31;
-                uint8_t byte = b * 8 + bl < kb ? blk[bl].qs[l & 15] : (uint8_t)0;
-                uint32_t nib = l < 16 ? (byte & 15u) : (uint32_t)(byte >> 4);
-                v |= nib << (4 * NIBPOS(j));
-            }
-        }
-        dst[w] = v;
+template <int TYPE>
+__device__ static inline void scale16(const uint8_t *blk, int s, int &sc, int &mn, float &d, float &dmin) {
+    if constexpr (TYPE == LFAMD_TYPE_Q2_K) {
+        const uint8_t *scales = blk;
+        d = h2f(*(const uint16_t *)(blk + 80));
+        dmin = h2f(*(const uint16_t *)(blk + 82));
+        sc = scales[s] & 0xF;
+        mn = scales[s] >> 4;
     } else {
-        int s = w - 1024; // row i, scale pair q: blocks 2q, 2q+1
-        int i = s >> 2, q = s & 3;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const lfamd_block_q4_0 *blk = (const lfamd_block_q4_0 *)(raw + row * raw_row_bytes) + (size_t)b * 8;
-            const uint32_t lo = b * 8 + 2 * q < kb ? blk[2 * q].d : 0u, hi = b * 8 + 2 * q + 1 < kb ? blk[2 * q + 1].d : 0u;
-            v = lo | (hi << 16);
-        }
-        dst[1024 + s] = v;
+        const uint8_t *scales = blk + 96;
+        d = h2f(*(const uint16_t *)(blk + 108));
+        dmin = 0.0f;
+        int is = s;
+        int us = is < 4    ? (scales[is] & 0xF) | (((scales[is + 8] >> 0) & 3) << 4)
+                 : is < 8  ? (scales[is] & 0xF) | (((scales[is + 4] >> 2) & 3) << 4)
+                 : is < 12 ? (scales[is - 8] >> 4) | (((scales[is] >> 4) & 3) << 4)
+                           : (scales[is - 8] >> 4) | (((scales[is - 4] >> 6) & 3) << 4);
+        sc = us - 32;
+        mn = 0;
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// Q5_K -> P5K: the P4K image of the low nibbles and the header, then one dword of fifth bits per (lane, group).
-// block_q5_K = {d, dmin, scales[12], qh[32], qs[128]}: weight l of sub-block j has its fifth bit at bit j of qh[l].
-
-__global__ void pack_q5k_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb,
-                                uint8_t *__restrict__ out, long n_tiles) {
-    long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long tile = tid / 1408; // 1024 qs dwords + 128 header dwords + 256 fifth-bit dwords
-    int w = (int)(tid % 1408);
-    if (tile >= n_tiles)
-        return;
-    long rt = tile / nb;
-    int b = (int)(tile % nb);
-    uint32_t *dst = (uint32_t *)(out + tile * P5K_TILE);
-    if (w < 1024) {
-        int g = w >> 8, lane = (w >> 2) & 63, dd = w & 3;
-        int i = lane & 31, h = lane >> 5;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const lfamd_block_q5_K *blk = (const lfamd_block_q5_K *)(raw + row * raw_row_bytes) + b;
-            int t = 4 * g + dd;
-            for (int j = 0; j < 8; j++) {
-                int k = 16 * t + 8 * h + j;
-                int c = k >> 6, wi = k & 63;
-                uint8_t byte = blk->qs[32 * c + (wi & 31)];
-                uint32_t nib = wi < 32 ? (byte & 15u) : (uint32_t)(byte >> 4);
-                v |= nib << (4 * NIBPOS(j));
-            }
-        }
-        dst[w] = v;
-    } else if (w < 1152) {
-        int s = w - 1024; // header dword: the block's first 16 bytes {d, dmin, scales[12]}
-        int i = s >> 2, q = s & 3;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const uint8_t *blk = raw + row * raw_row_bytes + (size_t)b * sizeof(lfamd_block_q5_K);
-            const uint16_t *p = (const uint16_t *)(blk + 4 * q);
-            v = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-        }
-        dst[1024 + s] = v;
-    } else {
-        int s = w - 1152; // lane * 4 + g
-        int lane = s >> 2, g = s & 3;
-        int i = lane & 31, h = lane >> 5;
-        long row = rt * 32 + i;
-        uint32_t v = 0;
-        if (row < rows) {
-            const lfamd_block_q5_K *blk = (const lfamd_block_q5_K *)(raw + row * raw_row_bytes) + b;
-            for (int dd = 0; dd < 4; dd++) {
-                int t = 4 * g + dd, sub = t >> 1;
-                for (int j = 0; j < 8; j++) {
-                    int l = 16 * (t & 1) + 8 * h + j;
-                    uint32_t bit = (blk->qh[l] >> sub) & 1u;
-                    v |= bit << (4 * q5hpos(j) + dd);
-                }
-            }
-        }
-        dst[1152 + s] = v;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Q6_K -> P6K
 
 __device__ static inline int q6k_code(const lfamd_block_q6_K *blk, int k) { // 0..63
     int p = k >> 7, wi = k & 127, l = wi & 31, quarter = wi >> 5;
@@ -175,6 +62,257 @@ __device__ static inline int q6k_code(const lfamd_block_q6_K *blk, int k) { // 0
     return nib | (hi << 4);
 }
 
+// bytes of a block; the legacy 32-blocks: {d, [m], [qh[4]], qs[16]}
+__host__ __device__ static constexpr int gguf_block(int type) {
+    return type == LFAMD_TYPE_Q4_K     ? 144
+           : type == LFAMD_TYPE_Q5_K   ? 176
+           : type == LFAMD_TYPE_Q6_K   ? 210
+           : type == LFAMD_TYPE_Q2_K   ? 84
+           : type == LFAMD_TYPE_Q3_K   ? 110
+           : type == LFAMD_TYPE_IQ4_XS ? 136
+           : type == LFAMD_TYPE_Q4_1   ? 20
+           : type == LFAMD_TYPE_Q5_0   ? 22
+           : type == LFAMD_TYPE_Q5_1   ? 24
+                                       : 18; // Q4_0, IQ4_NL
+}
+__host__ __device__ static constexpr bool gguf_has_m(int type) {
+    return type == LFAMD_TYPE_Q4_1 || type == LFAMD_TYPE_Q5_1;
+}
+__host__ __device__ static constexpr bool gguf_has_h(int type) {
+    return type == LFAMD_TYPE_Q5_0 || type == LFAMD_TYPE_Q5_1;
+}
+
+// kb: 32-blocks of a raw row of the legacy types.  kb < 8 nb (LFAMD_TYPE_PAD256): the blocks from kb on are not read and count as zero
+// bytes (d = +0, m = +0, nibbles and fifth bits 0), for every row of the tile.  The other types have whole super-blocks.
+template <int TYPE>
+__device__ static inline int gguf_code(const uint8_t *row, int b, int k, int kb) {
+    if constexpr (TYPE == LFAMD_TYPE_Q4_K) {
+        const lfamd_block_q4_K *blk = (const lfamd_block_q4_K *)row + b;
+        const uint8_t byte = blk->qs[32 * (k >> 6) + (k & 31)];
+        return (k & 32) ? byte >> 4 : byte & 15;
+    } else if constexpr (TYPE == LFAMD_TYPE_Q5_K) { // weight l of sub-block j has its fifth bit at bit j of qh[l]
+        const lfamd_block_q5_K *blk = (const lfamd_block_q5_K *)row + b;
+        const uint8_t byte = blk->qs[32 * (k >> 6) + (k & 31)];
+        return ((k & 32) ? byte >> 4 : byte & 15) | (((blk->qh[k & 31] >> (k >> 5)) & 1) << 4);
+    } else if constexpr (TYPE == LFAMD_TYPE_Q2_K) {
+        return code16<TYPE>(row + (size_t)b * gguf_block(TYPE), k >> 4, k & 15);
+    } else if constexpr (TYPE == LFAMD_TYPE_Q3_K) { // q + 4 in 0..7
+        return code16<TYPE>(row + (size_t)b * gguf_block(TYPE), k >> 4, k & 15) + 4;
+    } else if constexpr (TYPE == LFAMD_TYPE_IQ4_XS) { // the codebook index
+        const lfamd_block_iq4_xs *blk = (const lfamd_block_iq4_xs *)row + b;
+        const uint8_t byte = blk->qs[16 * (k >> 5) + (k & 15)];
+        return (k & 16) ? byte >> 4 : byte & 15;
+    } else { // weight l of a 32-block: low nibble of qs[l] (l < 16) or high nibble of qs[l - 16], fifth bit = bit l of qh
+        constexpr int BS = gguf_block(TYPE), QH_OFF = gguf_has_m(TYPE) ? 4 : 2, QS_OFF = QH_OFF + (gguf_has_h(TYPE) ? 4 : 0);
+        const int bl = b * 8 + (k >> 5), l = k & 31;
+        const uint8_t *blk = row + (size_t)bl * BS;
+        const uint8_t byte = bl < kb ? blk[QS_OFF + (l & 15)] : (uint8_t)0; // (a guarded load, not an early return: the eight loads
+        int c = l < 16 ? byte & 15 : byte >> 4;                             // of a dword stay in flight together)
+        if constexpr (gguf_has_h(TYPE)) {
+            const uint8_t hb = bl < kb ? blk[QH_OFF + (l >> 3)] : (uint8_t)0;
+            c |= ((hb >> (l & 7)) & 1) << 4;
+        }
+        return c;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Images: the sections of a tile, in dwords.  IMG is the layout id of lfamd_internal.h, or one of the canonical per-call images.
+enum { IMG_PCK2 = LY_NONE + 1, IMG_PCK3, IMG_PC8 }; // PCK from Q2_K / Q3_K rows, PC8 from IQ4_XS rows
+enum {
+    S_NIB,   // 1024: the nibble lattice, 4 groups g x 64 lanes x 4 dwords dd: K-step t = 4 g + dd of lane (i, h), low four bits
+    S_HDR,   // 128 per part: 32 rows x 4 header words (hdr_word)
+    S_FIFTH, // 256: 64 lanes x 4 groups: the fifth bits of the group's four K-steps
+    S_BIT2,  // 512: PK2 / PK3, the low two bits of two K-steps per dword
+    S_BIT3,  // 256: PK3's third bits of four K-steps per dword
+    S_ROW,   // 32: one word per row (row_word)
+    S_BYTE   // 2048: PC8, one byte per weight
+};
+struct tile_sections {
+    int type;     // the GGUF type the tile is made from
+    int n;        // sections
+    int kind[4];
+    int first[5]; // first dword of each section; first[n]: dwords of the tile
+};
+__host__ __device__ static constexpr tile_sections sections_of(int img) {
+    switch (img) {
+    case LY_P4K:
+        return {LFAMD_TYPE_Q4_K, 2, {S_NIB, S_HDR}, {0, P4K_HDR / 4, P4K_TILE / 4}};
+    case LY_P40: // (IQ4_NL, LY_P4N: the same image)
+        return {LFAMD_TYPE_Q4_0, 2, {S_NIB, S_HDR}, {0, P4K_HDR / 4, P4K_TILE / 4}};
+    case LY_PX4:
+        return {LFAMD_TYPE_IQ4_XS, 2, {S_NIB, S_HDR}, {0, P4K_HDR / 4, P4K_TILE / 4}};
+    case LY_P5K:
+        return {LFAMD_TYPE_Q5_K, 3, {S_NIB, S_HDR, S_FIFTH}, {0, P5K_HDR / 4, P5K_QH / 4, P5K_TILE / 4}};
+    case LY_PCL41: // (two header parts: d, m)
+        return {LFAMD_TYPE_Q4_1, 3, {S_NIB, S_HDR, S_FIFTH}, {0, PCL_D / 4, PCL_QH / 4, PCL_TILE / 4}};
+    case LY_PCL50:
+        return {LFAMD_TYPE_Q5_0, 3, {S_NIB, S_HDR, S_FIFTH}, {0, PCL_D / 4, PCL_QH / 4, PCL_TILE / 4}};
+    case LY_PCL51:
+        return {LFAMD_TYPE_Q5_1, 3, {S_NIB, S_HDR, S_FIFTH}, {0, PCL_D / 4, PCL_QH / 4, PCL_TILE / 4}};
+    case LY_PK2:
+        return {LFAMD_TYPE_Q2_K, 3, {S_BIT2, S_HDR, S_ROW}, {0, PK2_SC / 4, PK2_D / 4, PK2_TILE / 4}};
+    case LY_PK3:
+        return {LFAMD_TYPE_Q3_K, 4, {S_BIT2, S_BIT3, S_HDR, S_ROW}, {0, PK3_HB / 4, PK3_SC / 4, PK3_D / 4, PK3_TILE / 4}};
+    case IMG_PCK2: // (two header parts: scales, mins)
+        return {LFAMD_TYPE_Q2_K, 3, {S_NIB, S_HDR, S_ROW}, {0, PCK_SC / 4, PCK_D / 4, PCK_TILE / 4}};
+    case IMG_PCK3:
+        return {LFAMD_TYPE_Q3_K, 3, {S_NIB, S_HDR, S_ROW}, {0, PCK_SC / 4, PCK_D / 4, PCK_TILE / 4}};
+    case IMG_PC8:
+        return {LFAMD_TYPE_IQ4_XS, 2, {S_BYTE, S_HDR}, {0, PC8_HDR / 4, PC8_TILE / 4}};
+    default:
+        return {0, 0, {}, {}};
+    }
+}
+
+// Header word q of a row: q = 0..3, and 4..7 where the image has a second part.
+//   P4K / P5K    the block's first 16 bytes {d, dmin, scales[12]}
+//   P40 / PCL    d of the 32-blocks 2q, 2q + 1; second part (PCL): their m, zeros for the types without
+//   PX4 / PC8    {8 int8 sub-block scales (ls - 32), f16 d, pad}
+//   PK2          the block's scale bytes sc | mn << 4;  PK3: int8 6-bit scale - 32;  PCK: int8 scales, second part uint8 mins
+template <int IMG>
+__device__ static inline uint32_t hdr_word(const uint8_t *row, int b, int q, int kb) {
+    constexpr int TYPE = sections_of(IMG).type, BS = gguf_block(TYPE);
+    uint32_t v = 0;
+    if constexpr (IMG == LY_P4K || IMG == LY_P5K) {
+        // raw blocks are only 2-byte aligned in general (row strides are multiples of 144, so 4-byte here, but stay safe)
+        const uint16_t *p = (const uint16_t *)(row + (size_t)b * BS + 4 * q);
+        v = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
+    } else if constexpr (IMG == LY_P40 || IMG == LY_PCL41 || IMG == LY_PCL50 || IMG == LY_PCL51) {
+        const int is_m = q >> 2, bl = b * 8 + 2 * (q & 3);
+        if (!is_m || gguf_has_m(TYPE)) {
+            const uint8_t *blk = row + (size_t)bl * BS + (is_m ? 2 : 0);
+            const uint32_t lo = bl < kb ? *(const uint16_t *)blk : 0u, hi = bl + 1 < kb ? *(const uint16_t *)(blk + BS) : 0u;
+            v = lo | (hi << 16);
+        }
+    } else if constexpr (IMG == LY_PX4 || IMG == IMG_PC8) {
+        const lfamd_block_iq4_xs *blk = (const lfamd_block_iq4_xs *)row + b;
+        if (q < 2) {
+            for (int e = 0; e < 4; e++) {
+                const int ib = 4 * q + e;
+                const int ls = ((blk->scales_l[ib / 2] >> (4 * (ib % 2))) & 0xf) | (((blk->scales_h >> (2 * ib)) & 3) << 4);
+                v |= (uint32_t)((ls - 32) & 0xff) << (8 * e);
+            }
+        } else if (q == 2) {
+            v = blk->d;
+        }
+    } else {
+        for (int e = 0; e < 4; e++) {
+            int sc, mn;
+            float d, dmin;
+            scale16<TYPE>(row + (size_t)b * BS, 4 * (q & 3) + e, sc, mn, d, dmin);
+            v |= (uint32_t)((IMG == LY_PK2 ? sc | (mn << 4) : q >= 4 ? mn : sc) & 0xff) << (8 * e);
+        }
+    }
+    return v;
+}
+// PK2 / PK3 / PCK: {d, dmin} of the row's block (both were f16 in the block: exact round trip)
+template <int IMG>
+__device__ static inline uint32_t row_word(const uint8_t *row, int b) {
+    constexpr int TYPE = sections_of(IMG).type;
+    int sc, mn;
+    float d, dmin;
+    scale16<TYPE>(row + (size_t)b * gguf_block(TYPE), 0, sc, mn, d, dmin);
+    return (uint32_t)f2h_bits(d) | ((uint32_t)f2h_bits(dmin) << 16);
+}
+
+// The lattice walk: the eight weights k = 16 t + 8 h + j of K-step t of lane half h; place(j, code) gives weight j's bits in the dword.
+// (j stays a compile-time index: a position table indexed by a runtime j would go through scratch memory.)
+template <int TYPE, class PLACE>
+__device__ static inline uint32_t lat_walk(const uint8_t *row, int b, int kb, int t, int h, PLACE place) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        v |= place(j, (uint32_t)gguf_code<TYPE>(row, b, 16 * t + 8 * h + j, kb));
+    return v;
+}
+// bits (code >> lo) & mask of weight j at bit 4 NIBPOS(j) + at: the nibble section, PK2 / PK3's two- and third-bit sections
+template <int TYPE>
+__device__ static inline uint32_t lat_bits(const uint8_t *row, int b, int kb, int t, int h, int lo, uint32_t mask, int at) {
+    return lat_walk<TYPE>(row, b, kb, t, h, [=](int j, uint32_t c) { return ((c >> lo) & mask) << (4 * NIBPOS(j) + at); });
+}
+
+// the rows of a tile: row i at base + i * stride, rows from n on lie past the matrix (zeros are written)
+struct tile_rows {
+    const uint8_t *base;
+    size_t stride;
+    int n;
+    __device__ const uint8_t *operator()(int i) const {
+        return base + (size_t)i * stride;
+    }
+};
+
+// dword w of the tile, from section E on
+template <int IMG, int E>
+__device__ static inline uint32_t tile_dword(int w, const tile_rows &row, int b, int kb) {
+    constexpr tile_sections S = sections_of(IMG);
+    constexpr int TYPE = S.type;
+    if constexpr (E == S.n) {
+        return 0;
+    } else {
+        if (w >= S.first[E + 1])
+            return tile_dword<IMG, E + 1>(w, row, b, kb);
+        constexpr int KIND = S.kind[E];
+        const int s = w - S.first[E];
+        const int lane = (s >> 2) & 63, i = lane & 31, h = lane >> 5; // (all but S_BIT3, S_ROW)
+        uint32_t v = 0;
+        if constexpr (KIND == S_NIB) {
+            if (const uint8_t *r = row(i); i < row.n)
+                v = lat_bits<TYPE>(r, b, kb, 4 * (s >> 8) + (s & 3), h, 0, 15, 0);
+        } else if constexpr (KIND == S_HDR) {
+            if (const uint8_t *r = row(i); i < row.n)
+                v = hdr_word<IMG>(r, b, 4 * (s >> 7) + (s & 3), kb);
+        } else if constexpr (KIND == S_FIFTH) { // element j of K-step dd of group g = s & 3 at bit 4 q5hpos(j) + dd
+            if (const uint8_t *r = row(i); i < row.n) {
+#pragma unroll
+                for (int dd = 0; dd < 4; dd++)
+                    v |= lat_walk<TYPE>(r, b, kb, 4 * (s & 3) + dd, h, [=](int j, uint32_t c) { return (c >> 4) << (4 * q5hpos(j) + dd); });
+            }
+        } else if constexpr (KIND == S_BIT2) { // dword u of [gsel][lane]: K-steps 8 gsel + 2 u (bits 0-1 of a nibble) and + 1 (bits 2-3)
+            if (const uint8_t *r = row(i); i < row.n)
+                for (int e = 0; e < 2; e++)
+                    v |= lat_bits<TYPE>(r, b, kb, 8 * (s >> 8) + 2 * (s & 3) + e, h, 0, 3, 2 * e);
+        } else if constexpr (KIND == S_BIT3) { // dword x of [gsel][lane]: K-steps 8 gsel + 4 x + e at bit 4 NIBPOS(j) + e
+            const int ln = (s >> 1) & 63;
+            if (const uint8_t *r = row(ln & 31); (ln & 31) < row.n)
+                for (int e = 0; e < 4; e++)
+                    v |= lat_bits<TYPE>(r, b, kb, 8 * (s >> 7) + 4 * (s & 1) + e, ln >> 5, 2, 1, e);
+        } else if constexpr (KIND == S_ROW) {
+            if (const uint8_t *r = row(s); s < row.n)
+                v = row_word<IMG>(r, b);
+        } else { // S_BYTE: K-steps 2 g', 2 g' + 1 of the lane in 16 bytes; kvalues_iq4nl applied here, so the GEMM sees plain integers
+            const int e = s & 3, t = 2 * (s >> 8) + (e >> 1);
+            if (const uint8_t *r = row(i); i < row.n)
+                for (int jj = 0; jj < 4; jj++) {
+                    const int val = kvalues_iq4nl_dev[gguf_code<TYPE>(r, b, 16 * t + 8 * h + 4 * (e & 1) + jj, kb)];
+                    v |= (uint32_t)((val + 128) & 0xff) << (8 * jj);
+                }
+        }
+        return v;
+    }
+}
+
+// One thread per output dword; every dword of every tile is written, zeros included.  nb: super-blocks of an image row.
+template <int IMG>
+__global__ void pack_tiles_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb, int kb,
+                                  uint8_t *__restrict__ out, long n_tiles) {
+    constexpr int NDW = sections_of(IMG).first[sections_of(IMG).n];
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long tile = tid / NDW;
+    const int w = (int)(tid % NDW);
+    if (tile >= n_tiles)
+        return;
+    const long rt = tile / nb;
+    const int b = (int)(tile % nb);
+    const long left = rows - rt * 32;
+    const tile_rows row = {raw + rt * 32 * raw_row_bytes, raw_row_bytes, left < 32 ? (int)left : 32};
+    ((uint32_t *)(out + tile * (NDW * 4)))[w] = tile_dword<IMG, 0>(w, row, b, kb);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Q6_K -> P6K: a kernel of its own.  As an instantiation of pack_tiles_kernel (sections: nibbles, upper two bits, scales, d) the
+// image was the same, and the largest tensor of a model, 128256 x 4096, packed 0.9 % slower (473.8 us against 469.4:
+// profiles/pack_images_q6k_writers.txt).  The nibble section is the lattice of lat_bits; the upper two bits sit at qhbit.
 __global__ void pack_q6k_kernel(const uint8_t *__restrict__ raw, size_t raw_row_bytes, long rows, int nb,
                                 uint8_t *__restrict__ out, long n_tiles) {
     long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -238,7 +376,6 @@ __global__ void pack_q6k_kernel(const uint8_t *__restrict__ raw, size_t raw_row_
         dst[w] = v;
     }
 }
-
 // ---------------------------------------------------------------------------------------------
 // Q8_0 -> P80
 
@@ -295,571 +432,65 @@ __global__ void pack_raw_kernel(const uint8_t *__restrict__ raw, size_t raw_row_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Activation preparation for the MFMA GEMM: llamafile-order Q8_K rows ->
-//   Xh  [nb][n_pad][256] f16  integer codes q8 (exact in f16), zero rows beyond n.  Super-block major: a token
-//                             tile's codes of one super-block are ONE contiguous run (a [n_pad][k] matrix puts the
-//                             tile's 512-byte row pieces a power-of-two stride apart -> they camp on 2 of the 16
-//                             L2 channels and the GEMM's operand stream tops out near 10 TB/s)
-//   d8T [nb][n_pad]     f32   block scales, transposed so a token tile's scales are contiguous
-//   Xm  [nb][n_pad][16] f16   mins operand: for the 8 pair sums S_j = bsums[2j]+bsums[2j+1]
-//                             (|S_j| <= 4096) the split S_j = 64*hi_j + lo_j, lo in [0,63]:
-//                             elements 0..7 = lo_j, 8..15 = hi_j (both exact in f16)
+// Batches of Q2_K / Q3_K / IQ4_XS: the resident compact image -> the canonical image the MFMA body reads, into the caller's
+// workspace (per call).
 
-// mins16 == 1: Xm holds the 16 bsums themselves (exact in f16, |sum| <= 2032) for the types with 16-wide sub-blocks (Q2_K)
-// mins16 == 2: SCALED staging for the scaled-operand body (gemm_lw.hip, FAST): Xh = f16(d8 * code), Xm = f16(d8 * S_j) in
-//              elements 0..7 and zeros in 8..15 — one f16 rounding per operand, no per-super-block scaling in the GEMM
-__device__ static inline _Float16 sat_f16(float v) {
-    return (_Float16)fminf(fmaxf(v, -65504.0f), 65504.0f);
-}
-__global__ void prep_q8k_kernel(const uint8_t *__restrict__ B, size_t b_row_bytes, long n, long n_pad, int nb,
-                                _Float16 *__restrict__ Xh, float *__restrict__ d8T, _Float16 *__restrict__ Xm, int mins16,
-                                const int32_t *__restrict__ src_idx) {
-    long blk = blockIdx.x; // (token, super-block)
-    long tok = blk / nb;
-    int b = (int)(blk % nb);
-    int t = threadIdx.x; // 64 threads: 4 codes each
-    _Float16 *xo = Xh + ((size_t)b * n_pad + tok) * 256;
-    // src_idx (MUL_MAT_ID batches): token slot -> activation row, -1 = padding slot
-    const long src = src_idx ? (long)src_idx[tok] : (tok < n ? tok : -1);
-    if (src >= 0) {
-        const lfamd_block_q8_K *y = (const lfamd_block_q8_K *)(B + src * b_row_bytes) + b;
-        uint32_t q = *(const uint32_t *)((const uint8_t *)y->qs + 4 * t); // 292-byte blocks are 4-aligned
-        const float xs = mins16 == 2 ? y->d : 1.0f;
-        for (int e = 0; e < 4; e++)
-            xo[4 * t + e] = sat_f16((float)(int)(int8_t)(q >> (8 * e)) * xs);
-        if (t == 0)
-            d8T[(size_t)b * n_pad + tok] = y->d;
-        if (mins16 == 2) {
-            if (t < 8) {
-                _Float16 *mo = Xm + ((size_t)b * n_pad + tok) * 16;
-                mo[t] = sat_f16((float)((int)y->bsums[2 * t] + (int)y->bsums[2 * t + 1]) * xs);
-                mo[8 + t] = (_Float16)0;
-            }
-        } else if (mins16) {
-            if (t < 16)
-                Xm[((size_t)b * n_pad + tok) * 16 + t] = (_Float16)(int)y->bsums[t];
-        } else if (t < 8) {
-            int S = (int)y->bsums[2 * t] + (int)y->bsums[2 * t + 1];
-            int lo = S & 63, hi = (S - lo) / 64;
-            _Float16 *mo = Xm + ((size_t)b * n_pad + tok) * 16;
-            mo[t] = (_Float16)lo;
-            mo[8 + t] = (_Float16)hi;
-        }
-    } else {
-        for (int e = 0; e < 4; e++)
-            xo[4 * t + e] = (_Float16)0;
-        if (t == 0)
-            d8T[(size_t)b * n_pad + tok] = 0.0f;
-        if (t < 16)
-            Xm[((size_t)b * n_pad + tok) * 16 + t] = (_Float16)0;
-    }
-}
-
-// Same outputs straight from f32 activations: quantise exactly like quantize_row_q8_K (first index of
-// the largest |x|, iscale = -128/max, nearest-even, clamp 127, d = 1/iscale) without materialising
-// the Q8_K blocks.  One wave per (token, super-block), 4 values per lane.
-__global__ __launch_bounds__(64) void prep_f32_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long n, long n_pad,
-                                                      int nb, _Float16 *__restrict__ Xh, float *__restrict__ d8T,
-                                                      _Float16 *__restrict__ Xm, int mins16, const int32_t *__restrict__ src_idx) {
-    long blk = blockIdx.x;
-    long tok = blk / nb;
-    int b = (int)(blk % nb);
-    int t = threadIdx.x;
-    _Float16 *xo = Xh + ((size_t)b * n_pad + tok) * 256;
-    typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-    const long src = src_idx ? (long)src_idx[tok] : (tok < n ? tok : -1); // as prep_q8k_kernel
-    if (src < 0) {
-        half4_t z = {(_Float16)0, (_Float16)0, (_Float16)0, (_Float16)0};
-        *(half4_t *)(xo + 4 * t) = z;
-        if (t == 0)
-            d8T[(size_t)b * n_pad + tok] = 0.0f;
-        if (t < 16)
-            Xm[((size_t)b * n_pad + tok) * 16 + t] = (_Float16)0;
+template <int TYPE>
+__global__ void pk_expand_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long n_tiles) {
+    constexpr bool Q3 = TYPE == LFAMD_TYPE_Q3_K;
+    constexpr int TILE = Q3 ? PK3_TILE : PK2_TILE, SC0 = Q3 ? PK3_SC : PK2_SC, D0 = Q3 ? PK3_D : PK2_D;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long tile = tid / (PCK_TILE / 4); // (the PCK sections of sections_of)
+    const int w = (int)(tid % (PCK_TILE / 4));
+    if (tile >= n_tiles)
         return;
-    }
-    const float4 f = *(const float4 *)((const float *)(X + src * x_row_bytes) + (size_t)b * 256 + 4 * t);
-    const float v[4] = {f.x, f.y, f.z, f.w};
-    float amax = 0.0f, val = 0.0f;
-    int idx = 4 * t;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        float ax = fabsf(v[e]);
-        if (ax > amax) {
-            amax = ax;
-            val = v[e];
-            idx = 4 * t + e;
+    const uint8_t *src = in + tile * TILE;
+    uint32_t *dst = (uint32_t *)(out + tile * PCK_TILE);
+    uint32_t v;
+    if (w < PCK_SC / 4) {
+        const int g = w >> 8, lane = (w >> 2) & 63, dd = w & 3;
+        const int t = 4 * g + dd, gsel = t >> 3, t8 = t & 7;
+        const uint32_t c = *(const uint32_t *)(src + gsel * 1024 + lane * 16 + (t8 >> 1) * 4);
+        v = ((t8 & 1) ? (c >> 2) : c) & 0x33333333u;
+        if constexpr (Q3) {
+            const uint32_t hb = *(const uint32_t *)(src + PK3_HB + gsel * 512 + lane * 8 + (t8 >> 2) * 4);
+            v |= ((hb >> (t8 & 3)) & 0x11111111u) << 2;
         }
+    } else if (w < PCK_D / 4) {
+        const int s4 = w - PCK_SC / 4, mins = s4 >= 128;
+        const int i = (s4 & 127) >> 2, u = s4 & 3;
+        const uint32_t sb = *(const uint32_t *)(src + SC0 + i * 16 + u * 4);
+        v = Q3 ? (mins ? 0u : sb) : (mins ? (sb >> 4) & 0x0F0F0F0Fu : sb & 0x0F0F0F0Fu);
+    } else {
+        v = *(const uint32_t *)(src + D0 + (w - PCK_D / 4) * 4);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float oa = __shfl_xor(amax, off, 64);
-        int oi = __shfl_xor(idx, off, 64);
-        float ov = __shfl_xor(val, off, 64);
-        if (oa > amax || (oa == amax && oi < idx)) {
-            amax = oa;
-            idx = oi;
-            val = ov;
-        }
-    }
-    int q[4] = {0, 0, 0, 0};
-    float d = 0.0f;
-    if (amax != 0.0f) {
-        const float iscale = -128.0f / val;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            int c = (int)rintf(iscale * v[e]);
-            q[e] = c > 127 ? 127 : c;
-        }
-        d = 1.0f / iscale;
-    }
-    const float xs = mins16 == 2 ? d : 1.0f;
-    half4_t h4 = {sat_f16((float)q[0] * xs), sat_f16((float)q[1] * xs), sat_f16((float)q[2] * xs), sat_f16((float)q[3] * xs)};
-    *(half4_t *)(xo + 4 * t) = h4;
-    int S = q[0] + q[1] + q[2] + q[3]; // pair sum j = t/8 covers codes 32j..32j+31 = lanes 8j..8j+7
-    S += __shfl_xor(S, 1, 64);
-    S += __shfl_xor(S, 2, 64);
-    if (mins16 == 1 && (t & 3) == 0) // bsums[t/4]: codes 16(t/4) .. +15
-        Xm[((size_t)b * n_pad + tok) * 16 + (t >> 2)] = (_Float16)S;
-    S += __shfl_xor(S, 4, 64);
-    if (mins16 == 2) {
-        if ((t & 7) == 0) {
-            _Float16 *mo = Xm + ((size_t)b * n_pad + tok) * 16;
-            mo[t >> 3] = sat_f16((float)S * xs);
-            mo[8 + (t >> 3)] = (_Float16)0;
-        }
-    } else if (!mins16 && (t & 7) == 0) {
-        int j = t >> 3;
-        int lo = S & 63, hi = (S - lo) / 64;
-        _Float16 *mo = Xm + ((size_t)b * n_pad + tok) * 16;
-        mo[j] = (_Float16)lo;
-        mo[8 + j] = (_Float16)hi;
-    }
-    if (t == 0)
-        d8T[(size_t)b * n_pad + tok] = d;
+    dst[w] = v;
 }
 
-// SCALED staging with a per-token power-of-two normalisation (mode 2, the scaled-operand GEMM of gemm_lw.hip):
-//   Xh = f16(d8 * code * 2^-e(token)),  Xm[0..7] = f16(d8 * S_j * 2^-e), Xm[8..15] = 0,  tok_scale[token] = 2^e
-// with e chosen so that the token's largest |d8 * 128| lands in [512, 1024): no f16 overflow for huge activations, no
-// subnormals for tiny ones, and — a power of two commutes with the rounding — the same bits as the unnormalised staging
-// wherever that one is in range.  The GEMM multiplies its output column by tok_scale when it stores.
-// One work-group per token: pass 1 finds the largest block scale (|d8| = amax / 128), pass 2 quantises exactly like
-// prep_f32_kernel / prep_q8k_kernel (the second read of the row hits the caches).
-// MAXJ > 0: the wave's super-blocks (b = wave + 16 j, j < MAXJ) are loaded ONCE, all loads in flight together, and both
-// passes run from registers (one memory round trip per token; 16 waves per token keep as many waves in flight as the per-super-block kernels);
-// MAXJ == 0: any nb, the row is read twice (the second time from the caches).
-template <bool F32IN, int MAXJ, int NW>
-__global__ __launch_bounds__(NW * 64) void prep_scaled_kernel(const uint8_t *__restrict__ X, size_t row_bytes, long n, long n_pad, int nb,
-                                                          _Float16 *__restrict__ Xh, float *__restrict__ tok_scale,
-                                                          _Float16 *__restrict__ Xm, const int32_t *__restrict__ src_idx) {
-    __shared__ float wmax[NW]; // NW = 4 or 16 waves per token
-    typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-    constexpr int NJ = MAXJ > 0 ? MAXJ : 1;
-    const long tok = blockIdx.x;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const long src = src_idx ? (long)src_idx[tok] : (tok < n ? tok : -1);
-    if (src < 0) { // padding slot: zero codes, never stored
-        const half4_t z = {(_Float16)0, (_Float16)0, (_Float16)0, (_Float16)0};
-        for (int b = wave; b < nb; b += NW) {
-            *(half4_t *)(Xh + ((size_t)b * n_pad + tok) * 256 + 4 * lane) = z;
-            if (lane < 16)
-                Xm[((size_t)b * n_pad + tok) * 16 + lane] = (_Float16)0;
-        }
-        if (t == 0)
-            tok_scale[tok] = 0.0f;
+// batches: compact image -> the PC8 byte image (codebook value + 128) the MFMA body reads, per call, into the workspace
+__global__ void pk4x_expand_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, long n_tiles, long rows, int nb) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long tile = tid / (PC8_TILE / 4); // (the PC8 sections of sections_of)
+    const int w = (int)(tid % (PC8_TILE / 4));
+    if (tile >= n_tiles)
         return;
-    }
-    const uint8_t *row = X + src * row_bytes;
-    // what a lane holds of super-block b: four f32 values, or four codes and the block scale
-    float4 fv[NJ];
-    uint32_t qv[NJ];
-    float dv[NJ];
-    auto load = [&](int b, float4 &f, uint32_t &w, float &d) {
-        if constexpr (F32IN) {
-            f = *(const float4 *)((const float *)row + (size_t)b * 256 + 4 * lane);
-        } else {
-            const lfamd_block_q8_K *y = (const lfamd_block_q8_K *)row + b;
-            w = *(const uint32_t *)((const uint8_t *)y->qs + 4 * lane);
-            d = y->d;
-        }
-    };
-    auto block_amax = [&](const float4 &f, float d) -> float { // |d8| * 128 (lane-local part for f32 input)
-        if constexpr (F32IN)
-            return fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w)));
-        else
-            return fabsf(d) * 128.0f;
-    };
-    float dmax = 0.0f;
-    if constexpr (MAXJ > 0) {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            fv[j] = make_float4(0.f, 0.f, 0.f, 0.f), qv[j] = 0, dv[j] = 0.0f;
-            if (wave + NW * j < nb)
-                load(wave + NW * j, fv[j], qv[j], dv[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; j++)
-            dmax = fmaxf(dmax, block_amax(fv[j], dv[j]));
-    } else {
-        for (int b = wave; b < nb; b += NW) {
-            load(b, fv[0], qv[0], dv[0]);
-            dmax = fmaxf(dmax, block_amax(fv[0], dv[0]));
-        }
-    }
-    // (DPP + readlane reductions: the ds_bpermute butterflies of the first version — about twenty LDS round trips per
-    // thread — made this 12 MB conversion take 7.5 us)
-    dmax = wave_max_f32(dmax);
-    if (lane == 0)
-        wmax[wave] = dmax;
-    __syncthreads();
-    dmax = wmax[lane & (NW - 1)]; // (every wave reduces the NW partial maxima itself)
-    dmax = fmaxf(dmax, dpp_f32<DPP_XOR1>(dmax));
-    dmax = fmaxf(dmax, dpp_f32<DPP_XOR2>(dmax));
-    dmax = fmaxf(dmax, dpp_f32<DPP_HALF_MIRROR>(dmax));
-    dmax = fmaxf(dmax, dpp_f32<DPP_MIRROR>(dmax));
-    const bool ok = dmax > 0.0f && dmax < 3.0e38f; // (zero / non-finite rows: no normalisation)
-    const float scale = ok ? ldexpf(1.0f, 9 - ilogbf(dmax)) : 1.0f;
-    if (t == 0)
-        tok_scale[tok] = ok ? ldexpf(1.0f, ilogbf(dmax) - 9) : 1.0f;
-
-    auto emit = [&](int b, const float4 &f, uint32_t w, float dq) {
-        _Float16 *xo = Xh + ((size_t)b * n_pad + tok) * 256;
-        int q[4] = {0, 0, 0, 0};
-        float d = 0.0f;
-        if constexpr (F32IN) { // quantize_row_q8_K: first index of the largest |x|, iscale = -128 / max, nearest-even, clamp 127
-            const float v[4] = {f.x, f.y, f.z, f.w};
-            float amax = 0.0f, val = 0.0f;
-            int idx = 4 * lane;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const float ax = fabsf(v[e]);
-                if (ax > amax)
-                    amax = ax, val = v[e], idx = 4 * lane + e;
-            }
-            // the block's largest |x| (one value through the butterfly), then the FIRST lane holding it: lanes are in index
-            // order and `val` is already the lane's first such element, so this is quantize_row_q8_K's tie-break
-            const float bmax = wave_max_f32(amax);
-            const unsigned long long holders = __builtin_amdgcn_ballot_w64(amax == bmax);
-            val = readlane_f32(val, holders ? __builtin_ctzll(holders) : 0);
-            amax = bmax;
-            (void)idx;
-            // (branch-free: an all-zero block gives iscale = 0 -> codes 0, d = 0, like the reference's early return; with a
-            // branch per block the four blocks of a wave cannot be scheduled into each other)
-            const bool nz = amax != 0.0f;
-            const float iscale = nz ? -128.0f / val : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int c = (int)rintf(iscale * v[e]);
-                q[e] = c > 127 ? 127 : c;
-            }
-            d = nz ? 1.0f / iscale : 0.0f;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                q[e] = (int)(int8_t)(w >> (8 * e));
-            d = dq;
-        }
-        const float xs = d * scale;
-        const half4_t h4 = {sat_f16((float)q[0] * xs), sat_f16((float)q[1] * xs), sat_f16((float)q[2] * xs), sat_f16((float)q[3] * xs)};
-        *(half4_t *)(xo + 4 * lane) = h4;
-        int S = q[0] + q[1] + q[2] + q[3]; // pair sum j = lane / 8 covers codes 32j .. 32j+31
-        S += (int)dpp_u32<DPP_XOR1>((uint32_t)S);
-        S += (int)dpp_u32<DPP_XOR2>((uint32_t)S);
-        S += (int)dpp_u32<DPP_HALF_MIRROR>((uint32_t)S);
-        if ((lane & 7) == 0) {
-            _Float16 *mo = Xm + ((size_t)b * n_pad + tok) * 16;
-            mo[lane >> 3] = sat_f16((float)S * xs);
-            mo[8 + (lane >> 3)] = (_Float16)0;
-        }
-    };
-    if constexpr (MAXJ > 0) {
-        if (nb == NW * NJ) { // every wave has all NJ blocks: straight-line code, the blocks' dependent chains interleave
-#pragma unroll
-            for (int j = 0; j < NJ; j++)
-                emit(wave + NW * j, fv[j], qv[j], dv[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NJ; j++)
-                if (wave + NW * j < nb) // (wave-uniform)
-                    emit(wave + NW * j, fv[j], qv[j], dv[j]);
+    const uint8_t *src = in + tile * P4K_TILE;
+    uint32_t *dst = (uint32_t *)(out + tile * PC8_TILE);
+    uint32_t v = 0;
+    if (w < PC8_HDR / 4) {
+        const int g2 = w >> 8, lane = (w >> 2) & 63, e = w & 3;
+        const int t = 2 * g2 + (e >> 1);
+        const uint32_t x = *(const uint32_t *)(src + (t >> 2) * 1024 + lane * 16 + (t & 3) * 4);
+        if ((tile / nb) * 32 + (lane & 31) < rows) // (rows past the matrix: zero bytes, like the builder from GGUF rows)
+        for (int jj = 0; jj < 4; jj++) {
+            const int j = 4 * (e & 1) + jj;
+            const int val = kvalues_iq4nl_dev[(x >> (4 * NIBPOS(j))) & 15];
+            v |= (uint32_t)((val + 128) & 0xff) << (8 * jj);
         }
     } else {
-        for (int b = wave; b < nb; b += NW) {
-            load(b, fv[0], qv[0], dv[0]);
-            emit(b, fv[0], qv[0], dv[0]);
-        }
+        v = *(const uint32_t *)(src + P4K_HDR + (w - PC8_HDR / 4) * 4);
     }
-}
-
-// Activation preparation for the legacy 32-block weight types (Q4_0 ...): Q8_0 quantisation (upstream
-// quantize_row_q8_0: d = amax/127 stored as f16, q = roundf(x/d)) ->
-//   Xh  [nb][n_pad][256] f16 codes (as above);  d8T [nb*8][n_pad] f32 block scales.  One wave per (super-block, token).
-// Q81: Q8_1 activations (Q4_1 / Q5_1 weights): additionally sT [nb*8][n_pad] = the block's s = f16(d * sum(q)).
-// kb: 32-blocks of an activation row.  kb < 8 nb (a padded weight image, LFAMD_TYPE_PAD256): the blocks from kb on are not read —
-// what lies behind the row may be NaN — and staged as a row of zeros: codes, d and s all 0.  The eight lanes of a 32-block take the
-// same side, so the shuffles below stay among lanes that all loaded.  TAIL = false (whole rows, kb = 8 nb): the kernel as it was.
-template <bool F32IN, bool Q81, bool TAIL>
-__global__ __launch_bounds__(256) void prep80_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long n, long n_pad, int nb, int kb,
-                                                    _Float16 *__restrict__ Xh, float *__restrict__ d8T, float *__restrict__ sT) {
-    typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-    long blk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (blk >= (long)nb * n_pad)
-        return;
-    int b = (int)(blk / n_pad);
-    long tok = blk - (long)b * n_pad;
-    int t = threadIdx.x & 63; // codes 4t..4t+3 of the super-block: 32-block t >> 3
-    int q[4] = {0, 0, 0, 0};
-    float d = 0.0f, sv = 0.0f;
-    if (tok < n && (!TAIL || b * 8 + (t >> 3) < kb)) {
-        if constexpr (F32IN) {
-            const float4 f = *(const float4 *)((const float *)(X + tok * x_row_bytes) + (size_t)b * 256 + 4 * t);
-            const float v[4] = {f.x, f.y, f.z, f.w};
-            float amax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-            amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-            amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-            amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
-            const float dd = amax / 127.0f;
-            const float id = dd != 0.0f ? 1.0f / dd : 0.0f;
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                q[e] = (int)roundf(v[e] * id);
-            d = h2f(f2h_bits(dd));
-            if constexpr (Q81) { // upstream quantize_row_q8_1: s = f16(sum * d), d not yet rounded
-                int sum = q[0] + q[1] + q[2] + q[3];
-                sum += __shfl_xor(sum, 1, 64);
-                sum += __shfl_xor(sum, 2, 64);
-                sum += __shfl_xor(sum, 4, 64);
-                sv = h2f(f2h_bits_of_product((float)sum, dd));
-            }
-        } else {
-            constexpr int BSZ = Q81 ? 36 : 34, QOFF = Q81 ? 4 : 2;
-            const uint8_t *y = X + tok * x_row_bytes + (size_t)(b * 8 + (t >> 3)) * BSZ; // 2-byte aligned blocks
-            const uint16_t *p = (const uint16_t *)(y + QOFF + 4 * (t & 7));
-            if constexpr (Q81)
-                sv = h2f(*(const uint16_t *)(y + 2));
-            const uint32_t w = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                q[e] = (int)(int8_t)(w >> (8 * e));
-            d = h2f(*(const uint16_t *)y);
-        }
-    }
-    half4_t h4 = {(_Float16)q[0], (_Float16)q[1], (_Float16)q[2], (_Float16)q[3]};
-    *(half4_t *)(Xh + ((size_t)b * n_pad + tok) * 256 + 4 * t) = h4;
-    if ((t & 7) == 0) {
-        d8T[((size_t)b * 8 + (t >> 3)) * n_pad + tok] = d;
-        if constexpr (Q81)
-            sT[((size_t)b * 8 + (t >> 3)) * n_pad + tok] = sv;
-    }
-}
-
-// Activation preparation for the float weight types (F16 / BF16): Xh [nb][n_pad][256] of 2-byte values — f32 rows
-// converted like ggml does before calling sgemm (f16: round to nearest even; bf16: ggml_compute_fp32_to_bf16, nearest even
-// with NaN quieting) or rows already in the weight's type copied.  One wave per (super-block, token).
-template <int OUT, bool F32IN>
-__global__ __launch_bounds__(256) void prep_float_kernel(const uint8_t *__restrict__ X, size_t x_row_bytes, long n, long n_pad,
-                                                        int nb, uint16_t *__restrict__ Xh) {
-    long blk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (blk >= (long)nb * n_pad)
-        return;
-    int b = (int)(blk / n_pad);
-    long tok = blk - (long)b * n_pad;
-    int t = threadIdx.x & 63;
-    uint16_t o[4] = {0, 0, 0, 0};
-    if (tok < n) {
-        // rows of float weights' activations may sit at any element-aligned address (include/lfamd_hip.h): whole 16- / 8-byte loads
-        // only where the row is aligned to them, element by element otherwise (the same values either way)
-        const uint8_t *row = X + tok * x_row_bytes;
-        if constexpr (F32IN) {
-            const float *src = (const float *)row + (size_t)b * 256 + 4 * t;
-            float v[4];
-            if (((uintptr_t)row & 15) == 0) {
-                const float4 f = *(const float4 *)src;
-                v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    v[e] = src[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                if constexpr (OUT == LFAMD_TYPE_F16) {
-                    o[e] = f2h_bits(v[e]);
-                } else {
-                    const uint32_t u = __builtin_bit_cast(uint32_t, v[e]);
-                    o[e] = (u & 0x7fffffffu) > 0x7f800000u ? (uint16_t)((u >> 16) | 64) : (uint16_t)((u + (0x7fffu + ((u >> 16) & 1))) >> 16);
-                }
-            }
-        } else if (((uintptr_t)row & 7) == 0) {
-            const uint2 w = *(const uint2 *)(row + ((size_t)b * 256 + 4 * t) * 2);
-            o[0] = (uint16_t)w.x, o[1] = (uint16_t)(w.x >> 16), o[2] = (uint16_t)w.y, o[3] = (uint16_t)(w.y >> 16);
-        } else {
-            const uint16_t *src = (const uint16_t *)row + (size_t)b * 256 + 4 * t;
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                o[e] = src[e];
-        }
-    }
-    *(uint2 *)(Xh + ((size_t)b * n_pad + tok) * 256 + 4 * t) =
-        make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
-}
-
-// ---------------------------------------------------------------------------------------------
-// host-callable launchers (used by api.hip)
-
-extern "C" {
-
-hipError_t lfamd_launch_pack_q4k(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
-    int nb = (int)(cols / 256);
-    long n_tiles = ((rows + 31) / 32) * nb;
-    long threads = n_tiles * 1152;
-    pack_q4k_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb,
-                                                                        (uint8_t *)out, n_tiles);
-    return hipGetLastError();
-}
-
-// (cols: of a raw row, whole 32-blocks; the image has ceil(cols / 256) super-blocks per row)
-hipError_t lfamd_launch_pack_q40(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
-    int nb = (int)((cols + 255) / 256);
-    long n_tiles = ((rows + 31) / 32) * nb;
-    long threads = n_tiles * 1152;
-    pack_q40_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb, (int)(cols / 32),
-                                                                        (uint8_t *)out, n_tiles);
-    return hipGetLastError();
-}
-
-hipError_t lfamd_launch_pack_q5k(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
-    int nb = (int)(cols / 256);
-    long n_tiles = ((rows + 31) / 32) * nb;
-    long threads = n_tiles * 1408;
-    pack_q5k_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb,
-                                                                        (uint8_t *)out, n_tiles);
-    return hipGetLastError();
-}
-
-hipError_t lfamd_launch_pack_q6k(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
-    int nb = (int)(cols / 256);
-    long n_tiles = ((rows + 31) / 32) * nb;
-    long threads = n_tiles * 1680;
-    pack_q6k_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb,
-                                                                        (uint8_t *)out, n_tiles);
-    return hipGetLastError();
-}
-
-hipError_t lfamd_launch_pack_q80(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
-    int nblocks = (int)(cols / 32);
-    int nquads = (nblocks + 3) / 4;
-    long n_tiles = ((rows + 7) / 8) * nquads;
-    long threads = n_tiles * 272;
-    pack_q80_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nblocks,
-                                                                        nquads, (uint8_t *)out, n_tiles);
-    return hipGetLastError();
-}
-
-hipError_t lfamd_launch_pack_raw(const void *raw, size_t raw_row_bytes, long rows, size_t row_bytes, void *out,
-                                 hipStream_t s) {
-    size_t total = (size_t)rows * row_bytes;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65536)
-        blocks = 65536;
-    if (blocks == 0)
-        return hipSuccess;
-    pack_raw_kernel<<<(unsigned)blocks, 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, row_bytes, (uint8_t *)out);
-    return hipGetLastError();
-}
-
-// the register-resident forms up to 16 / 64 super-blocks (k <= 4096 / 16384: 1 / 4 per wave), the looping one beyond
-// register-resident forms: 4 waves per token with 4 / 16 super-blocks each (k <= 4096 / 16384) — a quarter of the waves of
-// the 16-wave form to launch and to meet at the barrier, four loads in flight per lane instead of one; the looping form beyond
-#define PREP_SCALED_GO(F32IN, SRC, RB)                                                                                 \
-    do {                                                                                                               \
-        if (nb <= 16)                                                                                                  \
-            prep_scaled_kernel<F32IN, 4, 4><<<(unsigned)n_pad, 256, 0, s>>>((const uint8_t *)SRC, RB, n, n_pad, nb, (_Float16 *)Xh, \
-                                                                           (float *)d8T, (_Float16 *)Xm, src_idx);      \
-        else if (nb <= 64)                                                                                             \
-            prep_scaled_kernel<F32IN, 16, 4><<<(unsigned)n_pad, 256, 0, s>>>((const uint8_t *)SRC, RB, n, n_pad, nb, (_Float16 *)Xh, \
-                                                                            (float *)d8T, (_Float16 *)Xm, src_idx);     \
-        else                                                                                                           \
-            prep_scaled_kernel<F32IN, 0, 16><<<(unsigned)n_pad, 1024, 0, s>>>((const uint8_t *)SRC, RB, n, n_pad, nb, (_Float16 *)Xh, \
-                                                                             (float *)d8T, (_Float16 *)Xm, src_idx);    \
-    } while (0)
-
-hipError_t lfamd_launch_prep_f32(const void *X, size_t x_row_bytes, long n, long n_pad, long cols, void *Xh, void *d8T,
-                                 void *Xm, int mins16, const int32_t *src_idx, hipStream_t s) {
-    int nb = (int)(cols / 256);
-    long blocks = n_pad * nb;
-    if (blocks == 0)
-        return hipSuccess;
-    if (mins16 == 2) // scaled staging: d8T receives the per-token output scales [n_pad]
-        PREP_SCALED_GO(true, X, x_row_bytes);
-    else
-        prep_f32_kernel<<<(unsigned)blocks, 64, 0, s>>>((const uint8_t *)X, x_row_bytes, n, n_pad, nb, (_Float16 *)Xh,
-                                                         (float *)d8T, (_Float16 *)Xm, mins16, src_idx);
-    return hipGetLastError();
-}
-
-// (cols: of an activation row, whole 32-blocks; the image has ceil(cols / 256) super-blocks per token)
-hipError_t lfamd_launch_prep80(int Btype, const void *B, size_t b_row_bytes, long n, long n_pad, long cols, void *Xh, void *d8T,
-                               void *sT, hipStream_t s) {
-    int nb = (int)((cols + 255) / 256), kb = (int)(cols / 32);
-    long blocks = n_pad * nb;
-    if (blocks == 0)
-        return hipSuccess;
-    const unsigned grid = (unsigned)((blocks + 3) / 4);
-    const uint8_t *X = (const uint8_t *)B;
-    const bool f32 = Btype == LFAMD_TYPE_F32, tail = kb != 8 * nb;
-#define PREP80_GO(F32IN, Q81, TAIL)                                                                                    \
-    prep80_kernel<F32IN, Q81, TAIL><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, kb, (_Float16 *)Xh, (float *)d8T, (float *)sT)
-    if (sT) { // Q8_1 activations
-        if (f32)
-            tail ? PREP80_GO(true, true, true) : PREP80_GO(true, true, false);
-        else
-            tail ? PREP80_GO(false, true, true) : PREP80_GO(false, true, false);
-    } else {
-        if (f32)
-            tail ? PREP80_GO(true, false, true) : PREP80_GO(true, false, false);
-        else
-            tail ? PREP80_GO(false, false, true) : PREP80_GO(false, false, false);
-    }
-#undef PREP80_GO
-    return hipGetLastError();
-}
-
-hipError_t lfamd_launch_prep_float(int Atype, int Btype, const void *B, size_t b_row_bytes, long n, long n_pad, long cols, void *Xh,
-                                   hipStream_t s) {
-    int nb = (int)(cols / 256);
-    long blocks = n_pad * nb;
-    if (blocks == 0)
-        return hipSuccess;
-    const unsigned grid = (unsigned)((blocks + 3) / 4);
-    const uint8_t *X = (const uint8_t *)B;
-    if (Atype == LFAMD_TYPE_F16) {
-        if (Btype == LFAMD_TYPE_F32)
-            prep_float_kernel<LFAMD_TYPE_F16, true><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (uint16_t *)Xh);
-        else
-            prep_float_kernel<LFAMD_TYPE_F16, false><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (uint16_t *)Xh);
-    } else {
-        if (Btype == LFAMD_TYPE_F32)
-            prep_float_kernel<LFAMD_TYPE_BF16, true><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (uint16_t *)Xh);
-        else
-            prep_float_kernel<LFAMD_TYPE_BF16, false><<<grid, 256, 0, s>>>(X, b_row_bytes, n, n_pad, nb, (uint16_t *)Xh);
-    }
-    return hipGetLastError();
-}
-
-hipError_t lfamd_launch_prep_q8k(const void *B, size_t b_row_bytes, long n, long n_pad, long cols, void *Xh, void *d8T,
-                                 void *Xm, int mins16, const int32_t *src_idx, hipStream_t s) {
-    int nb = (int)(cols / 256);
-    long blocks = n_pad * nb;
-    if (blocks == 0)
-        return hipSuccess;
-    if (mins16 == 2)
-        PREP_SCALED_GO(false, B, b_row_bytes);
-    else
-        prep_q8k_kernel<<<(unsigned)blocks, 64, 0, s>>>((const uint8_t *)B, b_row_bytes, n, n_pad, nb, (_Float16 *)Xh,
-                                                         (float *)d8T, (_Float16 *)Xm, mins16, src_idx);
-    return hipGetLastError();
-}
+    dst[w] = v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -895,12 +526,123 @@ __global__ void scaled_ok_kernel(const uint8_t *__restrict__ img, long tiles, in
         atomicOr(bad, 1);
 }
 
-extern "C" hipError_t lfamd_launch_scaled_ok(int type, long rows, long cols, const void *packed, int *d_flag, hipStream_t s) {
-    const bool q80 = type == LFAMD_TYPE_Q8_0;
-    const long tiles = q80 ? ((rows + 7) / 8) * ((cols / 32 + 3) / 4) : ((rows + 31) / 32) * (cols / 256);
-    const int tile_bytes = q80 ? P80_TILE : type == LFAMD_TYPE_Q5_K ? P5K_TILE : type == LFAMD_TYPE_Q6_K ? P6K_TILE : P4K_TILE;
-    const long threads = tiles * 32;
-    scaled_ok_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)packed, tiles, tile_bytes,
-                                                                       q80 ? 2 : type == LFAMD_TYPE_Q6_K ? 1 : 0, d_flag);
+// ---------------------------------------------------------------------------------------------
+// host-callable launchers and the sizes of the canonical images
+
+// cols: of a GGUF row (the legacy types: whole 32-blocks; the image has ceil(cols / 256) super-blocks per row)
+template <int IMG>
+static hipError_t launch_tiles(const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
+    constexpr int NDW = sections_of(IMG).first[sections_of(IMG).n];
+    const int nb = (int)((cols + 255) / 256), kb = (int)(cols / 32);
+    const long n_tiles = ((rows + 31) / 32) * nb;
+    if (n_tiles == 0)
+        return hipSuccess;
+    const long threads = n_tiles * NDW;
+    pack_tiles_kernel<IMG><<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb, kb, (uint8_t *)out,
+                                                                            n_tiles);
     return hipGetLastError();
+}
+
+extern "C" {
+
+hipError_t lfamd_launch_pack(const lfamd_image &im, const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
+    switch (im.ly) {
+#define TILES(LY)                                                                                                                          \
+    case LY:                                                                                                                               \
+        return launch_tiles<LY>(raw, raw_row_bytes, rows, cols, out, s);
+        TILES(LY_P4K)
+        TILES(LY_P5K)
+    case LY_P6K: {
+        int nb = (int)(cols / 256);
+        long n_tiles = ((rows + 31) / 32) * nb;
+        long threads = n_tiles * 1680;
+        pack_q6k_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nb, (uint8_t *)out, n_tiles);
+        return hipGetLastError();
+    }
+        TILES(LY_PK2)
+        TILES(LY_PK3)
+        TILES(LY_PX4)
+        TILES(LY_PCL41)
+        TILES(LY_PCL50)
+        TILES(LY_PCL51)
+    case LY_P4N:
+        TILES(LY_P40)
+#undef TILES
+    case LY_P80: {
+        int nblocks = (int)(cols / 32);
+        int nquads = (nblocks + 3) / 4;
+        long n_tiles = ((rows + 7) / 8) * nquads;
+        long threads = n_tiles * 272;
+        pack_q80_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, nblocks,
+                                                                            nquads, (uint8_t *)out, n_tiles);
+        return hipGetLastError();
+    }
+    case LY_NONE:
+        return hipErrorInvalidValue;
+    default: { // GGUF rows
+        const size_t row_bytes = lfamd_row_size(im.type, cols);
+        size_t total = (size_t)rows * row_bytes;
+        size_t blocks = (total + 255) / 256;
+        if (blocks > 65536)
+            blocks = 65536;
+        if (blocks == 0)
+            return hipSuccess;
+        pack_raw_kernel<<<(unsigned)blocks, 256, 0, s>>>((const uint8_t *)raw, raw_row_bytes, rows, row_bytes, (uint8_t *)out);
+        return hipGetLastError();
+    }
+    }
+}
+
+// the canonical images from GGUF rows: what the expanders below give from the resident compact images (tests/test_gpu_pack.py)
+size_t lfamd_wprep16_bytes(long rows, long cols) {
+    return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * PCK_TILE;
+}
+hipError_t lfamd_launch_wprep16(int type, const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
+    if (type == LFAMD_TYPE_Q2_K)
+        return launch_tiles<IMG_PCK2>(raw, raw_row_bytes, rows, cols, out, s);
+    if (type == LFAMD_TYPE_Q3_K)
+        return launch_tiles<IMG_PCK3>(raw, raw_row_bytes, rows, cols, out, s);
+    return hipErrorInvalidValue;
+}
+size_t lfamd_wprep8_bytes(long rows, long cols) {
+    return (size_t)((rows + 31) / 32) * (size_t)(cols / 256) * PC8_TILE;
+}
+hipError_t lfamd_launch_wprep8(int type, const void *raw, size_t raw_row_bytes, long rows, long cols, void *out, hipStream_t s) {
+    if (type != LFAMD_TYPE_IQ4_XS)
+        return hipErrorInvalidValue;
+    return launch_tiles<IMG_PC8>(raw, raw_row_bytes, rows, cols, out, s);
+}
+
+hipError_t lfamd_launch_pk4x_expand(const void *packed, long rows, long cols, void *out, hipStream_t s) {
+    const long n_tiles = ((rows + 31) / 32) * (cols / 256);
+    if (n_tiles == 0)
+        return hipSuccess;
+    const long threads = n_tiles * (PC8_TILE / 4);
+    pk4x_expand_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)packed, (uint8_t *)out, n_tiles, rows, (int)(cols / 256));
+    return hipGetLastError();
+}
+
+hipError_t lfamd_launch_pk_expand(int type, const void *packed, long rows, long cols, void *out, hipStream_t s) {
+    const long n_tiles = ((rows + 31) / 32) * (cols / 256);
+    if (n_tiles == 0)
+        return hipSuccess;
+    const long threads = n_tiles * (PCK_TILE / 4);
+    const unsigned grid = (unsigned)((threads + 255) / 256);
+    if (type == LFAMD_TYPE_Q2_K)
+        pk_expand_kernel<LFAMD_TYPE_Q2_K><<<grid, 256, 0, s>>>((const uint8_t *)packed, (uint8_t *)out, n_tiles);
+    else if (type == LFAMD_TYPE_Q3_K)
+        pk_expand_kernel<LFAMD_TYPE_Q3_K><<<grid, 256, 0, s>>>((const uint8_t *)packed, (uint8_t *)out, n_tiles);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t lfamd_launch_scaled_ok(int type, long rows, long cols, const void *packed, int *d_flag, hipStream_t s) {
+    const lfamd_image im = lfamd_image_of(type, cols); // (Q4_K, Q5_K, Q6_K or Q8_0: api.hip)
+    const long tiles = (long)im.tiles(rows);
+    const long threads = tiles * 32;
+    scaled_ok_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>((const uint8_t *)packed, tiles, im.tile,
+                                                                       im.ly == LY_P80 ? 2 : im.ly == LY_P6K ? 1 : 0, d_flag);
+    return hipGetLastError();
+}
 }

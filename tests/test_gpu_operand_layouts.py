@@ -216,7 +216,7 @@ def baseline(spec, base, Btype):
 
 def accepted(spec, Btype, b_off, stride):
     """The contract of include/lfamd_hip.h.  Every reader of f32 rows under quantised weights takes 16 bytes per lane —
-    prep_f32_kernel, prep_scaled_kernel and prep80_kernel (pack.hip), sb_prep_kernel (gemm_sb.hip), the staging of gemm_i8.hip,
+    prep_f32_kernel, prep_scaled_kernel and prep80_kernel (prep.hip), sb_prep_kernel (gemm_sb.hip), the staging of gemm_i8.hip,
     gemm_lf.hip and gemm_q80.hip as float4, the decode GEMVs as 16-byte buffer loads (gemv_impl.h: buf_ld16 on make_rsrc(row)) —
     so a base or a stride that is not a multiple of 16 is refused, not run.  Rows in a vec_dot format are read field by field and
     code word by code word at offsets that are only block-aligned inside a contiguous row already (292-, 36-, 34-byte blocks):
