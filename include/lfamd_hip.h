@@ -438,6 +438,41 @@ int lfamd_gemm_strided_batched_f16(long m, long n, long k, float alpha, const vo
 int lfamd_gemm_batched_f16(long m, long n, long k, float alpha, const void *const *d_Aarray, long lda, const void *const *d_Barray,
                            long ldb, float beta, void *const *d_Carray, int Ctype, long ldc, int batch, void *stream);
 
+/* ---- batched GGML_OP_MUL_MAT: F16 x F32, a whole attention product in one launch ------------------
+ * The two attention products of a llama.cpp graph (KQ: src0 = the permuted F16 K cache; KQV: src0 = the F16 V cache), on the
+ * tensors' own pointers and strides (csrc/mul_mat_batched.hip; reference: ggml_cuda_mul_mat_vec_p021 / _nc /
+ * ggml_cuda_mul_mat_batched_cublas, ggml-cuda.cu.patch:18424-18433).  For i3 < ne3, i2 < ne2, j < n, i < m:
+ *     C[i3][i2][j][i] = sum_l A[i3 / r3][i2 / r2][i][l] * B[i3][i2][j][l],   r2 = ne2 / a_ne2, r3 = ne3 / a_ne3
+ * (r2 query heads share one K / V head: grouped-query attention).
+ *   A: raw F16 rows of k elements — no resident image, no pack call, no workspace (the KV cache is rewritten every step);
+ *      a_ne2 x a_ne3 slices; element (i03, i02, i, l) at d_A + i03 * a_nb3 + i02 * a_nb2 + i * a_nb1 + l * 2
+ *   B: F32, ne2 x ne3 slices of n rows;  element (i3, i2, j, l) at d_B + i3 * b_nb3 + i2 * b_nb2 + j * b_nb1 + l * 4
+ *   C: F32 in ORDINARY device memory;    element (i3, i2, j, i) at d_C + i3 * c_nb3 + i2 * c_nb2 + j * c_nb1 + i * 4
+ * All strides are ggml's nb[] in BYTES and free beyond the checks below (a_nb2 < a_nb1, the permuted K cache, is legal).  Any
+ * element-aligned layout works; A and B with 16-byte aligned bases and strides (of every dimension of extent > 1) are read with
+ * 16-byte loads.  The bits of the result do not depend on which loads ran.  Nothing outside the m x n results of each slice is
+ * written; nothing behind a row's k values is read.
+ * Asynchronous on `stream`, graph-capturable: no allocation, no host read-back, no float atomics; deterministic.
+ * Arithmetic — lfamd_mul_mat's float route, selected by n alone:
+ *   n <= 8: the f16 weights widened to f32, the activations kept as f32, f32 fused multiply-add, in this module's own fixed order
+ *           (a function of k alone).  Where r2 * n <= 8 the K / V rows are read once for all r2 query heads of a group.
+ *   n > 8:  each activation rounded once to f16, to nearest-even (a value f16 cannot hold becomes inf or 0, as the reference's
+ *           to_fp16 conversion makes it), the products on the f16 matrix cores with f32 accumulation.
+ *   Both within 2e-6 (normwise, per slice) of the f64 product of the operands as that route sees them.  A slice's bits do not
+ *   depend on how many slices the call has or where the slice sits: the call on ne2 x ne3 slices gives the bits of ne2 x ne3
+ *   calls on one slice each.  Domain: finite inputs.
+ * Checks, before any launch and in this order:
+ *   1. a negative dimension (m, k, n, ne2, ne3, a_ne2, a_ne3)                               -> LFAMD_ERR_INVALID
+ *   2. m, n, ne2 or ne3 == 0 -> LFAMD_OK, nothing launched, no pointer looked at (k == 0 is not empty: it writes zeros)
+ *   3. Atype != LFAMD_TYPE_F16; more than 65535 slices (ne2 * ne3: they are a grid dimension), more than 65535 * 64 columns or
+ *      more than 2^32 rows                                                                  -> LFAMD_ERR_UNSUPPORTED
+ *   4. a NULL pointer; a_ne2 < 1 or a_ne3 < 1; ne2 % a_ne2 != 0 or ne3 % a_ne3 != 0; a_nb1 < 2 k, b_nb1 < 4 k or c_nb1 < 4 m; an A
+ *      base or stride that is not a multiple of 2; a B or C base or stride that is not a multiple of 4; flags != 0 (reserved)
+ *                                                                                           -> LFAMD_ERR_INVALID */
+int lfamd_mul_mat_batched(int Atype, const void *d_A, long m, long k, size_t a_nb1, size_t a_nb2, size_t a_nb3, long a_ne2, long a_ne3,
+                          const float *d_B, long n, size_t b_nb1, size_t b_nb2, size_t b_nb3, long ne2, long ne3,
+                          float *d_C, size_t c_nb1, size_t c_nb2, size_t c_nb3, unsigned flags, void *stream);
+
 /* ---- collectives (tensor parallel, one process per GPU) ---------------------------------------
  * The exchange step of the sharded path: attn_output / ffn_down are split by input columns and
  * the f32 partial sums of the residual stream are all-reduced; output.weight is split by vocabulary rows and the logits

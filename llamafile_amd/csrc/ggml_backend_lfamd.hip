@@ -131,6 +131,7 @@ struct backend_ctx {
     size_t plan_cap = 0;
     peer_scratch peer[LFAMD_MAX_DEVS];
     long sibling_calls = 0; // calls that served more than one node (LFAMD_BACKEND_STATS=1 prints it when the backend is freed)
+    long batched_calls = 0; // lfamd_mul_mat_batched calls: a node's slices in one launch (printed beside it)
 };
 
 bool grow(void *&p, size_t &cap, size_t need) {
@@ -580,6 +581,24 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
     const int64_t r2 = b->ne[2] / (a->ne[2] ? a->ne[2] : 1), r3 = b->ne[3] / (a->ne[3] ? a->ne[3] : 1);
     if (is_split(a) && a->ne[2] * a->ne[3] == 1)
         return run_mul_mat_split(ctx, dst);
+    // F16 src0 under several src1 slices (the attention products KQ and KQV: src0 = a view of the KV cache, r2 query heads per
+    // KV head): ONE call on the tensors' own pointers and nb[] — no packed copy, no scratch (the reference's condition for its
+    // batched routes, ggml-cuda.cu.patch:18430-18431).  LFAMD_BACKEND_NO_BATCHED=1 keeps the loop over the slices below.
+    static const bool no_batched = getenv("LFAMD_BACKEND_NO_BATCHED") && atoi(getenv("LFAMD_BACKEND_NO_BATCHED"));
+    if (!no_batched && a->type == LFAMD_TYPE_F16 && row_major(a) && !is_split(a) && b->ne[2] * b->ne[3] > 1 && a->ne[2] > 0 &&
+        a->ne[3] > 0 && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0) {
+        const int rc = lfamd_mul_mat_batched(LFAMD_TYPE_F16, a->data, m, k, a->nb[1], a->nb[2], a->nb[3], (long)a->ne[2], (long)a->ne[3],
+                                             (const float *)b->data, n, b->nb[1], b->nb[2], b->nb[3], (long)b->ne[2], (long)b->ne[3],
+                                             (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3], 0u, nullptr);
+        if (rc == LFAMD_OK) {
+            ctx->batched_calls++;
+            return GGML_STATUS_SUCCESS;
+        }
+        if (rc != LFAMD_ERR_UNSUPPORTED) { // (UNSUPPORTED: more slices than one launch indexes — the loop below serves them)
+            logf("%s: lfamd_mul_mat_batched: %s\n", "ggml_backend_lfamd", lfamd_last_error());
+            return GGML_STATUS_FAILED;
+        }
+    }
     const int rt = resident_type(a);
     const size_t wsb = lfamd_mul_mat_workspace(rt, m, k, n);
     if (!grow(ctx->ws, ctx->ws_cap, wsb))
@@ -798,7 +817,7 @@ GGML_CALL const char *be_get_name(ggml_backend_t) {
 GGML_CALL void be_free(ggml_backend_t backend) {
     backend_ctx *c = (backend_ctx *)backend->context;
     if (g_api && g_api->getenv && g_api->getenv("LFAMD_BACKEND_STATS"))
-        fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\n", c->sibling_calls);
+        fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\n", c->sibling_calls, c->batched_calls);
     {
         on_device d(c->device);
         (void)hipDeviceSynchronize();
