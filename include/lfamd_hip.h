@@ -473,6 +473,42 @@ int lfamd_mul_mat_batched(int Atype, const void *d_A, long m, long k, size_t a_n
                           const float *d_B, long n, size_t b_nb1, size_t b_nb2, size_t b_nb3, long ne2, long ne3,
                           float *d_C, size_t c_nb1, size_t c_nb2, size_t c_nb3, unsigned flags, void *stream);
 
+/* ---- batched GGML_OP_MUL_MAT on a QUANTISED K cache: 32-block rows x F32, the KQ product in one launch --------------
+ * What lfamd_mul_mat_batched is for an F16 cache, for the cache types of -ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl (src0 = a
+ * permuted view of a 32-block tensor that is rewritten every step; csrc/mul_mat_batched_q.hip).  The argument list and the index rule
+ * are lfamd_mul_mat_batched's: for i3 < ne3, i2 < ne2, j < n, i < m:
+ *     C[i3][i2][j][i] = sum_l A[i3 / r3][i2 / r2][i][l] * B[i3][i2][j][l],   r2 = ne2 / a_ne2, r3 = ne3 / a_ne3
+ *   A: raw GGUF rows of k / 32 blocks of Atype — no resident image, no pack call, no workspace; row (i03, i02, i) at
+ *      d_A + i03 * a_nb3 + i02 * a_nb2 + i * a_nb1
+ *   B: F32, element (i3, i2, j, l) at d_B + i3 * b_nb3 + i2 * b_nb2 + j * b_nb1 + l * 4
+ *   C: F32 in ORDINARY device memory, element (i3, i2, j, i) at d_C + i3 * c_nb3 + i2 * c_nb2 + j * c_nb1 + i * 4
+ * All strides are ggml's nb[] in BYTES and free beyond the checks below (a_nb2 < a_nb1, the permuted K cache, is legal).  Every
+ * layout that passes the checks works: a block is read as aligned dwords plus at most one 2-byte load, the activations with 16-byte
+ * loads where an address allows; the bits of the result do not depend on which loads ran.  Nothing behind a row's last block is
+ * read; nothing outside the m x n results of each slice is written.
+ * Asynchronous on `stream`, graph-capturable: no allocation, no host read-back, no float atomics; deterministic.
+ * Arithmetic — the reference's CPU path, with exact integer block dots for every n:
+ *   activation row (i3, i2, j) is quantised on the device per 32-block, bit for bit as lfamd_quantize_rows does it: Q8_0 for Q8_0,
+ *   Q4_0, Q5_0 and IQ4_NL weights, Q8_1 for Q4_1 and Q5_1 (d stored as f16, s = f16(sum * d)).  Block b contributes
+ *   (f32(d_w) * f32(d_a)) * isum_b, isum_b the exact int32 dot of the weight codes (Q8_0 qs; Q4_0 q - 8; Q5_0 q - 16; IQ4_NL the
+ *   codebook values; Q4_1 / Q5_1 the unsigned q) with the activation codes, and for Q4_1 / Q5_1 then f32(m_w) * f32(s_a).  The
+ *   contributions are added in f32 in ascending block order — a function of k and the type alone, not of m, n, the slice or the
+ *   layout.  Within 2e-6 (normwise, per slice) of the f64 value of the same sums.  A slice's bits do not depend on the call's other
+ *   slices.  Domain: finite inputs.
+ * Checks, before any device call and in this order:
+ *   1. a negative dimension (m, k, n, ne2, ne3, a_ne2, a_ne3)                               -> LFAMD_ERR_INVALID
+ *   2. m, n, ne2 or ne3 == 0 -> LFAMD_OK, nothing launched, no pointer, type, stride or flag looked at (k == 0 is not empty: it
+ *      writes zeros)
+ *   3. Atype is not Q8_0, Q4_0, Q4_1, Q5_0, Q5_1 or IQ4_NL (an id with LFAMD_TYPE_PAD256, the K-quants, F16, F32, BF16: refused);
+ *      k > 1024 (a work-group keeps its quantised activations in LDS); more than 65535 slices, more than 65535 * 64 columns or
+ *      more than 2^32 rows                                                                  -> LFAMD_ERR_UNSUPPORTED
+ *   4. a NULL pointer; a_ne2 < 1 or a_ne3 < 1; ne2 % a_ne2 != 0 or ne3 % a_ne3 != 0; k % 32 != 0; a_nb1 < lfamd_row_size(Atype, k),
+ *      b_nb1 < 4 k or c_nb1 < 4 m; an A base or stride that is not a multiple of 2 (34- and 18-byte blocks guarantee no more); a B
+ *      or C base or stride that is not a multiple of 4; flags != 0 (reserved)               -> LFAMD_ERR_INVALID */
+int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long k, size_t a_nb1, size_t a_nb2, size_t a_nb3, long a_ne2, long a_ne3,
+                            const float *d_B, long n, size_t b_nb1, size_t b_nb2, size_t b_nb3, long ne2, long ne3,
+                            float *d_C, size_t c_nb1, size_t c_nb2, size_t c_nb3, unsigned flags, void *stream);
+
 /* ---- collectives (tensor parallel, one process per GPU) ---------------------------------------
  * The exchange step of the sharded path: attn_output / ffn_down are split by input columns and
  * the f32 partial sums of the residual stream are all-reduced; output.weight is split by vocabulary rows and the logits

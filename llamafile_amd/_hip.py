@@ -80,6 +80,7 @@ _SIGS = {
                                             C.c_longlong, _i, _vp]),
     "lfamd_gemm_batched_f16": (_i, [_l, _l, _l, C.c_float, _vp, _l, _vp, _l, C.c_float, _vp, _i, _l, _i, _vp]),
     "lfamd_mul_mat_batched": (_i, [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]),
+    "lfamd_mul_mat_batched_q": (_i, [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]),
     "lfamd_comm_unique_id": (_i, [_vp]),
     "lfamd_comm_init": (_i, [C.POINTER(_vp), _i, _i, _vp]),
     "lfamd_comm_destroy": (_i, [_vp]),

@@ -370,16 +370,7 @@ struct q40_traits {
     }
 };
 
-// The 16-entry int8 codebook of IQ4_NL / IQ4_XS (kvalues_iq4nl), four indices (one per byte) -> four values: four constant
-// registers and three v_perm per four codes: the lower and the upper eight entries by the index's low three bits, then byte i of
-// one or the other by its bit 3.
-__device__ static inline uint32_t kvalues_lut4(uint32_t n) {
-    constexpr uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u; // kvalues_iq4nl, 4 entries each
-    const uint32_t sel = n & 0x07070707u;
-    const uint32_t lo = __builtin_amdgcn_perm(T1, T0, sel), hi = __builtin_amdgcn_perm(T3, T2, sel);
-    return __builtin_amdgcn_perm(hi, lo, ((n >> 1) & 0x04040404u) | 0x03020100u);
-}
-
+// (the codebook lookup kvalues_lut4: lfamd_device.h)
 // IQ4_NL (32-blocks {f16 d, 16 index bytes}, activations Q8_0): Q4_0's resident image byte for byte (P40), the nibbles being
 // codebook indices.  Per 32-block: (d * d8) * <kvalue[q], q8>; no offset, so the staged pair sums are not read.
 struct iq4nl_traits {

@@ -132,6 +132,7 @@ struct backend_ctx {
     peer_scratch peer[LFAMD_MAX_DEVS];
     long sibling_calls = 0; // calls that served more than one node (LFAMD_BACKEND_STATS=1 prints it when the backend is freed)
     long batched_calls = 0; // lfamd_mul_mat_batched calls: a node's slices in one launch (printed beside it)
+    long block_k_calls = 0; // lfamd_mul_mat_batched_q calls: the same for a 32-block src0 outside the weights buffers (a third line)
 };
 
 bool grow(void *&p, size_t &cap, size_t need) {
@@ -599,6 +600,26 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
             return GGML_STATUS_FAILED;
         }
     }
+    // A 32-block src0 that is NOT in a weights buffer, under several src1 slices (KQ on a quantised K cache, -ctk q8_0 ...: a permuted
+    // view of a tensor rewritten every step): ONE lfamd_mul_mat_batched_q call on the raw rows — the loop below would pack every KV
+    // head's slice into the scratch image and call once per query head.  Weights keep their resident image and its routes.
+    const bool block_k = a->type == LFAMD_TYPE_Q8_0 || a->type == LFAMD_TYPE_Q4_0 || a->type == LFAMD_TYPE_Q4_1 ||
+                         a->type == LFAMD_TYPE_Q5_0 || a->type == LFAMD_TYPE_Q5_1 || a->type == LFAMD_TYPE_IQ4_NL;
+    if (!no_batched && block_k && row_major(a) && !is_split(a) &&
+        !(a->buffer && g_api->ggml_backend_buffer_get_usage(a->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS) &&
+        b->ne[2] * b->ne[3] > 1 && a->ne[2] > 0 && a->ne[3] > 0 && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0) {
+        const int rc = lfamd_mul_mat_batched_q((int)a->type, a->data, m, k, a->nb[1], a->nb[2], a->nb[3], (long)a->ne[2], (long)a->ne[3],
+                                               (const float *)b->data, n, b->nb[1], b->nb[2], b->nb[3], (long)b->ne[2], (long)b->ne[3],
+                                               (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3], 0u, nullptr);
+        if (rc == LFAMD_OK) {
+            ctx->block_k_calls++;
+            return GGML_STATUS_SUCCESS;
+        }
+        if (rc != LFAMD_ERR_UNSUPPORTED) { // (UNSUPPORTED: k > 1024 or more slices than one launch indexes — the loop below serves them)
+            logf("%s: lfamd_mul_mat_batched_q: %s\n", "ggml_backend_lfamd", lfamd_last_error());
+            return GGML_STATUS_FAILED;
+        }
+    }
     const int rt = resident_type(a);
     const size_t wsb = lfamd_mul_mat_workspace(rt, m, k, n);
     if (!grow(ctx->ws, ctx->ws_cap, wsb))
@@ -817,7 +838,8 @@ GGML_CALL const char *be_get_name(ggml_backend_t) {
 GGML_CALL void be_free(ggml_backend_t backend) {
     backend_ctx *c = (backend_ctx *)backend->context;
     if (g_api && g_api->getenv && g_api->getenv("LFAMD_BACKEND_STATS"))
-        fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\n", c->sibling_calls, c->batched_calls);
+        fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\nggml_backend_lfamd: %ld block-K calls\n",
+                c->sibling_calls, c->batched_calls, c->block_k_calls);
     {
         on_device d(c->device);
         (void)hipDeviceSynchronize();

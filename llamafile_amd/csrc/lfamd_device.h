@@ -150,6 +150,16 @@ __device__ static inline int sdot4(uint32_t a, uint32_t b, int c) { // signed i8
     return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
 }
 
+// The 16-entry int8 codebook of IQ4_NL / IQ4_XS (kvalues_iq4nl), four indices (one per byte) -> four values: four constant
+// registers and three v_perm per four codes: the lower and the upper eight entries by the index's low three bits, then byte i of
+// one or the other by its bit 3.
+__device__ static inline uint32_t kvalues_lut4(uint32_t n) {
+    constexpr uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u; // kvalues_iq4nl, 4 entries each
+    const uint32_t sel = n & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(T1, T0, sel), hi = __builtin_amdgcn_perm(T3, T2, sel);
+    return __builtin_amdgcn_perm(hi, lo, ((n >> 1) & 0x04040404u) | 0x03020100u);
+}
+
 // get_scale_min_k4 (ggml-cuda.cu.patch:3311-3318)
 __device__ static inline void scale_min_k4(int j, const uint8_t *q, int &d, int &m) {
     if (j < 4) {
