@@ -19,6 +19,7 @@
 #include "lfamd_device.h"
 #include "../../include/ggml_backend_lfamd.h"
 #include "../../include/lfamd_hip.h"
+#include "lfamd_internal.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -369,6 +370,14 @@ bool is_split(const struct ggml_tensor *t) {
 bool is_split_buft(ggml_backend_buffer_type_t buft) {
     return buft && buft->iface.get_name == split_buft_get_name;
 }
+bool in_weights_buffer(const struct ggml_tensor *t) {
+    return t->buffer && g_api->ggml_backend_buffer_get_usage(t->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
+}
+// views of this backend's tensors carry no work (the scheduler keeps them with their source)
+bool is_view_op(const char *name) {
+    return !strcmp(name, "NONE") || !strcmp(name, "RESHAPE") || !strcmp(name, "VIEW") || !strcmp(name, "PERMUTE") ||
+           !strcmp(name, "TRANSPOSE");
+}
 
 // ------------------------------------------------------------------ mat-mul nodes
 bool row_major(const struct ggml_tensor *t) { // elements of a row contiguous, rows / slices at any stride
@@ -427,9 +436,8 @@ const packed *get_packed(backend_ctx *ctx, const struct ggml_tensor *a, int64_t 
     const uint8_t *base = weight_bytes(a);
     if (!base)
         return nullptr;
-    const bool keep = a->buffer && g_api->ggml_backend_buffer_get_usage(a->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
     return get_packed_rows(ctx->scratch, ctx->scratch_cap, resident_type(a), base + i02 * a->nb[2] + i03 * a->nb[3], (long)a->ne[1],
-                           (long)a->ne[0], a->nb[1], keep, tmp);
+                           (long)a->ne[0], a->nb[1], in_weights_buffer(a), tmp);
 }
 
 // The struct layouts this module reads (include/ggml_backend_lfamd.h, marked RECALLED: llama.cpp is not vendored in the reference
@@ -572,6 +580,29 @@ enum ggml_status run_mul_mat_split(backend_ctx *ctx, struct ggml_tensor *dst) {
     return GGML_STATUS_SUCCESS;
 }
 
+// A node of several src1 slices in ONE call of a batched entry point, on the tensors' own pointers and nb[] — no packed copy, no
+// scratch (the reference's condition for its batched routes, ggml-cuda.cu.patch:18430-18431).  GGML_STATUS_ABORTED: not taken (the
+// shape, LFAMD_BACKEND_NO_BATCHED=1, or the call answered LFAMD_ERR_UNSUPPORTED: k > 1024 on a block type, more slices than one launch
+// indexes) — run_mul_mat's loop over the slices serves the node.  Any other refusal fails the graph.
+enum ggml_status run_batched(struct ggml_tensor *dst, decltype(&lfamd_mul_mat_batched) call, const char *name, long &calls) {
+    const struct ggml_tensor *a = dst->src[0], *b = dst->src[1];
+    static const bool no_batched = getenv("LFAMD_BACKEND_NO_BATCHED") && atoi(getenv("LFAMD_BACKEND_NO_BATCHED"));
+    if (no_batched || !row_major(a) || is_split(a) || b->ne[2] * b->ne[3] <= 1 || a->ne[2] <= 0 || a->ne[3] <= 0 ||
+        b->ne[2] % a->ne[2] != 0 || b->ne[3] % a->ne[3] != 0)
+        return GGML_STATUS_ABORTED;
+    const int rc = call((int)a->type, a->data, (long)a->ne[1], (long)a->ne[0], a->nb[1], a->nb[2], a->nb[3], (long)a->ne[2], (long)a->ne[3],
+                        (const float *)b->data, (long)b->ne[1], b->nb[1], b->nb[2], b->nb[3], (long)b->ne[2], (long)b->ne[3],
+                        (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3], 0u, nullptr);
+    if (rc == LFAMD_OK) {
+        calls++;
+        return GGML_STATUS_SUCCESS;
+    }
+    if (rc == LFAMD_ERR_UNSUPPORTED)
+        return GGML_STATUS_ABORTED;
+    logf("ggml_backend_lfamd: %s: %s\n", name, lfamd_last_error());
+    return GGML_STATUS_FAILED;
+}
+
 enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
     const struct ggml_tensor *a = dst->src[0], *b = dst->src[1];
     const long m = (long)a->ne[1], k = (long)a->ne[0], n = (long)b->ne[1];
@@ -582,44 +613,17 @@ enum ggml_status run_mul_mat(backend_ctx *ctx, struct ggml_tensor *dst) {
     const int64_t r2 = b->ne[2] / (a->ne[2] ? a->ne[2] : 1), r3 = b->ne[3] / (a->ne[3] ? a->ne[3] : 1);
     if (is_split(a) && a->ne[2] * a->ne[3] == 1)
         return run_mul_mat_split(ctx, dst);
-    // F16 src0 under several src1 slices (the attention products KQ and KQV: src0 = a view of the KV cache, r2 query heads per
-    // KV head): ONE call on the tensors' own pointers and nb[] — no packed copy, no scratch (the reference's condition for its
-    // batched routes, ggml-cuda.cu.patch:18430-18431).  LFAMD_BACKEND_NO_BATCHED=1 keeps the loop over the slices below.
-    static const bool no_batched = getenv("LFAMD_BACKEND_NO_BATCHED") && atoi(getenv("LFAMD_BACKEND_NO_BATCHED"));
-    if (!no_batched && a->type == LFAMD_TYPE_F16 && row_major(a) && !is_split(a) && b->ne[2] * b->ne[3] > 1 && a->ne[2] > 0 &&
-        a->ne[3] > 0 && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0) {
-        const int rc = lfamd_mul_mat_batched(LFAMD_TYPE_F16, a->data, m, k, a->nb[1], a->nb[2], a->nb[3], (long)a->ne[2], (long)a->ne[3],
-                                             (const float *)b->data, n, b->nb[1], b->nb[2], b->nb[3], (long)b->ne[2], (long)b->ne[3],
-                                             (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3], 0u, nullptr);
-        if (rc == LFAMD_OK) {
-            ctx->batched_calls++;
-            return GGML_STATUS_SUCCESS;
-        }
-        if (rc != LFAMD_ERR_UNSUPPORTED) { // (UNSUPPORTED: more slices than one launch indexes — the loop below serves them)
-            logf("%s: lfamd_mul_mat_batched: %s\n", "ggml_backend_lfamd", lfamd_last_error());
-            return GGML_STATUS_FAILED;
-        }
-    }
-    // A 32-block src0 that is NOT in a weights buffer, under several src1 slices (KQ on a quantised K cache, -ctk q8_0 ...: a permuted
-    // view of a tensor rewritten every step): ONE lfamd_mul_mat_batched_q call on the raw rows — the loop below would pack every KV
-    // head's slice into the scratch image and call once per query head.  Weights keep their resident image and its routes.
-    const bool block_k = a->type == LFAMD_TYPE_Q8_0 || a->type == LFAMD_TYPE_Q4_0 || a->type == LFAMD_TYPE_Q4_1 ||
-                         a->type == LFAMD_TYPE_Q5_0 || a->type == LFAMD_TYPE_Q5_1 || a->type == LFAMD_TYPE_IQ4_NL;
-    if (!no_batched && block_k && row_major(a) && !is_split(a) &&
-        !(a->buffer && g_api->ggml_backend_buffer_get_usage(a->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS) &&
-        b->ne[2] * b->ne[3] > 1 && a->ne[2] > 0 && a->ne[3] > 0 && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0) {
-        const int rc = lfamd_mul_mat_batched_q((int)a->type, a->data, m, k, a->nb[1], a->nb[2], a->nb[3], (long)a->ne[2], (long)a->ne[3],
-                                               (const float *)b->data, n, b->nb[1], b->nb[2], b->nb[3], (long)b->ne[2], (long)b->ne[3],
-                                               (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3], 0u, nullptr);
-        if (rc == LFAMD_OK) {
-            ctx->block_k_calls++;
-            return GGML_STATUS_SUCCESS;
-        }
-        if (rc != LFAMD_ERR_UNSUPPORTED) { // (UNSUPPORTED: k > 1024 or more slices than one launch indexes — the loop below serves them)
-            logf("%s: lfamd_mul_mat_batched_q: %s\n", "ggml_backend_lfamd", lfamd_last_error());
-            return GGML_STATUS_FAILED;
-        }
-    }
+    // F16 src0 under several src1 slices (the attention products KQ and KQV: src0 = a view of the KV cache, r2 query heads per KV
+    // head), or a 32-block src0 that is NOT in a weights buffer (KQ on a quantised K cache, -ctk q8_0 ...: a permuted view of a tensor
+    // rewritten every step; weights keep their resident image and its routes): ONE call instead of the loop below, which would pack
+    // every KV head's slice into the scratch image and call once per query head
+    enum ggml_status st = GGML_STATUS_ABORTED;
+    if (a->type == LFAMD_TYPE_F16)
+        st = run_batched(dst, lfamd_mul_mat_batched, "lfamd_mul_mat_batched", ctx->batched_calls);
+    else if (lfamd_block_k_type(a->type) && !in_weights_buffer(a))
+        st = run_batched(dst, lfamd_mul_mat_batched_q, "lfamd_mul_mat_batched_q", ctx->block_k_calls);
+    if (st != GGML_STATUS_ABORTED)
+        return st;
     const int rt = resident_type(a);
     const size_t wsb = lfamd_mul_mat_workspace(rt, m, k, n);
     if (!grow(ctx->ws, ctx->ws_cap, wsb))
@@ -676,7 +680,7 @@ const packed *get_packed_stack(backend_ctx *ctx, const struct ggml_tensor *as, p
     const uint8_t *as_bytes = weight_bytes(as); // (an expert stack of a row-split buffer stays whole on the first device)
     if (!as_bytes)
         return nullptr;
-    const bool keep = as->buffer && g_api->ggml_backend_buffer_get_usage(as->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
+    const bool keep = in_weights_buffer(as);
     auto it = g_packed.find(as_bytes);
     if (keep && it != g_packed.end() && it->second.type == rt && it->second.rows == rows * experts && it->second.cols == cols)
         return &it->second;
@@ -778,11 +782,8 @@ int sibling_run(const struct ggml_cgraph *g, int i) {
         if (id) {
             // (stacks outside a weights buffer are packed into the context's ONE scratch image per call: two of them cannot be live
             // together, so such nodes run one by one)
-            const auto kept = [](const struct ggml_tensor *w) {
-                return w->buffer && g_api->ggml_backend_buffer_get_usage(w->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
-            };
             if (t->src[2] != first->src[2] || a->type != a0->type || a->ne[0] != a0->ne[0] || a->ne[1] != a0->ne[1] || a->ne[2] != a0->ne[2] ||
-                !mul_mat_id_supported(t) || !kept(a0) || !kept(a))
+                !mul_mat_id_supported(t) || !in_weights_buffer(a0) || !in_weights_buffer(a))
                 break;
         } else if (a->ne[2] * a->ne[3] != 1 || is_split(a) || !mul_mat_supported(t) || t->nb[1] != (size_t)a->ne[1] * 4 ||
                    lfamd_vec_dot_type(a->type) != lfamd_vec_dot_type(a0->type)) {
@@ -809,8 +810,7 @@ enum ggml_status run_mul_mat_siblings(backend_ctx *ctx, struct ggml_tensor *cons
         const struct ggml_tensor *a = dsts[j]->src[0];
         packed tmp;
         // (a matrix outside a weights buffer is packed into the one scratch area: it cannot share a call with another)
-        const bool keep = a->buffer && g_api->ggml_backend_buffer_get_usage(a->buffer) == GGML_BACKEND_BUFFER_USAGE_WEIGHTS;
-        if (!keep)
+        if (!in_weights_buffer(a))
             return GGML_STATUS_ABORTED;
         const packed *w = get_packed(ctx, a, 0, 0, &tmp);
         if (!w)
@@ -891,9 +891,7 @@ GGML_CALL enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_
             continue;
         else {
             const char *name = g_api->ggml_op_name(node->op);
-            // views of this backend's tensors carry no work (the scheduler keeps them with their source)
-            if (!strcmp(name, "NONE") || !strcmp(name, "RESHAPE") || !strcmp(name, "VIEW") || !strcmp(name, "PERMUTE") ||
-                !strcmp(name, "TRANSPOSE"))
+            if (is_view_op(name))
                 continue;
             logf("%s: op %s is not supported by this backend\n", "ggml_backend_lfamd", name);
             return GGML_STATUS_FAILED;
@@ -910,9 +908,7 @@ GGML_CALL bool be_supports_op(ggml_backend_t, const struct ggml_tensor *op) {
         return mul_mat_supported(op);
     if (op->op == g_op_mul_mat_id)
         return mul_mat_id_supported(op);
-    const char *name = g_api->ggml_op_name(op->op);
-    return !strcmp(name, "NONE") || !strcmp(name, "RESHAPE") || !strcmp(name, "VIEW") || !strcmp(name, "PERMUTE") ||
-           !strcmp(name, "TRANSPOSE");
+    return is_view_op(g_api->ggml_op_name(op->op));
 }
 GGML_CALL bool be_supports_buft(ggml_backend_t backend, ggml_backend_buffer_type_t buft) {
     return buft == &g_bufts[((backend_ctx *)backend->context)->device] || is_split_buft(buft);

@@ -77,6 +77,11 @@ static inline lfamd_image lfamd_image_of(int id, long cols) {
 static inline bool lfamd_type_known(int id) { // (at every row length: cols only picks between a type's layouts)
     return lfamd_image_of(id, 0).ly != LY_NONE;
 }
+// the K cache types lfamd_mul_mat_batched_q reads as raw GGUF rows (the 32-block types; an id with LFAMD_TYPE_PAD256 is not one)
+static inline bool lfamd_block_k_type(int id) {
+    return id == LFAMD_TYPE_Q8_0 || id == LFAMD_TYPE_Q4_0 || id == LFAMD_TYPE_Q4_1 || id == LFAMD_TYPE_Q5_0 || id == LFAMD_TYPE_Q5_1 ||
+           id == LFAMD_TYPE_IQ4_NL;
+}
 
 // A planned decode GEMV launch.  kind = the entry point that asks, variant = the kernel form it gets.
 enum { LFAMD_GEMV_MULTI, LFAMD_GEMV_IDS, LFAMD_GEMV_IDS_PAIR, LFAMD_GEMV_DUAL, LFAMD_GEMV_MULTI_RELAXED }; // (_RELAXED: Q8_0 under LFAMD_FLAG_Q80_RELAXED)

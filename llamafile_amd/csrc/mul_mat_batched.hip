@@ -20,18 +20,12 @@
 //           (nearest-even) in registers and used for both row tiles.  Slices on blockIdx.z in i12-major order: the r2 heads of a
 //           group are neighbours and find their K / V slice in L2.
 // Neither body holds anything across slices: a slice's bits are those of the call on that slice alone.
-#include "lfamd_device.h"
-#include "../../include/lfamd_hip.h"
-#include "lfamd_internal.h"
+// The argument checks, the slice geometry and the index rule are mul_mat_batched_common.h's, shared with mul_mat_batched_q.hip.
+#include "mul_mat_batched_common.h"
 
 namespace {
 
-struct mmb_args {
-    const uint8_t *A, *B;
-    uint8_t *C;
-    long m, k, n;
-    size_t a_nb1, a_nb2, a_nb3, b_nb1, b_nb2, b_nb3, c_nb1, c_nb2, c_nb3;
-    long a_ne2, ne2, r2, r3;
+struct mmb_args : lfamd_batched_geom {
     int hg, hchunks; // GEMV: query heads per item, items per group
 };
 
@@ -85,16 +79,12 @@ __global__ __launch_bounds__(256) void mmb_gemv_kernel(const mmb_args a) {
     constexpr bool KSPLIT = LPR == 64; // the four waves share the work-group's RU rows and take every fourth step of k
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, sl = lane % LPR;
-    long y = blockIdx.y; // (i3, KV head, chunk of the group's heads)
-    const int hc = (int)(y % a.hchunks);
-    y /= a.hchunks;
-    const long i02 = y % a.a_ne2, i3 = y / a.a_ne2, i03 = i3 / a.r3;
-    const long h0 = (long)hc * a.hg;
-    const int nh = (int)(a.r2 - h0 < a.hg ? a.r2 - h0 : a.hg), n = (int)a.n, nc = nh * n;
+    const lfamd_batched_index it(a.a_ne2, a.r2, a.r3, a.hg, a.hchunks);
+    const int n = (int)a.n, nc = it.nh * n;
     const long row0 = KSPLIT ? (long)blockIdx.x * RU : ((long)blockIdx.x * 4 + wave) * (RPP * RU);
     if (row0 >= a.m) // (KSPLIT: uniform over the work-group, so every wave reaches the barrier below)
         return;
-    const uint8_t *Ab = a.A + i03 * a.a_nb3 + i02 * a.a_nb2;
+    const uint8_t *Ab = it.a_slice(a.A, a.a_nb3, a.a_nb2);
     const uint8_t *wrow[RU];
 #pragma unroll
     for (int u = 0; u < RU; u++) { // rows past the edge are clamped for the loads and masked at the store
@@ -103,11 +93,8 @@ __global__ __launch_bounds__(256) void mmb_gemv_kernel(const mmb_args a) {
     }
     const uint8_t *xrow[NC];
 #pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int cc = c < nc ? c : 0;
-        const long i2 = i02 * a.r2 + h0 + cc / n, j = cc % n;
-        xrow[c] = a.B + i3 * a.b_nb3 + i2 * a.b_nb2 + j * a.b_nb1;
-    }
+    for (int c = 0; c < NC; c++)
+        xrow[c] = it.column(a.B, a.b_nb3, a.b_nb2, a.b_nb1, a.r2, c < nc ? c : 0, n);
     float acc[RU][NC];
 #pragma unroll
     for (int u = 0; u < RU; u++)
@@ -146,16 +133,14 @@ __global__ __launch_bounds__(256) void mmb_gemv_kernel(const mmb_args a) {
         __syncthreads();
         const int u = threadIdx.x / NC, c = threadIdx.x % NC;
         if (u < RU && c < nc && row0 + u < a.m) {
-            const long i2 = i02 * a.r2 + h0 + c / n, j = c % n;
-            float *Cc = (float *)(a.C + i3 * a.c_nb3 + i2 * a.c_nb2 + j * a.c_nb1);
+            float *Cc = (float *)it.column(a.C, a.c_nb3, a.c_nb2, a.c_nb1, a.r2, c, n);
             Cc[row0 + u] = (part[0][u][c] + part[1][u][c]) + (part[2][u][c] + part[3][u][c]);
         }
     } else {
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (c < nc) {
-                const long i2 = i02 * a.r2 + h0 + c / n, j = c % n;
-                float *Cc = (float *)(a.C + i3 * a.c_nb3 + i2 * a.c_nb2 + j * a.c_nb1);
+                float *Cc = (float *)it.column(a.C, a.c_nb3, a.c_nb2, a.c_nb1, a.r2, c, n);
 #pragma unroll
                 for (int u = 0; u < RU; u++) {
                     const float s = mmb_lane_sum<LPR>(acc[u][c]);
@@ -196,7 +181,7 @@ template <bool ALIGNED>
 __global__ __launch_bounds__(256) void mmb_mfma_kernel(const mmb_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
-    const long z = blockIdx.z, i2 = z % a.ne2, i3 = z / a.ne2, i02 = i2 / a.r2, i03 = i3 / a.r3;
+    const lfamd_batched_index sl(a.ne2, a.r2, a.r3);
     const long m0 = (long)blockIdx.x * 128 + (wave & 1) * 64, n0 = (long)blockIdx.y * 64 + (wave >> 1) * 32;
     if (m0 >= a.m || n0 >= a.n)
         return;
@@ -204,9 +189,9 @@ __global__ __launch_bounds__(256) void mmb_mfma_kernel(const mmb_args a) {
     // rows past the edge are clamped for the loads and masked at the store
     const long ar0 = m0 + i < a.m ? m0 + i : a.m - 1, ar1 = m0 + 32 + i < a.m ? m0 + 32 + i : a.m - 1;
     const long br = n0 + i < a.n ? n0 + i : a.n - 1;
-    const uint8_t *Ab = a.A + i03 * a.a_nb3 + i02 * a.a_nb2;
+    const uint8_t *Ab = sl.a_slice(a.A, a.a_nb3, a.a_nb2);
     const uint8_t *A0 = Ab + ar0 * a.a_nb1, *A1 = Ab + ar1 * a.a_nb1;
-    const uint8_t *Br = a.B + i3 * a.b_nb3 + i2 * a.b_nb2 + br * a.b_nb1;
+    const uint8_t *Br = sl.slice(a.B, a.b_nb3, a.b_nb2) + br * a.b_nb1;
     float16_t_ acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
     for (long k0 = 0; k0 < a.k; k0 += 16) {
         const long kk = k0 + 8 * h;
@@ -222,7 +207,7 @@ __global__ __launch_bounds__(256) void mmb_mfma_kernel(const mmb_args a) {
     const long col = n0 + i;
     if (col >= a.n)
         return;
-    float *Cc = (float *)(a.C + i3 * a.c_nb3 + i2 * a.c_nb2 + col * a.c_nb1);
+    float *Cc = (float *)(sl.slice(a.C, a.c_nb3, a.c_nb2) + col * a.c_nb1);
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const long row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -234,20 +219,8 @@ __global__ __launch_bounds__(256) void mmb_mfma_kernel(const mmb_args a) {
 }
 
 template <int LPR, bool ALIGNED>
-void gemv_go(const mmb_args &a, int nc_max, dim3 grid, hipStream_t s) {
-    if (nc_max <= 1)
-        mmb_gemv_kernel<LPR, 1, ALIGNED><<<grid, 256, 0, s>>>(a);
-    else if (nc_max <= 2)
-        mmb_gemv_kernel<LPR, 2, ALIGNED><<<grid, 256, 0, s>>>(a);
-    else if (nc_max <= 4)
-        mmb_gemv_kernel<LPR, 4, ALIGNED><<<grid, 256, 0, s>>>(a);
-    else
-        mmb_gemv_kernel<LPR, 8, ALIGNED><<<grid, 256, 0, s>>>(a);
-}
-
-int refuse(int code, const char *msg) {
-    lfamd_set_error(msg);
-    return code;
+void gemv_go(const mmb_args &a, dim3 grid, hipStream_t s) {
+    lfamd_batched_nc(a.hg * (int)a.n, [&](auto nc) { mmb_gemv_kernel<LPR, decltype(nc)::value, ALIGNED><<<grid, 256, 0, s>>>(a); });
 }
 
 } // namespace
@@ -255,54 +228,30 @@ int refuse(int code, const char *msg) {
 extern "C" int lfamd_mul_mat_batched(int Atype, const void *d_A, long m, long k, size_t a_nb1, size_t a_nb2, size_t a_nb3, long a_ne2,
                                      long a_ne3, const float *d_B, long n, size_t b_nb1, size_t b_nb2, size_t b_nb3, long ne2, long ne3,
                                      float *d_C, size_t c_nb1, size_t c_nb2, size_t c_nb3, unsigned flags, void *stream) {
-    if (m < 0 || k < 0 || n < 0 || ne2 < 0 || ne3 < 0 || a_ne2 < 0 || a_ne3 < 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: negative dimension");
-    if (m == 0 || n == 0 || ne2 == 0 || ne3 == 0)
-        return LFAMD_OK;
-    if (Atype != LFAMD_TYPE_F16)
-        return refuse(LFAMD_ERR_UNSUPPORTED, "lfamd_mul_mat_batched: F16 weights only");
-    // slices are a grid dimension (65535 at most); so are the 64-column tiles of the batch body
-    if (ne2 > 65535 || ne3 > 65535 || ne2 * ne3 > 65535 || (n + 63) / 64 > 65535 || m > (1L << 32))
-        return refuse(LFAMD_ERR_UNSUPPORTED, "lfamd_mul_mat_batched: more than 65535 slices (or 64-column tiles, or 2^32 rows)");
-    if (!d_A || !d_B || !d_C)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: null pointer");
-    if (a_ne2 < 1 || a_ne3 < 1 || ne2 % a_ne2 != 0 || ne3 % a_ne3 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: ne2 / ne3 are not multiples of a_ne2 / a_ne3");
-    if (a_nb1 < (size_t)k * 2 || b_nb1 < (size_t)k * 4 || c_nb1 < (size_t)m * 4)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: a row stride is smaller than the row");
-    if (((uintptr_t)d_A | a_nb1 | a_nb2 | a_nb3) % 2 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: A base / strides are not multiples of 2");
-    if (((uintptr_t)d_B | b_nb1 | b_nb2 | b_nb3 | (uintptr_t)d_C | c_nb1 | c_nb2 | c_nb3) % 4 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: B / C bases / strides are not multiples of 4");
-    if (flags != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched: flags are reserved (0)");
-
-    mmb_args a{};
-    a.A = (const uint8_t *)d_A, a.B = (const uint8_t *)d_B, a.C = (uint8_t *)d_C;
-    a.m = m, a.k = k, a.n = n;
-    a.a_nb1 = a_nb1, a.a_nb2 = a_nb2, a.a_nb3 = a_nb3, a.b_nb1 = b_nb1, a.b_nb2 = b_nb2, a.b_nb3 = b_nb3;
-    a.c_nb1 = c_nb1, a.c_nb2 = c_nb2, a.c_nb3 = c_nb3;
-    a.a_ne2 = a_ne2, a.ne2 = ne2, a.r2 = ne2 / a_ne2, a.r3 = ne3 / a_ne3;
+    mmb_args a{{(const uint8_t *)d_A, (const uint8_t *)d_B, (uint8_t *)d_C, m, k, n, a_nb1, a_nb2, a_nb3, b_nb1, b_nb2, b_nb3,
+                c_nb1, c_nb2, c_nb3, a_ne2, ne2}};
+    const lfamd_batched_desc d{Atype == LFAMD_TYPE_F16, 0, 1, (size_t)k * 2, "F16 weights only", nullptr, nullptr};
+    int rc;
+    if (!lfamd_batched_check("lfamd_mul_mat_batched", d, a, a_ne3, ne3, flags, &rc))
+        return rc;
+    lfamd_batched_groups(a, a_ne3, ne3, a.hg, a.hchunks);
     // 16-byte loads need every row of every slice of A and B on a 16-byte boundary (a stride of an extent of 1 is never applied)
     const size_t strides = (m > 1 ? a_nb1 : 0) | (a_ne2 > 1 ? a_nb2 : 0) | (a_ne3 > 1 ? a_nb3 : 0) | (n > 1 ? b_nb1 : 0) |
                            (ne2 > 1 ? b_nb2 : 0) | (ne3 > 1 ? b_nb3 : 0);
     const bool aligned = (((uintptr_t)d_A | (uintptr_t)d_B | strides) & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
     if (n <= 8) {
-        a.hg = (int)(8 / n < a.r2 ? 8 / n : a.r2);
-        a.hchunks = (int)((a.r2 + a.hg - 1) / a.hg);
-        const int nc_max = a.hg * (int)n;
         const bool lanes16 = k <= 128;
         const long rows_wg = lanes16 ? 4 * 16 : 4; // 16 lanes: four waves of 16 rows; 64 lanes: four rows, k split over the waves
         const dim3 grid((unsigned)((m + rows_wg - 1) / rows_wg), (unsigned)(ne3 * a_ne2 * a.hchunks), 1);
         if (lanes16 && aligned)
-            gemv_go<16, true>(a, nc_max, grid, s);
+            gemv_go<16, true>(a, grid, s);
         else if (lanes16)
-            gemv_go<16, false>(a, nc_max, grid, s);
+            gemv_go<16, false>(a, grid, s);
         else if (aligned)
-            gemv_go<64, true>(a, nc_max, grid, s);
+            gemv_go<64, true>(a, grid, s);
         else
-            gemv_go<64, false>(a, nc_max, grid, s);
+            gemv_go<64, false>(a, grid, s);
     } else {
         const dim3 grid((unsigned)((m + 127) / 128), (unsigned)((n + 63) / 64), (unsigned)(ne2 * ne3));
         if (aligned)
@@ -312,6 +261,6 @@ extern "C" int lfamd_mul_mat_batched(int Atype, const void *d_A, long m, long k,
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return refuse(LFAMD_ERR_HIP, hipGetErrorString(e));
-    return LFAMD_OK;
+        lfamd_set_error(hipGetErrorString(e));
+    return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
 }

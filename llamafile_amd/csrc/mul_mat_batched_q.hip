@@ -2,8 +2,8 @@
 // iq4_nl) in ONE launch.
 //
 // GGML_OP_MUL_MAT where src0 is a permuted view of a 32-block K cache that is rewritten every step and src1 is F32 with ne[2] =
-// query heads.  The argument list and the index rule are lfamd_mul_mat_batched's (mul_mat_batched.hip); A is raw GGUF rows of
-// k / 32 blocks, read where ggml keeps them: no resident image, no pack call, no workspace.
+// query heads.  The argument list, its checks and the index rule are lfamd_mul_mat_batched's (mul_mat_batched_common.h); A is raw GGUF
+// rows of k / 32 blocks, read where ggml keeps them: no resident image, no pack call, no workspace.
 //
 // Arithmetic (the reference's CPU path: quantize_row_q8_0 / q8_1 of src1, then the type's vec_dot):
 //   - an activation row is quantised per 32-block in LDS, bit for bit as lfamd_quantize_rows does: Q8_0 (Q8_0, Q4_0, Q5_0, IQ4_NL
@@ -28,18 +28,11 @@
 // the checks, and nothing outside the block is touched.  f32 activations take 16-byte loads where the address allows, element
 // loads otherwise; the values are the same either way.
 // Neither body holds anything across slices: a slice's bits are those of the call on that slice alone.
-#include "lfamd_device.h"
-#include "../../include/lfamd_hip.h"
-#include "lfamd_internal.h"
+#include "mul_mat_batched_common.h"
 
 namespace {
 
-struct mmq_args {
-    const uint8_t *A, *B;
-    uint8_t *C;
-    long m, k, n;
-    size_t a_nb1, a_nb2, a_nb3, b_nb1, b_nb2, b_nb3, c_nb1, c_nb2, c_nb3;
-    long a_ne2, ne2, r2, r3;
+struct mmq_args : lfamd_batched_geom {
     int kb;          // 32-blocks per row
     int hg, hchunks; // GEMV: query heads per item, items per group
 };
@@ -191,22 +184,16 @@ __global__ __launch_bounds__(256) void mmq_gemv_kernel(const mmq_args a) {
     __shared__ float ssc[W::S1 ? NC * 32 : 1];
     const int sub = threadIdx.x & 3, quad = threadIdx.x >> 2;
     const int kb = a.kb, k = (int)a.k;
-    long y = blockIdx.y; // (i3, KV head, chunk of the group's heads)
-    const int hc = (int)(y % a.hchunks);
-    y /= a.hchunks;
-    const long i02 = y % a.a_ne2, i3 = y / a.a_ne2, i03 = i3 / a.r3;
-    const long h0 = (long)hc * a.hg;
-    const int nh = (int)(a.r2 - h0 < a.hg ? a.r2 - h0 : a.hg), n = (int)a.n, nc = nh * n;
+    const lfamd_batched_index it(a.a_ne2, a.r2, a.r3, a.hg, a.hchunks);
+    const int n = (int)a.n, nc = it.nh * n;
     // ---- quantise: nc * kb blocks, one quad each (the trip count is uniform: every lane reaches the DPP exchanges)
     for (int g0 = 0; g0 < nc * kb; g0 += 64) {
         const int g = g0 + quad;
         const bool live = g < nc * kb;
         const int c = live ? g / kb : 0, b = live ? g % kb : 0;
         float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (live) {
-            const long i2 = i02 * a.r2 + h0 + c / n, j = c % n;
-            ld_x8(a.B + i3 * a.b_nb3 + i2 * a.b_nb2 + j * a.b_nb1, (long)b * 32 + 8 * sub, v);
-        }
+        if (live)
+            ld_x8(it.column(a.B, a.b_nb3, a.b_nb2, a.b_nb1, a.r2, c, n), (long)b * 32 + 8 * sub, v);
         uint32_t y0, y1;
         float d, s;
         quantise_quad<W::S1>(v, y0, y1, d, s);
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(256) void mmq_gemv_kernel(const mmq_args a) {
     __syncthreads();
     // ---- a quad per row: 64 rows per work-group.  Rows past the edge are clamped for the loads and masked at the store.
     const long row = (long)blockIdx.x * 64 + quad;
-    const uint8_t *wrow = a.A + i03 * a.a_nb3 + i02 * a.a_nb2 + (row < a.m ? row : a.m - 1) * a.a_nb1;
+    const uint8_t *wrow = it.a_slice(a.A, a.a_nb3, a.a_nb2) + (row < a.m ? row : a.m - 1) * a.a_nb1;
     float acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++)
@@ -263,8 +250,8 @@ __global__ __launch_bounds__(256) void mmq_gemv_kernel(const mmq_args a) {
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (c < nc) {
-                const long i2 = i02 * a.r2 + h0 + c / n, j = c % n;
-                ((float *)(a.C + i3 * a.c_nb3 + i2 * a.c_nb2 + j * a.c_nb1))[row] = acc[c];
+                float *Cc = (float *)it.column(a.C, a.c_nb3, a.c_nb2, a.c_nb1, a.r2, c, n);
+                Cc[row] = acc[c];
             }
         }
     }
@@ -301,10 +288,10 @@ __global__ __launch_bounds__(256) void mmq_mfma_kernel(const mmq_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
     const int sub = threadIdx.x & 3, quad = threadIdx.x >> 2;
-    const long z = blockIdx.z, i2 = z % a.ne2, i3 = z / a.ne2, i02 = i2 / a.r2, i03 = i3 / a.r3;
+    const lfamd_batched_index sl(a.ne2, a.r2, a.r3);
     const long n0 = (long)blockIdx.y * 64;
     // ---- quantise: 64 * kb blocks, one quad each, kb passes; the columns past n are staged as rows of zeros and never loaded
-    const uint8_t *Bs = a.B + i3 * a.b_nb3 + i2 * a.b_nb2;
+    const uint8_t *Bs = sl.slice(a.B, a.b_nb3, a.b_nb2);
     for (int g = quad; g < 64 * kb; g += 64) {
         const int c = g / kb, b = g % kb;
         float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -328,7 +315,7 @@ __global__ __launch_bounds__(256) void mmq_mfma_kernel(const mmq_args a) {
     const bool two = m0 + 32 < a.m; // (uniform: the wave's second row tile exists)
     // rows past the edge are clamped for the loads and masked at the store
     const long ar0 = m0 + i < a.m ? m0 + i : a.m - 1, ar1 = m0 + 32 + i < a.m ? m0 + 32 + i : a.m - 1;
-    const uint8_t *Ab = a.A + i03 * a.a_nb3 + i02 * a.a_nb2;
+    const uint8_t *Ab = sl.a_slice(a.A, a.a_nb3, a.a_nb2);
     const uint8_t *A0 = Ab + ar0 * a.a_nb1, *A1 = Ab + ar1 * a.a_nb1;
     const v16i_t zero16i = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     float acc0[16], acc1[16];
@@ -370,7 +357,7 @@ __global__ __launch_bounds__(256) void mmq_mfma_kernel(const mmq_args a) {
         }
     }
     // lane (i, h) holds rows m0 + i and m0 + 32 + i; register r holds column n0 + cw + (r & 3) + 8 (r >> 2) + 4 h
-    uint8_t *Cs = a.C + i3 * a.c_nb3 + i2 * a.c_nb2;
+    uint8_t *Cs = sl.slice(a.C, a.c_nb3, a.c_nb2);
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const long col = n0 + cw + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -384,25 +371,12 @@ __global__ __launch_bounds__(256) void mmq_mfma_kernel(const mmq_args a) {
     }
 }
 
-int refuse(int code, const char *msg) {
-    lfamd_set_error(msg);
-    return code;
-}
-
 template <int T>
 hipError_t launch(const mmq_args &a, long ne3, hipStream_t s) {
     using W = wt<T>;
     if (a.n <= 8) {
-        const int nc_max = a.hg * (int)a.n;
         const dim3 grid((unsigned)((a.m + 63) / 64), (unsigned)(ne3 * a.a_ne2 * a.hchunks), 1);
-        if (nc_max <= 1)
-            mmq_gemv_kernel<T, 1><<<grid, 256, 0, s>>>(a);
-        else if (nc_max <= 2)
-            mmq_gemv_kernel<T, 2><<<grid, 256, 0, s>>>(a);
-        else if (nc_max <= 4)
-            mmq_gemv_kernel<T, 4><<<grid, 256, 0, s>>>(a);
-        else
-            mmq_gemv_kernel<T, 8><<<grid, 256, 0, s>>>(a);
+        lfamd_batched_nc(a.hg * (int)a.n, [&](auto nc) { mmq_gemv_kernel<T, decltype(nc)::value><<<grid, 256, 0, s>>>(a); });
     } else {
         const size_t smem = (size_t)a.kb * (2048 + 256 * (W::S1 ? 2 : 1));
         if (smem > 64 * 1024) {
@@ -416,73 +390,35 @@ hipError_t launch(const mmq_args &a, long ne3, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch(int Atype, const mmq_args &a, long ne3, hipStream_t s) {
+    static const struct {
+        int type;
+        hipError_t (*go)(const mmq_args &, long, hipStream_t);
+    } tab[] = {{LFAMD_TYPE_Q8_0, launch<LFAMD_TYPE_Q8_0>}, {LFAMD_TYPE_Q4_0, launch<LFAMD_TYPE_Q4_0>}, {LFAMD_TYPE_Q4_1, launch<LFAMD_TYPE_Q4_1>},
+               {LFAMD_TYPE_Q5_0, launch<LFAMD_TYPE_Q5_0>}, {LFAMD_TYPE_Q5_1, launch<LFAMD_TYPE_Q5_1>}, {LFAMD_TYPE_IQ4_NL, launch<LFAMD_TYPE_IQ4_NL>}};
+    for (const auto &e : tab)
+        if (e.type == Atype)
+            return e.go(a, ne3, s);
+    return hipErrorInvalidValue; // (not reached: the check admits lfamd_block_k_type alone)
+}
+
 } // namespace
 
 extern "C" int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long k, size_t a_nb1, size_t a_nb2, size_t a_nb3, long a_ne2,
                                        long a_ne3, const float *d_B, long n, size_t b_nb1, size_t b_nb2, size_t b_nb3, long ne2, long ne3,
                                        float *d_C, size_t c_nb1, size_t c_nb2, size_t c_nb3, unsigned flags, void *stream) {
-    if (m < 0 || k < 0 || n < 0 || ne2 < 0 || ne3 < 0 || a_ne2 < 0 || a_ne3 < 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: negative dimension");
-    if (m == 0 || n == 0 || ne2 == 0 || ne3 == 0)
-        return LFAMD_OK;
-    if (Atype != LFAMD_TYPE_Q8_0 && Atype != LFAMD_TYPE_Q4_0 && Atype != LFAMD_TYPE_Q4_1 && Atype != LFAMD_TYPE_Q5_0 &&
-        Atype != LFAMD_TYPE_Q5_1 && Atype != LFAMD_TYPE_IQ4_NL)
-        return refuse(LFAMD_ERR_UNSUPPORTED, "lfamd_mul_mat_batched_q: Q8_0, Q4_0, Q4_1, Q5_0, Q5_1 or IQ4_NL rows only");
-    if (k > 1024) // a work-group keeps its quantised activations in LDS
-        return refuse(LFAMD_ERR_UNSUPPORTED, "lfamd_mul_mat_batched_q: k > 1024");
-    // slices are a grid dimension (65535 at most); so are the 64-column tiles of the batch body
-    if (ne2 > 65535 || ne3 > 65535 || ne2 * ne3 > 65535 || (n + 63) / 64 > 65535 || m > (1L << 32))
-        return refuse(LFAMD_ERR_UNSUPPORTED, "lfamd_mul_mat_batched_q: more than 65535 slices (or 64-column tiles, or 2^32 rows)");
-    if (!d_A || !d_B || !d_C)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: null pointer");
-    if (a_ne2 < 1 || a_ne3 < 1 || ne2 % a_ne2 != 0 || ne3 % a_ne3 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: ne2 / ne3 are not multiples of a_ne2 / a_ne3");
-    if (k % 32 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: k is not a multiple of 32");
-    if (a_nb1 < lfamd_row_size(Atype, k) || b_nb1 < (size_t)k * 4 || c_nb1 < (size_t)m * 4)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: a row stride is smaller than the row");
-    if (((uintptr_t)d_A | a_nb1 | a_nb2 | a_nb3) % 2 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: A base / strides are not multiples of 2");
-    if (((uintptr_t)d_B | b_nb1 | b_nb2 | b_nb3 | (uintptr_t)d_C | c_nb1 | c_nb2 | c_nb3) % 4 != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: B / C bases / strides are not multiples of 4");
-    if (flags != 0)
-        return refuse(LFAMD_ERR_INVALID, "lfamd_mul_mat_batched_q: flags are reserved (0)");
-
-    mmq_args a{};
-    a.A = (const uint8_t *)d_A, a.B = (const uint8_t *)d_B, a.C = (uint8_t *)d_C;
-    a.m = m, a.k = k, a.n = n;
-    a.a_nb1 = a_nb1, a.a_nb2 = a_nb2, a.a_nb3 = a_nb3, a.b_nb1 = b_nb1, a.b_nb2 = b_nb2, a.b_nb3 = b_nb3;
-    a.c_nb1 = c_nb1, a.c_nb2 = c_nb2, a.c_nb3 = c_nb3;
-    a.a_ne2 = a_ne2, a.ne2 = ne2, a.r2 = ne2 / a_ne2, a.r3 = ne3 / a_ne3;
+    mmq_args a{{(const uint8_t *)d_A, (const uint8_t *)d_B, (uint8_t *)d_C, m, k, n, a_nb1, a_nb2, a_nb3, b_nb1, b_nb2, b_nb3,
+                c_nb1, c_nb2, c_nb3, a_ne2, ne2}};
+    const bool six = lfamd_block_k_type(Atype); // (k <= 1024: a work-group keeps its quantised activations in LDS)
+    const lfamd_batched_desc d{six, 1024, 32, six ? lfamd_row_size(Atype, k) : 0, "Q8_0, Q4_0, Q4_1, Q5_0, Q5_1 or IQ4_NL rows only",
+                               "k > 1024", "k is not a multiple of 32"};
+    int rc;
+    if (!lfamd_batched_check("lfamd_mul_mat_batched_q", d, a, a_ne3, ne3, flags, &rc))
+        return rc;
     a.kb = (int)(k / 32);
-    a.hg = 1, a.hchunks = 1;
-    if (n <= 8) {
-        a.hg = (int)(8 / n < a.r2 ? 8 / n : a.r2);
-        a.hchunks = (int)((a.r2 + a.hg - 1) / a.hg);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    switch (Atype) {
-    case LFAMD_TYPE_Q8_0:
-        e = launch<LFAMD_TYPE_Q8_0>(a, ne3, s);
-        break;
-    case LFAMD_TYPE_Q4_0:
-        e = launch<LFAMD_TYPE_Q4_0>(a, ne3, s);
-        break;
-    case LFAMD_TYPE_Q4_1:
-        e = launch<LFAMD_TYPE_Q4_1>(a, ne3, s);
-        break;
-    case LFAMD_TYPE_Q5_0:
-        e = launch<LFAMD_TYPE_Q5_0>(a, ne3, s);
-        break;
-    case LFAMD_TYPE_Q5_1:
-        e = launch<LFAMD_TYPE_Q5_1>(a, ne3, s);
-        break;
-    default:
-        e = launch<LFAMD_TYPE_IQ4_NL>(a, ne3, s);
-        break;
-    }
+    lfamd_batched_groups(a, a_ne3, ne3, a.hg, a.hchunks);
+    const hipError_t e = launch(Atype, a, ne3, (hipStream_t)stream);
     if (e != hipSuccess)
-        return refuse(LFAMD_ERR_HIP, hipGetErrorString(e));
-    return LFAMD_OK;
+        lfamd_set_error(hipGetErrorString(e));
+    return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
 }

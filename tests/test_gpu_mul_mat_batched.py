@@ -12,49 +12,17 @@ chains are shorter (k / 16 or k / 64 per lane, then a tree; the matrix cores add
 import numpy as np
 import pytest
 
-from llamafile_amd import _hip, ggml_types as T
+from llamafile_amd import ggml_types as T
+from batched_case import Dev, b_image, run_strided_call, span, strided
 from helpers import rel_err
 
 TOL = 2e-6
-NAN16, NAN32 = 0x7e00, 0x7fc00000
-
-
-class Dev:
-    """Device buffers through torch; a buffer's base sits `misalign` bytes past a 16-byte boundary."""
-
-    def __init__(self):
-        import torch
-        self.torch = torch
-        self.lib = _hip.lib()
-
-    def put(self, host_u8, misalign):
-        t = self.torch.empty(host_u8.size + 48, dtype=self.torch.uint8, device="cuda")
-        off = (-t.data_ptr()) % 16 + misalign
-        t[off:off + host_u8.size] = self.torch.from_numpy(host_u8).cuda()
-        return t, off, host_u8.size
-
-    def ptr(self, h):
-        return h[0].data_ptr() + h[1]
-
-    def get(self, h):
-        self.torch.cuda.synchronize()
-        return h[0][h[1]:h[1] + h[2]].cpu().numpy()
-
-    def batched(self, *args):
-        return self.lib.lfamd_mul_mat_batched(*args)
+NAN16 = 0x7e00
 
 
 @pytest.fixture(scope="module")
 def dev(gpu):
     return Dev()
-
-
-def strided(buf, dtype, shape, strides):
-    return np.lib.stride_tricks.as_strided(buf.view(dtype), shape=shape, strides=strides, writeable=True)
-
-
-def span(shape, strides, elem):
-    return sum((e - 1) * s for e, s in zip(shape, strides)) + elem
 
 
 def make_layout(kind, m, k, n, kvh, group, ne3, a_ne3, unaligned):
@@ -89,36 +57,10 @@ def run_case(dev, Av, Bv, kind="kq", unaligned=False):
     ne3, heads, n, _ = Bv.shape
     group = heads // kvh
     a_nb, b_nb, c_nb = make_layout(kind, m, k, n, kvh, group, ne3, a_ne3, unaligned)
-    Ash, Bsh, Csh = (a_ne3, kvh, m, k), (ne3, heads, n, k), (ne3, heads, n, m)
-    A_img = np.full(span(Ash, a_nb + (2,), 2) // 2, NAN16, np.uint16)
-    strided(A_img, np.uint16, Ash, a_nb + (2,))[...] = Av.view(np.uint16)
-    B_img = np.full(span(Bsh, b_nb + (4,), 4) // 4, NAN32, np.uint32)
-    strided(B_img, np.uint32, Bsh, b_nb + (4,))[...] = Bv.view(np.uint32)
-    c_words = span(Csh, c_nb + (4,), 4) // 4 + 16
-    C_img = (np.arange(c_words, dtype=np.uint64) * 2654435761 % 2 ** 32).astype(np.uint32) | np.uint32(0x7f800001)  # (NaNs)
-    hA = dev.put(A_img.view(np.uint8), 2 if unaligned else 0)
-    hB = dev.put(B_img.view(np.uint8), 4 if unaligned else 0)
-    hC = dev.put(C_img.view(np.uint8), 4 if unaligned else 0)
-    rc = dev.batched(T.F16, dev.ptr(hA), m, k, a_nb[2], a_nb[1], a_nb[0], kvh, a_ne3, dev.ptr(hB), n, b_nb[2], b_nb[1], b_nb[0], heads, ne3,
-                     dev.ptr(hC), c_nb[2], c_nb[1], c_nb[0], 0, None)
-    assert rc == 0, _hip.lib().lfamd_last_error()
-    out = dev.get(hC).view(np.uint32).copy()
-    got = strided(out, np.uint32, Csh, c_nb + (4,)).copy()
-    # every byte outside the results is unchanged
-    strided(out, np.uint32, Csh, c_nb + (4,))[...] = strided(C_img, np.uint32, Csh, c_nb + (4,))
-    assert np.array_equal(out, C_img), "bytes outside the results were written"
-    # the same slices by single-slice calls: the same bits
-    one = dev.put(np.zeros(n * m * 4, np.uint8), 0)
-    for i3 in range(ne3):
-        for i2 in range(heads):
-            pa = dev.ptr(hA) + (i3 // (ne3 // a_ne3)) * a_nb[0] + (i2 // group) * a_nb[1]
-            pb = dev.ptr(hB) + i3 * b_nb[0] + i2 * b_nb[1]
-            rc = dev.batched(T.F16, pa, m, k, a_nb[2], a_nb[1], a_nb[0], 1, 1, pb, n, b_nb[2], b_nb[1], b_nb[0], 1, 1, dev.ptr(one), m * 4,
-                             n * m * 4, n * m * 4, 0, None)
-            assert rc == 0, _hip.lib().lfamd_last_error()
-            single = dev.get(one).view(np.uint32).reshape(n, m)
-            assert np.array_equal(single, got[i3, i2]), ("slice bits depend on the call's other slices", i3, i2)
-    return got.view(np.float32)
+    A_img = np.full(span(Av.shape, a_nb + (2,), 2) // 2, NAN16, np.uint16)
+    strided(A_img, np.uint16, Av.shape, a_nb + (2,))[...] = Av.view(np.uint16)
+    return run_strided_call(dev, dev.lib.lfamd_mul_mat_batched, T.F16, A_img, b_image(Bv, b_nb), (m, k, n, kvh, a_ne3, heads, ne3),
+                            a_nb, b_nb, c_nb, unaligned)
 
 
 def references(Av, Bv):

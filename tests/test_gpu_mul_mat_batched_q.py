@@ -21,49 +21,19 @@ import numpy as np
 import pytest
 
 from llamafile_amd import _hip, ggml_types as T, synth
+from batched_case import Dev, b_image, run_strided_call, span, strided
 from helpers import rel_err
 import block32_ref
 import iq4nl_ref
 
 TOL = 2e-6
 APART = 1e-3
-NAN32 = 0x7fc00000
 GAP = 0x7e
-
-
-class Dev:
-    """Device buffers through torch; a buffer's base sits `misalign` bytes past a 16-byte boundary."""
-
-    def __init__(self):
-        import torch
-        self.torch = torch
-        self.lib = _hip.lib()
-
-    def put(self, host_u8, misalign):
-        t = self.torch.empty(host_u8.size + 48, dtype=self.torch.uint8, device="cuda")
-        off = (-t.data_ptr()) % 16 + misalign
-        t[off:off + host_u8.size] = self.torch.from_numpy(host_u8).cuda()
-        return t, off, host_u8.size
-
-    def ptr(self, h):
-        return h[0].data_ptr() + h[1]
-
-    def get(self, h):
-        self.torch.cuda.synchronize()
-        return h[0][h[1]:h[1] + h[2]].cpu().numpy()
 
 
 @pytest.fixture(scope="module")
 def dev(gpu):
     return Dev()
-
-
-def strided(buf, dtype, shape, strides):
-    return np.lib.stride_tricks.as_strided(buf.view(dtype), shape=shape, strides=strides, writeable=True)
-
-
-def span(shape, strides, elem):
-    return sum((e - 1) * s for e, s in zip(shape, strides)) + elem
 
 
 def make_layout(row, m, k, n, kvh, heads, unaligned):
@@ -93,39 +63,12 @@ def run_case(dev, t, Av, Bv, unaligned=False, k_call=None):
     a_ne3, kvh, m, row = Av.shape
     ne3, heads, n, k = Bv.shape
     kc = k if k_call is None else k_call
-    group = heads // kvh
     a_nb, b_nb, c_nb = make_layout(row, m, k, n, kvh, heads, unaligned)
-    Ash, Bsh, Csh = (a_ne3, kvh, m, row), (ne3, heads, n, k), (ne3, heads, n, m)
-    A_img = np.full(span(Ash, a_nb + (1,), 1) + 6, GAP, np.uint8)
-    strided(A_img, np.uint8, Ash, a_nb + (1,))[...] = Av
-    B_img = np.full(span(Bsh, b_nb + (4,), 4) // 4 + 4, NAN32, np.uint32)
-    strided(B_img, np.uint32, Bsh, b_nb + (4,))[...] = Bv.view(np.uint32)
-    c_words = span(Csh, c_nb + (4,), 4) // 4 + 16
-    C_img = (np.arange(c_words, dtype=np.uint64) * 2654435761 % 2 ** 32).astype(np.uint32) | np.uint32(0x7f800001)  # (NaNs)
-    hA = dev.put(A_img, 2 if unaligned else 0)
-    hB = dev.put(B_img.view(np.uint8), 4 if unaligned else 0)
-    hC = dev.put(C_img.view(np.uint8), 4 if unaligned else 0)
-    fn = dev.lib.lfamd_mul_mat_batched_q
-    rc = fn(t, dev.ptr(hA), m, kc, a_nb[2], a_nb[1], a_nb[0], kvh, a_ne3, dev.ptr(hB), n, b_nb[2], b_nb[1], b_nb[0], heads, ne3,
-            dev.ptr(hC), c_nb[2], c_nb[1], c_nb[0], 0, None)
-    assert rc == 0, _hip.lib().lfamd_last_error()
-    out = dev.get(hC).view(np.uint32).copy()
-    got = strided(out, np.uint32, Csh, c_nb + (4,)).copy()
-    # (d) every byte outside the results is unchanged
-    strided(out, np.uint32, Csh, c_nb + (4,))[...] = strided(C_img, np.uint32, Csh, c_nb + (4,))
-    assert np.array_equal(out, C_img), "bytes outside the results were written"
-    # (c) the same slices by single-slice calls: the same bits
-    one = dev.put(np.full(n * m * 4, 0xff, np.uint8), 0)
-    for i3 in range(ne3):
-        for i2 in range(heads):
-            pa = dev.ptr(hA) + (i3 // (ne3 // a_ne3)) * a_nb[0] + (i2 // group) * a_nb[1]
-            pb = dev.ptr(hB) + i3 * b_nb[0] + i2 * b_nb[1]
-            rc = fn(t, pa, m, kc, a_nb[2], a_nb[1], a_nb[0], 1, 1, pb, n, b_nb[2], b_nb[1], b_nb[0], 1, 1, dev.ptr(one), m * 4,
-                    n * m * 4, n * m * 4, 0, None)
-            assert rc == 0, _hip.lib().lfamd_last_error()
-            single = dev.get(one).view(np.uint32).reshape(n, m)
-            assert np.array_equal(single, got[i3, i2]), ("slice bits depend on the call's other slices", i3, i2)
-    return got.view(np.float32)
+    A_img = np.full(span(Av.shape, a_nb + (1,), 1) + 6, GAP, np.uint8)
+    strided(A_img, np.uint8, Av.shape, a_nb + (1,))[...] = Av
+    # (c) the same slices by single-slice calls: the same bits; (d) every byte outside the results is unchanged
+    return run_strided_call(dev, dev.lib.lfamd_mul_mat_batched_q, t, A_img, b_image(Bv, b_nb, 4), (m, kc, n, kvh, a_ne3, heads, ne3),
+                            a_nb, b_nb, c_nb, unaligned)
 
 
 def dequantize(t, raw, k):

@@ -13,29 +13,16 @@ KQ: src0 = the K cache permuted, memory [n_kv][kv_head][row of 128 weights] (m =
 Device events around back-to-back calls on the null stream, warm-up first, every window at least --window seconds, the routes
 alternated inside one process for --rounds rounds; median and min .. max of the rounds.  The operands stay where they are between
 calls, so the cache is read from the on-die caches: these are times of the calls, not of HBM."""
-import argparse
 import json
-import math
-import os
-import sys
 
-import numpy as np
+from attn_common import HEAD_DIM, HEADS, KV_HEADS, parser, shapes_of, time_routes, write_doc
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from llamafile_amd import _hip, ggml_types as T, synth  # noqa: E402
-
-HEAD_DIM, HEADS, KV_HEADS = 128, 32, 8
-SHAPES = [(512, 1), (4096, 1), (512, 512), (4096, 512)]
+from llamafile_amd import _hip, ggml_types as T, synth  # noqa: E402  (attn_common put the repository root on the path)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "attn_batched_q.json"))
-    ap.add_argument("--window", type=float, default=0.5)
-    ap.add_argument("--rounds", type=int, default=3)
+    ap = parser("attn_batched_q.json")
     ap.add_argument("--types", default="Q8_0,Q4_0")
-    ap.add_argument("--shapes", default="", help="n_kv:n,... (default: the four Llama-3-8B shapes)")
     args = ap.parse_args()
     import torch
     from llamafile_amd import sgemm
@@ -43,7 +30,7 @@ def main():
     assert torch.cuda.is_available(), "attn_q_time.py measures on the GPU: there is no CPU fallback"
     sgemm.init(0)
     lib = _hip.lib()
-    shapes = [tuple(int(v) for v in s.split(":")) for s in args.shapes.split(",")] if args.shapes else SHAPES
+    shapes = shapes_of(args)
     types = [{v: key for key, v in T.NAMES.items()}[name] for name in args.types.split(",")]
     group = HEADS // KV_HEADS
     k = HEAD_DIM
@@ -95,30 +82,12 @@ def main():
             if agree > 2e-3:
                 print("WARNING: routes a and b disagree", T.NAMES[t], n_kv, n, agree, flush=True)
 
-            def window(f, reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    f()
-                e1.record()
-                e1.synchronize()
-                return e0.elapsed_time(e1) * 1e3 / reps  # us per product
-
-            reps = {}
-            for v, f in runs.items():  # warm-up, and how many calls fill a window
-                window(f, 3)
-                reps[v] = max(3, math.ceil(args.window * 1e6 / window(f, 10)))
-            times = {v: [] for v in runs}
-            for _ in range(args.rounds):
-                for v, f in runs.items():
-                    times[v].append(window(f, reps[v]))
+            timed = time_routes(torch, runs, args)
             nbytes = KV_HEADS * m * row_bytes + HEADS * n * k * 4 + HEADS * n * m * 4
             row = {"type": T.NAMES[t], "n_kv": n_kv, "n": n, "m": m, "k": k, "algorithmic_bytes": nbytes, "flop": 2 * HEADS * n * m * k,
                    "max_rel_diff_a_vs_b": agree}
-            for v in runs:
-                med = float(np.median(times[v]))
-                row[v] = {"us": round(med, 2), "us_min": round(min(times[v]), 2), "us_max": round(max(times[v]), 2),
-                          "calls_per_window": reps[v]}
+            for v, (_, entry) in timed.items():
+                row[v] = entry
             row["b_over_a"] = round(row["b"]["us"] / row["a"]["us"], 2)
             # the routing condition: a beats b by more than the two routes' run-to-run spread
             row["a_beats_b_beyond_spread"] = bool(row["a"]["us_max"] < row["b"]["us_min"])
@@ -126,16 +95,9 @@ def main():
             results.append(row)
             del A, A16, B, Cs, scratch, ws
             torch.cuda.empty_cache()
-    doc = {"device": torch.cuda.get_device_name(0), "heads": HEADS, "kv_heads": KV_HEADS, "head_dim": HEAD_DIM,
-           "window_s": args.window, "rounds": args.rounds,
-           "routes": {"a": "lfamd_mul_mat_batched_q, one call",
-                      "b": "lfamd_pack_weights(lfamd_resident_type) per KV head + lfamd_mul_mat per head (the per-slice loop)",
-                      "c": "lfamd_mul_mat_batched on an F16 K cache of the same shape (context, not a bar)"},
-           "results": results}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    write_doc(torch, args, {"a": "lfamd_mul_mat_batched_q, one call",
+                            "b": "lfamd_pack_weights(lfamd_resident_type) per KV head + lfamd_mul_mat per head (the per-slice loop)",
+                            "c": "lfamd_mul_mat_batched on an F16 K cache of the same shape (context, not a bar)"}, results)
 
 
 if __name__ == "__main__":
