@@ -509,6 +509,65 @@ int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long k, size_t a
                             const float *d_B, long n, size_t b_nb1, size_t b_nb2, size_t b_nb3, long ne2, long ne3,
                             float *d_C, size_t c_nb1, size_t c_nb2, size_t c_nb3, unsigned flags, void *stream);
 
+/* ---- GGML_OP_FLASH_ATTN_EXT on an F16 K / V cache: scores, mask, softmax and PV in one fused launch --------------
+ * What a llama.cpp graph built with -fa holds per layer in place of KQ, scale + mask, soft_max and KQV (csrc/flash_attn.hip;
+ * reference: ggml_cuda_flash_attn_ext, ggml-cuda.cu.patch:8280-8400, its argument list at :8361-8375).  For i3 < ne3, h < n_head,
+ * j < n_q, with hk = h / (n_head / n_head_kv) (grouped-query attention):
+ *     s_t = scale * sum_l Q[i3][h][j][l] * K[i3][hk][t][l] + mask[j][t],   p_t = exp(s_t - max_t s_t),   t < n_kv
+ *     dst[i3][j][h][l] = (sum_t p_t * V[i3][hk][t][l]) / sum_t p_t,        l < D
+ *   Q:    F32, element (i3, h, j, l) at d_Q + i3 * q_nb3 + h * q_nb2 + j * q_nb1 + 4 l
+ *   K, V: F16 rows of D elements, n_kv rows per KV head; row (i3, hk, t) at + i3 * nb3 + hk * nb2 + t * nb1.  V is NOT transposed
+ *         (the -fa cache layout)
+ *   mask: F16 or NULL (no mask); element (j, t) at d_mask + j * mask_nb1 + 2 t; one mask for all heads and i3
+ *   dst:  F32 in ORDINARY device memory; element (i3, j, h, l) at d_dst + i3 * dst_nb3 + j * dst_nb2 + h * dst_nb1 + 4 l (ggml's
+ *         order: heads inside tokens)
+ * All strides are ggml's nb[] in BYTES.  Memory contract: nothing behind row n_kv - 1 of K or V and nothing between rows is read;
+ * no mask element outside [n_q][n_kv] is read (rows n_q .. of a padded mask never); nothing outside the D * n_head * n_q * ne3
+ * results is written.
+ * Domain: finite Q, K, V and scale; mask entries finite or -inf; every query row has at least one key whose mask is not -inf.
+ * Asynchronous on `stream`, graph-capturable: no allocation, no host read-back, no float atomics; deterministic.
+ * Arithmetic — two routes, selected by n_q alone.  Scores are kept in log2 units: s2_t = S_t * (scale * log2 e) + mask * log2 e (one
+ * f32 fused multiply-add on the unscaled f32 dot S_t), p_t = exp2(s2_t - m) with the running maximum m; a maximum that is still
+ * -inf (every key so far masked) counts as 0 inside the exponentials.
+ *   n_q <= 8: Q stays f32, K / V are widened to f32; scores, p and the accumulators are f32 (fmaf).  The keys are cut into chunks of
+ *             256, a compile-time constant chosen by timing (128 is faster up to about 4096 keys and loses a
+ *             third at 16384, 512 the reverse).  A work-group takes one chunk of one KV head; where n_q * (n_head / n_head_kv)
+ *             <= 8 it serves all query heads of the group from one read of the K / V rows, else one query head.  Inside a chunk
+ *             wave w of eight takes keys 128 i + 16 w .. (D = 128; D = 64: 256 i + 32 w ..), a lane group one key of every 4 (8),
+ *             four keys per online-softmax step; lane groups merge pairwise by lane exchange, the eight waves in wave order.
+ *             n_kv <= 256: the work-group writes dst.  Longer: each chunk's (o[D], m, l) goes to the workspace and a second launch
+ *             merges the chunks in an order that is a function of the chunk count alone (the maximum first; then o over the
+ *             chunks c = g, g + G, ... of each of G = 512 / D groups in ascending order, the groups in ascending g; l by halving).
+ *   n_q > 8:  Q is rounded once to f16, unscaled, to nearest-even.  Both products run on the f16 matrix cores with f32
+ *             accumulation, in KV tiles of 64 keys; p is rounded once to f16 for the PV product, the row sum is taken from the f32
+ *             p.  A 64-key tile whose mask is -inf for every query row of a work-group's 128 is not loaded, and a 32-key half that
+ *             is -inf for all 32 rows of a wave is not computed (the causal upper triangle): neither moves a bit.
+ *   The bits of a result row are a function of that row's own operands, D and n_kv alone: not of n_head, ne3, where the slice sits,
+ *   the other rows, or the device's CU count.  A call on many heads gives the bits of calls on one head each.
+ * lfamd_flash_attn_workspace is the only source of the workspace size: 0 where no split runs (n_q > 8 or n_kv <= 256, or a
+ * dimension < 1), else ne3 * n_head * n_q * ceil(n_kv / 256) * (D + 2) * 4 bytes.  It makes no device call.
+ * Checks, before any device call and in this order:
+ *   1. a negative dimension (D, n_q, n_kv, n_head, n_head_kv, ne3)                          -> LFAMD_ERR_INVALID
+ *   2. n_q, n_head or ne3 == 0 -> LFAMD_OK, nothing launched, no pointer looked at
+ *   3. Ktype or Vtype is not LFAMD_TYPE_F16 (quantised K / V: refused; the parameters exist so that the block types can follow);
+ *      D is not 64 or 128; max_bias != 0 (ALiBi: refused); more than 65535 slices (n_head * ne3: a grid dimension) or 128-row query
+ *      blocks; n_kv == 0                                                                    -> LFAMD_ERR_UNSUPPORTED
+ *   4. a NULL pointer other than the mask or a zero-size workspace; n_head_kv < 1 or n_head % n_head_kv != 0; a Q / K / V / dst base
+ *      or stride that is not a multiple of 16; a mask base or mask_nb1 that is not a multiple of 2, or mask_nb1 < 2 n_kv; k_nb1 or
+ *      v_nb1 < 2 D, q_nb1 < 4 D or dst_nb1 < 4 D; flags != 0 (reserved)                       -> LFAMD_ERR_INVALID
+ *   5. workspace_bytes < lfamd_flash_attn_workspace(...)                                    -> LFAMD_ERR_WORKSPACE
+ * Not served, by design (a host declines the node): quantised K / V, ALiBi, GGML_PREC_F32 (the n_q > 8 route rounds Q and p to
+ * f16), head sizes other than 64 / 128, logit soft-capping (the call has no parameter for it). */
+size_t lfamd_flash_attn_workspace(long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3);
+int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
+                     int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,
+                     int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
+                     const void *d_mask, size_t mask_nb1,
+                     long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3,
+                     float scale, float max_bias,
+                     float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
+                     void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream);
+
 /* ---- collectives (tensor parallel, one process per GPU) ---------------------------------------
  * The exchange step of the sharded path: attn_output / ffn_down are split by input columns and
  * the f32 partial sums of the residual stream are all-reduced; output.weight is split by vocabulary rows and the logits

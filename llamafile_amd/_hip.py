@@ -81,6 +81,9 @@ _SIGS = {
     "lfamd_gemm_batched_f16": (_i, [_l, _l, _l, C.c_float, _vp, _l, _vp, _l, C.c_float, _vp, _i, _l, _i, _vp]),
     "lfamd_mul_mat_batched": (_i, [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]),
     "lfamd_mul_mat_batched_q": (_i, [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]),
+    "lfamd_flash_attn_workspace": (_sz, [_l, _l, _l, _l, _l, _l]),
+    "lfamd_flash_attn": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
+                              C.c_float, C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u, _vp]),
     "lfamd_comm_unique_id": (_i, [_vp]),
     "lfamd_comm_init": (_i, [C.POINTER(_vp), _i, _i, _vp]),
     "lfamd_comm_destroy": (_i, [_vp]),

@@ -1,5 +1,6 @@
 // ggml_backend_lfamd.hip — the 12 GGML_CALL (ms_abi) symbols llamafile/cuda.c:726-737 imports from ggml-rocm.so, served by
-// this module: a ggml backend whose supports_op says yes to GGML_OP_MUL_MAT / GGML_OP_MUL_MAT_ID only.
+// this module: a ggml backend whose supports_op says yes to GGML_OP_MUL_MAT / GGML_OP_MUL_MAT_ID and, on an F16
+// K / V cache, GGML_OP_FLASH_ATTN_EXT (the graph of -fa; reference: ggml_cuda_flash_attn_ext, ggml-cuda.cu.patch:8280-8400).
 //
 // Reference counterparts: ggml_cuda_link (ggml-cuda.cu.patch:468), the buffer interface (:16890-17027, set_tensor :16971),
 // the buffer type (:17040-17100, row padding :17072-17081), supports_op (:19221-19262), graph_compute (:18945),
@@ -33,6 +34,7 @@ namespace {
 
 const ggml_backend_api *g_api = nullptr;
 int g_op_mul_mat = -1, g_op_mul_mat_id = -1;
+int g_op_flash_attn = -1; // -1: the host's table does not name FLASH_ATTN_EXT; the op is never offered
 bool g_linked = false;
 
 #define LFAMD_MAX_DEVS 16 // GGML_CUDA_MAX_DEVICES (ggml-cuda.h.patch: the length of llama.cpp's tensor_split array)
@@ -134,6 +136,7 @@ struct backend_ctx {
     long sibling_calls = 0; // calls that served more than one node (LFAMD_BACKEND_STATS=1 prints it when the backend is freed)
     long batched_calls = 0; // lfamd_mul_mat_batched calls: a node's slices in one launch (printed beside it)
     long block_k_calls = 0; // lfamd_mul_mat_batched_q calls: the same for a 32-block src0 outside the weights buffers (a third line)
+    long flash_attn_calls = 0; // lfamd_flash_attn calls: one per FLASH_ATTN_EXT node (a fourth line)
 };
 
 bool grow(void *&p, size_t &cap, size_t need) {
@@ -476,7 +479,8 @@ bool layout_agrees(const struct ggml_tensor *t) {
 }
 bool op_layout_agrees(const struct ggml_tensor *op) {
     static bool warned = false;
-    const bool ok = layout_agrees(op) && layout_agrees(op->src[0]) && layout_agrees(op->src[1]) && layout_agrees(op->src[2]);
+    const bool ok = layout_agrees(op) && layout_agrees(op->src[0]) && layout_agrees(op->src[1]) && layout_agrees(op->src[2]) &&
+                    layout_agrees(op->src[3]);
     if (!ok && !warned) {
         warned = true;
         logf("%s: the host's ggml structs do not match this module's layouts (%s): declining every operator\n", "ggml_backend_lfamd",
@@ -831,6 +835,62 @@ enum ggml_status run_mul_mat_siblings(backend_ctx *ctx, struct ggml_tensor *cons
     return GGML_STATUS_SUCCESS;
 }
 
+// ------------------------------------------------------------------ GGML_OP_FLASH_ATTN_EXT
+// src[0] = Q f32 [D, n_q, n_head, ne3], src[1] = K f16 [D, n_kv, n_head_kv, ne3], src[2] = V f16 (not transposed), src[3] = mask f16
+// [n_kv, >= n_q] or NULL, dst f32 [D, n_head, n_q, ne3]; op_params: scale (f32) at [0], max_bias (f32) at [1], precision at [2]
+// (ggml-cuda.cu.patch:8352-8353, :9987).  The call takes bases and strides that are multiples of 16 (include/lfamd_hip.h), a view's
+// offset included: supports_op may be asked before the tensor has its address (rows_aligned's test, on every stride).
+bool fa_aligned(const struct ggml_tensor *t) {
+    return ((uintptr_t)t->data | t->view_offs | t->nb[1] | t->nb[2] | t->nb[3]) % 16 == 0;
+}
+
+bool flash_attn_supported(const struct ggml_tensor *op) {
+    const char *off = g_api->getenv ? g_api->getenv("LFAMD_BACKEND_NO_FLASH_ATTN") : nullptr;
+    if (off && atoi(off))
+        return false;
+    const struct ggml_tensor *q = op->src[0], *k = op->src[1], *v = op->src[2], *mask = op->src[3];
+    if (!q || !k || !v || q->type != LFAMD_TYPE_F32 || k->type != LFAMD_TYPE_F16 || v->type != LFAMD_TYPE_F16 || op->type != LFAMD_TYPE_F32)
+        return false;
+    if (q->nb[0] != 4 || k->nb[0] != 2 || v->nb[0] != 2 || !g_api->ggml_is_contiguous(op))
+        return false;
+    const int64_t D = q->ne[0], n_q = q->ne[1], n_head = q->ne[2], ne3 = q->ne[3], n_kv = k->ne[1], n_head_kv = k->ne[2];
+    if ((D != 64 && D != 128) || k->ne[0] != D || v->ne[0] != D || v->ne[1] != n_kv || v->ne[2] != n_head_kv || k->ne[3] != ne3 || v->ne[3] != ne3)
+        return false;
+    if (n_kv < 1 || n_head_kv < 1 || n_head % n_head_kv != 0 || n_head * ne3 > 65535 || (n_q + 127) / 128 > 65535)
+        return false;
+    if (op->ne[0] != D || op->ne[1] != n_head || op->ne[2] != n_q || op->ne[3] != ne3)
+        return false;
+    if (mask && (mask->type != LFAMD_TYPE_F16 || mask->nb[0] != 2 || mask->ne[0] < n_kv || mask->ne[1] < n_q || mask->ne[2] != 1 ||
+                 mask->ne[3] != 1 || mask->nb[1] < (size_t)n_kv * 2 || ((uintptr_t)mask->data | mask->view_offs | mask->nb[1]) % 2 != 0))
+        return false;
+    float max_bias;
+    memcpy(&max_bias, &op->op_params[1], sizeof(float));
+    if (max_bias != 0.0f || op->op_params[2] != 0 /* GGML_PREC_DEFAULT */)
+        return false;
+    return fa_aligned(q) && fa_aligned(k) && fa_aligned(v) && fa_aligned(op);
+}
+
+// ONE lfamd_flash_attn on the tensors' own pointers and nb[]
+enum ggml_status run_flash_attn(backend_ctx *ctx, struct ggml_tensor *dst) {
+    const struct ggml_tensor *q = dst->src[0], *k = dst->src[1], *v = dst->src[2], *mask = dst->src[3];
+    const long D = (long)q->ne[0], n_q = (long)q->ne[1], n_head = (long)q->ne[2], ne3 = (long)q->ne[3], n_kv = (long)k->ne[1], n_head_kv = (long)k->ne[2];
+    float scale, max_bias;
+    memcpy(&scale, &dst->op_params[0], sizeof(float));
+    memcpy(&max_bias, &dst->op_params[1], sizeof(float));
+    if (!grow(ctx->ws, ctx->ws_cap, lfamd_flash_attn_workspace(D, n_q, n_kv, n_head, n_head_kv, ne3)))
+        return GGML_STATUS_ALLOC_FAILED;
+    const int rc = lfamd_flash_attn((const float *)q->data, q->nb[1], q->nb[2], q->nb[3], (int)k->type, k->data, k->nb[1], k->nb[2], k->nb[3],
+                                    (int)v->type, v->data, v->nb[1], v->nb[2], v->nb[3], mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, D, n_q,
+                                    n_kv, n_head, n_head_kv, ne3, scale, max_bias, (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3],
+                                    ctx->ws, ctx->ws_cap, 0u, nullptr);
+    if (rc != LFAMD_OK) {
+        logf("ggml_backend_lfamd: %s: %s\n", "lfamd_flash_attn", lfamd_last_error());
+        return GGML_STATUS_FAILED;
+    }
+    ctx->flash_attn_calls++;
+    return GGML_STATUS_SUCCESS;
+}
+
 // ------------------------------------------------------------------ backend interface
 GGML_CALL const char *be_get_name(ggml_backend_t) {
     return "ROCm-lfamd";
@@ -838,8 +898,9 @@ GGML_CALL const char *be_get_name(ggml_backend_t) {
 GGML_CALL void be_free(ggml_backend_t backend) {
     backend_ctx *c = (backend_ctx *)backend->context;
     if (g_api && g_api->getenv && g_api->getenv("LFAMD_BACKEND_STATS"))
-        fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\nggml_backend_lfamd: %ld block-K calls\n",
-                c->sibling_calls, c->batched_calls, c->block_k_calls);
+        fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\nggml_backend_lfamd: %ld block-K calls\n"
+                        "ggml_backend_lfamd: %ld flash-attn calls\n",
+                c->sibling_calls, c->batched_calls, c->block_k_calls, c->flash_attn_calls);
     {
         on_device d(c->device);
         (void)hipDeviceSynchronize();
@@ -887,6 +948,8 @@ GGML_CALL enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_
                 else
                     i += run - 1, c->sibling_calls += 1;
             }
+        } else if (g_op_flash_attn >= 0 && node->op == g_op_flash_attn) {
+            st = run_flash_attn(c, node);
         } else if (g_api->ggml_is_empty(node))
             continue;
         else {
@@ -908,6 +971,8 @@ GGML_CALL bool be_supports_op(ggml_backend_t, const struct ggml_tensor *op) {
         return mul_mat_supported(op);
     if (op->op == g_op_mul_mat_id)
         return mul_mat_id_supported(op);
+    if (g_op_flash_attn >= 0 && op->op == g_op_flash_attn)
+        return flash_attn_supported(op);
     return is_view_op(g_api->ggml_op_name(op->op));
 }
 GGML_CALL bool be_supports_buft(ggml_backend_t backend, ggml_backend_buffer_type_t buft) {
@@ -948,6 +1013,18 @@ GGML_CALL bool ggml_cuda_link(const struct ggml_backend_api *backend_api) {
     if (g_op_mul_mat < 0 || g_op_mul_mat_id < 0) {
         logf("%s: the host's ggml_op_name table has no MUL_MAT / MUL_MAT_ID below 40: refusing to link\n", "ggml_cuda_link");
         return false;
+    }
+    // FLASH_ATTN_EXT: looked up the same way, below 64 and up to the table's first NULL name (RECALLED bound: upstream's table is
+    // longer than that at every revision that has the op).  A host whose table lacks the name still links; the op is never offered.
+    g_op_flash_attn = -1;
+    for (int i = 0; i < 64; i++) {
+        const char *n = backend_api->ggml_op_name(i);
+        if (!n)
+            break;
+        if (!strcmp(n, "FLASH_ATTN_EXT")) {
+            g_op_flash_attn = i;
+            break;
+        }
     }
     // type numbers, block and element sizes must be the ones this module was built for
     for (size_t i = 0; i < sizeof(k_types) / sizeof(k_types[0]); i++) {
