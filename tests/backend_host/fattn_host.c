@@ -5,11 +5,14 @@
  *
  *   fattn_host <module.so> decline <case>   what supports_op says for one node ("accepted" / "declined"); nothing is computed.
  *       control (F16 K / V, D = 128, F16 mask), control_nomask, d96, max_bias, prec_f32, q4_0_k, view_offs (Q a view 8 bytes into
- *       its parent, no address yet), control_view_offs16
- *   fattn_host <module.so> run <Q.bin> <K.bin> <V.bin> <mask.bin> <out.bin>
- *       one graph_compute of a grouped-query node: 2 KV heads x 4, n_q = 17, n_kv = 65, D = 128; Q memory [n_q][n_head][D], K / V
- *       the permuted cache views (memory [n_kv][kv head][D]), the mask F16 [65 x 32] (padded to 32 rows), dst contiguous
- *       [D, n_head, n_q]; op_params = {1 / sqrt(128), 0, GGML_PREC_DEFAULT}
+ *       its parent, no address yet), control_view_offs16; and, each the control node with one change: q_f16, v_f32, dst_f16, q_nb0,
+ *       dst_strided, v_ne1, v_ne2, k_ne3, heads_3kv (8 heads on 3 KV heads), dst_ne1, mask_f32, mask_ne0, mask_ne1, mask_ne2,
+ *       mask_nb1_odd, k_nb1_8 (not a multiple of 16), slices (n_head * ne3 = 65536)
+ *   fattn_host <module.so> run <Q.bin> <K.bin> <V.bin> <mask.bin> <out.bin> [<n_q> <n_kv> <mask rows> [<Q.bin> ... <mask rows>]]
+ *       one graph_compute of one grouped-query node per group of arguments, in their order: 2 KV heads x 4, D = 128, n_q = 17,
+ *       n_kv = 65 and a mask of 32 rows where the three numbers are not given; Q memory [n_q][n_head][D], K / V the permuted cache
+ *       views (memory [n_kv][kv head][D]), the mask F16 [n_kv x mask rows] (padded beyond n_q), dst contiguous [D, n_head, n_q];
+ *       op_params = {1 / sqrt(128), 0, GGML_PREC_DEFAULT}
  */
 #include <math.h>
 
@@ -25,19 +28,19 @@ static GGML_CALL const char *h_op_name_fa(int op) {
     return op >= 0 && op < 60 ? h_op_name(op) : NULL; /* a table of 60 names */
 }
 
-enum { D = 128, N_Q = 17, N_KV = 65, KVH = 2, HEADS = 8, MASK_ROWS = 32 };
+enum { D = 128, N_Q = 17, N_KV = 65, KVH = 2, HEADS = 8, MASK_ROWS = 32, MAX_NODES = 4 };
 
 static void fa_node(struct ggml_tensor *Q, struct ggml_tensor *K, struct ggml_tensor *V, struct ggml_tensor *M, struct ggml_tensor *OUT, long d,
-                    int ktype) {
-    shape(Q, LFAMD_TYPE_F32, d, N_Q, HEADS, 1); /* memory [n_q][heads][d] */
-    Q->nb[1] = (size_t)HEADS * d * 4, Q->nb[2] = (size_t)d * 4, Q->nb[3] = (size_t)N_Q * HEADS * d * 4;
-    shape(K, ktype, d, N_KV, KVH, 1); /* memory [n_kv][kv heads][row] */
+                    int ktype, long n_q, long n_kv, long mask_rows) {
+    shape(Q, LFAMD_TYPE_F32, d, n_q, HEADS, 1); /* memory [n_q][heads][d] */
+    Q->nb[1] = (size_t)HEADS * d * 4, Q->nb[2] = (size_t)d * 4, Q->nb[3] = (size_t)n_q * HEADS * d * 4;
+    shape(K, ktype, d, n_kv, KVH, 1); /* memory [n_kv][kv heads][row] */
     const size_t row = K->nb[1];
-    K->nb[1] = KVH * row, K->nb[2] = row, K->nb[3] = (size_t)N_KV * KVH * row;
-    shape(V, LFAMD_TYPE_F16, d, N_KV, KVH, 1);
-    V->nb[1] = (size_t)KVH * d * 2, V->nb[2] = (size_t)d * 2, V->nb[3] = (size_t)N_KV * KVH * d * 2;
-    shape(M, LFAMD_TYPE_F16, N_KV, MASK_ROWS, 1, 1);
-    shape(OUT, LFAMD_TYPE_F32, d, HEADS, N_Q, 1);
+    K->nb[1] = KVH * row, K->nb[2] = row, K->nb[3] = (size_t)n_kv * KVH * row;
+    shape(V, LFAMD_TYPE_F16, d, n_kv, KVH, 1);
+    V->nb[1] = (size_t)KVH * d * 2, V->nb[2] = (size_t)d * 2, V->nb[3] = (size_t)n_kv * KVH * d * 2;
+    shape(M, LFAMD_TYPE_F16, n_kv, mask_rows, 1, 1);
+    shape(OUT, LFAMD_TYPE_F32, d, HEADS, n_q, 1);
     const float scale = 1.0f / sqrtf((float)d), max_bias = 0.0f;
     memcpy(&OUT->op_params[0], &scale, 4);
     memcpy(&OUT->op_params[1], &max_bias, 4);
@@ -50,7 +53,7 @@ static int fa_decline(ggml_backend_t be, ggml_backend_buffer_type_t buft, const 
     ggml_backend_buffer_t buf = buft->iface.alloc_buffer(buft, 1 << 21);
     if (!buf) return 10;
     struct ggml_tensor Q, K, V, M, OUT;
-    fa_node(&Q, &K, &V, &M, &OUT, !strcmp(what, "d96") ? 96 : D, !strcmp(what, "q4_0_k") ? LFAMD_TYPE_Q4_0 : LFAMD_TYPE_F16);
+    fa_node(&Q, &K, &V, &M, &OUT, !strcmp(what, "d96") ? 96 : D, !strcmp(what, "q4_0_k") ? LFAMD_TYPE_Q4_0 : LFAMD_TYPE_F16, N_Q, N_KV, MASK_ROWS);
     size_t off = align;
     place(&Q, buf, &off, align);
     off += align;
@@ -69,6 +72,40 @@ static int fa_decline(ggml_backend_t be, ggml_backend_buffer_type_t buft, const 
         OUT.op_params[2] = 1; /* GGML_PREC_F32 */
     } else if (!strcmp(what, "view_offs") || !strcmp(what, "control_view_offs16")) {
         Q.view_src = &OUT, Q.view_offs = !strcmp(what, "view_offs") ? 8 : 16, Q.data = NULL;
+    } else if (!strcmp(what, "q_f16")) { /* from here on: the control node with ONE field changed (nothing is computed) */
+        Q.type = LFAMD_TYPE_F16;
+    } else if (!strcmp(what, "v_f32")) {
+        V.type = LFAMD_TYPE_F32;
+    } else if (!strcmp(what, "dst_f16")) {
+        OUT.type = LFAMD_TYPE_F16;
+    } else if (!strcmp(what, "q_nb0")) {
+        Q.nb[0] = 8;
+    } else if (!strcmp(what, "dst_strided")) {
+        OUT.nb[1] += 16, OUT.nb[2] = OUT.nb[1] * HEADS, OUT.nb[3] = OUT.nb[2] * N_Q; /* rows 16 bytes apart: aligned, not contiguous */
+    } else if (!strcmp(what, "v_ne1")) {
+        V.ne[1] = N_KV + 1;
+    } else if (!strcmp(what, "v_ne2")) {
+        V.ne[2] = 1;
+    } else if (!strcmp(what, "k_ne3")) {
+        K.ne[3] = 2;
+    } else if (!strcmp(what, "heads_3kv")) {
+        K.ne[2] = V.ne[2] = 3;
+    } else if (!strcmp(what, "dst_ne1")) {
+        OUT.ne[1] = HEADS + 1, OUT.nb[2] = OUT.nb[1] * OUT.ne[1], OUT.nb[3] = OUT.nb[2] * N_Q; /* (still contiguous) */
+    } else if (!strcmp(what, "mask_f32")) {
+        M.type = LFAMD_TYPE_F32;
+    } else if (!strcmp(what, "mask_ne0")) {
+        M.ne[0] = N_KV - 1;
+    } else if (!strcmp(what, "mask_ne1")) {
+        M.ne[1] = N_Q - 1;
+    } else if (!strcmp(what, "mask_ne2")) {
+        M.ne[2] = 2;
+    } else if (!strcmp(what, "mask_nb1_odd")) {
+        M.nb[1] = 2 * N_KV + 1;
+    } else if (!strcmp(what, "k_nb1_8")) {
+        K.nb[1] += 8;
+    } else if (!strcmp(what, "slices")) {
+        Q.ne[3] = K.ne[3] = V.ne[3] = OUT.ne[3] = 8192; /* 8 heads x 8192 = 65536 */
     } else {
         fprintf(stderr, "unknown case %s\n", what);
         return 2;
@@ -79,35 +116,53 @@ static int fa_decline(ggml_backend_t be, ggml_backend_buffer_type_t buft, const 
     return 0;
 }
 
-static int fa_run(ggml_backend_t be, ggml_backend_buffer_type_t buft, char **argv) {
-    size_t nq, nk, nv, nm;
-    void *hq = slurp(argv[3], &nq), *hk = slurp(argv[4], &nk), *hv = slurp(argv[5], &nv), *hm = slurp(argv[6], &nm);
-    struct ggml_tensor Q, K, V, M, OUT;
-    fa_node(&Q, &K, &V, &M, &OUT, D, LFAMD_TYPE_F16);
-    if (h_nbytes(&Q) != nq || h_nbytes(&K) != nk || h_nbytes(&V) != nv || h_nbytes(&M) != nm) { fprintf(stderr, "input size mismatch\n"); return 9; }
+/* argv[3 ..]: per node <Q> <K> <V> <mask> <out> <n_q> <n_kv> <mask rows>; the three numbers of the first node may be left out */
+static int fa_run(ggml_backend_t be, ggml_backend_buffer_type_t buft, int argc, char **argv) {
+    const int n_nodes = argc <= 8 ? 1 : (argc - 3) / 8;
+    if (n_nodes > MAX_NODES || (argc > 8 && (argc - 3) % 8 != 0)) { fprintf(stderr, "usage\n"); return 2; }
+    struct ggml_tensor Q[MAX_NODES], K[MAX_NODES], V[MAX_NODES], M[MAX_NODES], OUT[MAX_NODES];
+    struct ggml_tensor *nodes[MAX_NODES];
+    void *hq[MAX_NODES], *hk[MAX_NODES], *hv[MAX_NODES], *hm[MAX_NODES];
+    size_t nq[MAX_NODES], nk[MAX_NODES], nv[MAX_NODES], nm[MAX_NODES], kv_bytes = 0, c_bytes = 0;
     const size_t align = buft->iface.get_alignment(buft);
-    ggml_backend_buffer_t kvbuf = buft->iface.alloc_buffer(buft, nk + nv + 8 * align);
-    ggml_backend_buffer_t cbuf = buft->iface.alloc_buffer(buft, nq + nm + h_nbytes(&OUT) + 8 * align);
+    for (int i = 0; i < n_nodes; i++) {
+        char **a = argv + 3 + 8 * i;
+        const bool dims = argc > 8;
+        hq[i] = slurp(a[0], &nq[i]), hk[i] = slurp(a[1], &nk[i]), hv[i] = slurp(a[2], &nv[i]), hm[i] = slurp(a[3], &nm[i]);
+        fa_node(&Q[i], &K[i], &V[i], &M[i], &OUT[i], D, LFAMD_TYPE_F16, dims ? atol(a[5]) : N_Q, dims ? atol(a[6]) : N_KV, dims ? atol(a[7]) : MASK_ROWS);
+        if (h_nbytes(&Q[i]) != nq[i] || h_nbytes(&K[i]) != nk[i] || h_nbytes(&V[i]) != nv[i] || h_nbytes(&M[i]) != nm[i]) {
+            fprintf(stderr, "input size mismatch (node %d)\n", i);
+            return 9;
+        }
+        kv_bytes += nk[i] + nv[i] + 2 * align, c_bytes += nq[i] + nm[i] + h_nbytes(&OUT[i]) + 3 * align;
+        nodes[i] = &OUT[i];
+    }
+    ggml_backend_buffer_t kvbuf = buft->iface.alloc_buffer(buft, kv_bytes + 8 * align);
+    ggml_backend_buffer_t cbuf = buft->iface.alloc_buffer(buft, c_bytes + 8 * align);
     if (!kvbuf || !cbuf) return 10;
     size_t ko = 2 * align, co = align; /* every operand at a non-zero offset */
-    place(&K, kvbuf, &ko, align);
-    place(&V, kvbuf, &ko, align);
-    place(&Q, cbuf, &co, align);
-    place(&M, cbuf, &co, align);
-    place(&OUT, cbuf, &co, align);
-    kvbuf->iface.set_tensor(kvbuf, &K, hk, 0, nk);
-    kvbuf->iface.set_tensor(kvbuf, &V, hv, 0, nv);
-    cbuf->iface.set_tensor(cbuf, &Q, hq, 0, nq);
-    cbuf->iface.set_tensor(cbuf, &M, hm, 0, nm);
-    if (!be->iface.supports_op(be, &OUT)) { fprintf(stderr, "supports_op says no\n"); return 11; }
-    struct ggml_tensor *nodes[1] = {&OUT};
-    struct ggml_cgraph g = {1, 1, 0, nodes, NULL, NULL};
+    for (int i = 0; i < n_nodes; i++) {
+        place(&K[i], kvbuf, &ko, align);
+        place(&V[i], kvbuf, &ko, align);
+        place(&Q[i], cbuf, &co, align);
+        place(&M[i], cbuf, &co, align);
+        place(&OUT[i], cbuf, &co, align);
+        kvbuf->iface.set_tensor(kvbuf, &K[i], hk[i], 0, nk[i]);
+        kvbuf->iface.set_tensor(kvbuf, &V[i], hv[i], 0, nv[i]);
+        cbuf->iface.set_tensor(cbuf, &Q[i], hq[i], 0, nq[i]);
+        cbuf->iface.set_tensor(cbuf, &M[i], hm[i], 0, nm[i]);
+        if (!be->iface.supports_op(be, &OUT[i])) { fprintf(stderr, "supports_op says no (node %d)\n", i); return 11; }
+    }
+    struct ggml_cgraph g = {n_nodes, n_nodes, 0, nodes, NULL, NULL};
     if (be->iface.graph_compute(be, &g) != GGML_STATUS_SUCCESS) { fprintf(stderr, "graph_compute failed\n"); return 12; }
     be->iface.synchronize(be);
-    const size_t no = h_nbytes(&OUT);
-    void *ho = malloc(no);
-    cbuf->iface.get_tensor(cbuf, &OUT, ho, 0, no);
-    dump(argv[7], "", ho, no);
+    for (int i = 0; i < n_nodes; i++) {
+        const size_t no = h_nbytes(&OUT[i]);
+        void *ho = malloc(no);
+        cbuf->iface.get_tensor(cbuf, &OUT[i], ho, 0, no);
+        dump(argv[3 + 8 * i + 4], "", ho, no);
+        free(ho);
+    }
     cbuf->iface.free_buffer(cbuf);
     kvbuf->iface.free_buffer(kvbuf);
     be->iface.free(be);
@@ -131,7 +186,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[2], "decline"))
         return argc < 4 ? 2 : fa_decline(be, buft, argv[3]);
     if (!strcmp(argv[2], "run"))
-        return argc < 8 ? 2 : fa_run(be, buft, argv);
+        return argc < 8 ? 2 : fa_run(be, buft, argc, argv);
     fprintf(stderr, "unknown mode %s\n", argv[2]);
     return 2;
 }

@@ -59,8 +59,109 @@ def test_masks_keep_a_live_key_in_every_row_and_a_dead_first_tile():
     assert np.isinf(m[1, :R.CHUNK]).sum() >= 70
 
 
+# ---- the edge cases (fattn_ref.decode_edge_cases / prefill_edge_cases / scale_cases)
+def test_edge_case_ids_are_new_and_distinct():
+    old = {R.case_id(c) for c in R.decode_cases() + R.prefill_cases()}
+    new = [R.case_id(c) for c in R.decode_edge_cases() + R.prefill_edge_cases()]
+    assert len(set(new)) == len(new) and not old & set(new)
+    assert all(R.route_of(c[4]) == "decode" for c in R.decode_edge_cases())
+    assert all(R.route_of(c[4]) == "prefill" for c in R.prefill_edge_cases())
+
+
+def test_decode_edge_cases_keep_the_margin_the_tolerance_was_derived_with():
+    """TOL_F32 is 4 x the emulation's largest error over decode_cases(); every new input stays within that figure."""
+    for c, scale in [(c, None) for c in R.decode_edge_cases()] + [cs for cs in R.scale_cases() if R.route_of(cs[0][4]) == "decode"]:
+        Q, K, V, mask, scale = R.inputs_of(c, scale=scale)
+        ref, a = R.ref64(Q, K, V, mask, scale, "decode")
+        err = R.row_err(R.emulate(Q, K, V, mask, scale, "decode"), ref, a)
+        print(R.case_id(c), float(scale), err)
+        assert err <= R.TOL_F32 / 4, R.case_id(c)
+
+
+def test_prefill_edge_cases_emulate_within_half_the_tolerance():
+    for c, scale in [(c, None) for c in R.prefill_edge_cases()] + [cs for cs in R.scale_cases() if R.route_of(cs[0][4]) == "prefill"]:
+        Q, K, V, mask, scale = R.inputs_of(c, scale=scale)
+        ref, a = R.ref64(Q, K, V, mask, scale, "prefill")
+        err = R.row_err(R.emulate(Q, K, V, mask, scale, "prefill"), ref, a)
+        print(R.case_id(c), float(scale), err)
+        assert err < R.TOL_MMA / 2, R.case_id(c)
+
+
+def edge_mask(kind, n_q, n_kv):
+    return np.isfinite(R.make_mask(kind, n_q, n_kv, np.random.default_rng(0)))
+
+
+def blocks(live, width):
+    """live [n_q][n_kv] -> [n_q][blocks of `width` keys]: the row has a live key in the block."""
+    n_q, n_kv = live.shape
+    pad = np.zeros((n_q, -n_kv % width), bool)
+    return np.concatenate([live, pad], axis=1).reshape(n_q, -1, width).any(axis=2)
+
+
+def test_decode_edge_masks_have_the_dead_chunks_claimed():
+    C = R.CHUNK
+    w = blocks(edge_mask("window:40", 2, 3 * C + 7), C)
+    assert not w[:, :2].any() and w[:, 2:].all()  # chunks 0 and 1 entirely -inf, 2 and 3 live for both rows
+    h = blocks(edge_mask("head:5", 8, 9 * C + 1), C)
+    assert h[:, 0].all() and not h[:, 1:].any() and h.shape[1] == 10
+    o = edge_mask("onehot", 8, 3 * C + 7)
+    assert (o.sum(axis=1) == 1).all()
+    assert list(np.argmax(o, axis=1)) == [0, 3 * C + 6, C - 1, C, (3 * C + 7) // 2, 1, 3 * C + 5, C + 1]
+    assert blocks(edge_mask("causal70", 8, 3 * C + 7), C)[:, 0].all()  # the 70 keys of 'causal70' kill no chunk of 256
+
+
+def test_tiles_masks_have_dead_tiles_for_every_row_and_one_half_tile_for_wave_1():
+    for n_q, tiles in ((130, [1, 5, 6, 12]), (65, [0, 15])):
+        live = edge_mask("tiles:" + ",".join(map(str, tiles)), n_q, 1000)
+        t64, t32 = blocks(live, 64), blocks(live, 32)
+        dead = [t for t in range(16) if t not in tiles]
+        assert not t64[:128, dead].any()                      # dead for all rows of the first work-group (and of the second)
+        assert not t64[:, dead].any()
+        for t in tiles:
+            assert t64[:32, t].all() and t64[64:, t].all()    # waves 0, 2, 3 (and the second work-group): every listed tile
+        w1 = t32[32:64]
+        assert w1[:, 2 * tiles[1] + 1].all() and w1.sum(axis=1).max() == 1  # wave 1: one 32-key half of one tile
+
+
+def test_window_and_causal0_masks_are_not_decided_by_a_work_groups_last_eight_rows():
+    """A scan of the mask that looked at the last eight rows of a work-group alone would pass every causal mask whose diagonal ends
+    at the last key.  'window': some tile is dead for those rows and live for an earlier one, and some tile the other way round.
+    'causal0' (later rows see more keys, so no tile can be dead for the last rows and live before them): tiles live for the last
+    rows and dead for the first row, and dead tiles behind the last live one for every work-group but the last."""
+    for kind, n_q, n_kv in (("window:40", 300, 300), ("window:40", 130, 1000), ("causal0", 257, 257), ("causal0", 130, 130)):
+        t64 = blocks(edge_mask(kind, n_q, n_kv), 64)
+        wg = t64[:128]
+        last8, earlier = wg[-8:].any(axis=0), wg[:-8].any(axis=0)
+        assert (last8 & ~wg[0]).any(), kind
+        if kind == "causal0":
+            assert not wg[:, 2:].any() and t64.shape[1] > 2   # trailing dead tiles
+        else:
+            assert (~last8 & earlier).any(), (kind, n_q)
+    # a tile that is live for the work-group and dead for three of its four waves: tile 12 of the 130 x 1000 window (row 0 alone)
+    t64 = blocks(edge_mask("window:40", 130, 1000), 64)
+    assert t64[0, 12] and not t64[32:128, 12].any()
+    # a run of several dead tiles between two live ones
+    assert "".join("x" if v else "." for v in blocks(edge_mask("tiles:1,5,6,12", 130, 1000), 64)[0]) == ".x...xx.....x..."
+
+
+def test_segment_masks_have_the_dead_segments_claimed():
+    """Tiles per segment of the live flags: 128.  16449 keys are 258 tiles: segments of 128, 128 and 2 tiles, the last tile of one key."""
+    def segs(kind, n_kv):
+        t64 = blocks(edge_mask(kind, 9, n_kv), 64).any(axis=0)
+        return [t64[s:s + 128] for s in range(0, len(t64), 128)]
+    s = segs("tail:60", 16449)
+    assert len(s) == 3 and not s[0].any() and not s[1].any() and s[2].all() and len(s[2]) == 2
+    s = segs("tail:100", 16449)  # the last 100 keys begin in tile 255: segment 0 is dead, segment 1 but for its last tile
+    assert not s[0].any() and not s[1][:-1].any() and s[1][-1] and s[2].all()
+    s = segs("head:100", 16449)
+    assert s[0][:2].all() and not s[0][2:].any() and not s[1].any() and not s[2].any()
+    s = segs("window:100", 8257)
+    assert len(s) == 2 and not s[0][:-1].any() and s[0][-1] and s[1].all() and len(s[1]) == 2
+    assert (8192 + 63) // 64 == 128 and (8193 + 63) // 64 == 129  # one full segment; a second segment of one tile with one key
+
+
 # ---- the call's checks
-PQ, PK, PV, PM, PD, PW = 0x10000, 0x20000, 0x30000, 0x40002, 0x50000, 0x60000  # never dereferenced
+PQ,PK, PV, PM, PD, PW = 0x10000, 0x20000, 0x30000, 0x40002, 0x50000, 0x60000  # never dereferenced
 ORDER = ["Q", "q_nb1", "q_nb2", "q_nb3", "Ktype", "K", "k_nb1", "k_nb2", "k_nb3", "Vtype", "V", "v_nb1", "v_nb2", "v_nb3", "mask", "mask_nb1",
          "D", "n_q", "n_kv", "n_head", "n_head_kv", "ne3", "scale", "max_bias", "dst", "dst_nb1", "dst_nb2", "dst_nb3", "ws", "ws_bytes",
          "flags", "stream"]
