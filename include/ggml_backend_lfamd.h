@@ -1,15 +1,16 @@
 /*
  * ggml_backend_lfamd.h — the GPU-MODULE boundary: what llamafile/cuda.c dlopen()s as
  * ggml-rocm.so and imports by name (llamafile/cuda.c:726-737), served by the MI355X mat-mul module for the operators
- * it accelerates (GGML_OP_MUL_MAT, GGML_OP_MUL_MAT_ID, and GGML_OP_FLASH_ATTN_EXT on an F16 K / V cache; everything else stays
- * with the CPU backend: supports_op).
+ * it accelerates (GGML_OP_MUL_MAT, GGML_OP_MUL_MAT_ID, GGML_OP_FLASH_ATTN_EXT on an F16 K / V cache, and GGML_OP_CPY into a cache
+ * kept in the module's buffers; everything else stays with the CPU backend: supports_op).
  *
  * ONE header holds every ggml layout this glue touches.  Those marked IN-TREE are restated from the reference's own
  * patches; those marked RECALLED come from un-vendored upstream llama.cpp @ 8b3befc and must be
  * regenerated from the real headers when the submodule is available.  What can drift silently is NOT trusted: operator
  * and type NUMBERS are resolved at link time through the host's own ggml_op_name / ggml_type_name / ggml_type_size /
- * ggml_blck_size callbacks, and ggml_cuda_link answers false on any mismatch.  FLASH_ATTN_EXT is searched for below operator
- * number 64, up to the table's first NULL name (RECALLED bound); a host without the name links and is never offered the op.  Its
+ * ggml_blck_size callbacks, and ggml_cuda_link answers false on any mismatch.  FLASH_ATTN_EXT and CPY are searched for below operator
+ * number 64, up to the table's first NULL name (RECALLED bound); a host without a name links and is never offered that op (CPY:
+ * RECALLED operands src[0] = source, src[1] = destination, the node a view of src[1]; ggml-cuda.cu.patch:5150-5160).  FLASH_ATTN_EXT's
  * operands (RECALLED: src[0..3] = Q, K, V, mask; op_params = scale, max_bias, precision; GGML_PREC_DEFAULT = 0) are those of
  * the reference's launcher, ggml-cuda.cu.patch:8352-8375.
  *

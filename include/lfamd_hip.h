@@ -568,6 +568,54 @@ int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
                      float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
                      void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream);
 
+/* ---- GGML_OP_CPY: the store into an offloaded K / V cache, and the same-type moves of its defragmentation ----------
+ * What a llama.cpp graph holds per layer to fill the cache: src = the F32 k_cur / v_cur, dst = a view into the cache tensor
+ * (csrc/cpy.hip; reference: ggml_cuda_cpy, ggml-cuda.cu.patch:4242-4760, dispatch :5150-5260).  ggml's semantics: both tensors have
+ * the same number of elements, element i of the flattened source (index 0 fastest) becomes element i of the flattened destination;
+ * the shapes may differ.  ne[] / nb[] are ggml's, host arrays of four read before the call returns; nb[] in BYTES; for a block type
+ * ne[0] counts elements and nb[0] is the block size.
+ * Type pairs: F32 -> F32, F16, Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL (the list lfamd_mul_mat_batched_q reads); F16 -> F16 and each of
+ * the six block types onto itself (bytes unchanged, whole blocks moved).  Everything else (F16 -> F32, BF16, the K-quants) is
+ * LFAMD_ERR_UNSUPPORTED.
+ * Arithmetic — a function of the element or of the 32-block alone, never of the route, the shape description or the alignment:
+ *   F32 -> F16: round to nearest even; beyond F16's range +-inf; NaN stays NaN (numpy's astype(float16), bit for bit).
+ *   F32 -> block type: the scalar rule of ggml's quantize_row_<type>_reference as the reference's device copies restate it
+ *   (ggml-cuda.cu.patch:4330-4722), in f32, every product rounded before the add that follows it (no fused multiply-add),
+ *   id = d != 0 ? 1 / d : 0 by an IEEE division, the stored d / m = f16(d) / f16(min):
+ *     Q8_0   d = amax / 127, codes roundf(x * id)
+ *     Q4_0   vmax = the first element of the largest |x|; d = vmax / -8; code min(15, (int8_t)(x * id + 8.5f))
+ *     Q5_0   d = vmax / -16; code min(31, (int8_t)(x * id + 16.5f)); bit 4 of code j -> bit j of qh
+ *     Q4_1   d = (max - min) / 15; code min(15, (int8_t)((x - min) * id + 0.5f)); min / max = the first of equal values
+ *     Q5_1   d = (max - min) / 31; code (uint8_t)((x - min) * id + 0.5f)
+ *     IQ4_NL d0 = vmax / -127; codes = the nearest codebook value of x * id0, a tie to the upper index; then, with w = x * x and q the
+ *            codebook value, d = sumq2 > 0 ? sumqx / sumq2 : d0 where, for j = 0 .. 15 in ascending order,
+ *            sumqx += w[j] * q[j] * x[j] + w[j + 16] * q[j + 16] * x[j + 16] and sumq2 += w[j] * q[j] * q[j] + w[j + 16] * ...
+ *            (the reference's pairing of j with j + 16 inside one step, each product chain left to right)
+ *   Domain of the block types: finite inputs whose 1 / d is finite.
+ * Routes, by the layouts alone; all give the same bytes:
+ *   rows        both sides contiguous over runs of at least 128 elements (F32 -> block type; 64 destination bytes for any other pair): 16-byte
+ *               loads, eight lanes per 32-block, the run's image assembled in LDS and written with 16-byte stores between a head and a
+ *               tail of 2-byte stores (a Q8_0 row is only 2-byte aligned).  The K store, the V store under -fa, defragmentation.
+ *   transposed  F32 -> F16, two dimensions of the same extents on both sides, src nb[1] == 4 != src nb[0], dst nb[0] == 2, ne[0] >= 8,
+ *               ne[1] >= 2 (the V store without -fa): 64 x 32 tiles through padded LDS, coalesced on both sides, 16-byte stores inside a
+ *               destination row.  ne[0] < 8 (one token: every destination row is one element) takes the general route.
+ *   general     any other layout: an element per lane, a block per eight lanes.
+ * Memory contract: no byte outside the destination's elements is written — not the neighbouring cache cells, not the gap between
+ * strided rows, not the bytes in front of an unaligned run or behind it; nothing outside the source's elements is read.  Source and
+ * destination must not overlap.  Asynchronous on `stream`, graph-capturable: no allocation, no host read-back, no atomics, no
+ * workspace; deterministic.
+ * Checks, before any device call and in this order:
+ *   1. a NULL ne / nb array; a negative extent on either side                               -> LFAMD_ERR_INVALID
+ *   2. a destination without elements (a zero extent) -> LFAMD_OK, nothing launched, no pointer, type or stride looked at
+ *   3. a type pair outside the list; more than 2^31 - 1 elements on either side (the grid)  -> LFAMD_ERR_UNSUPPORTED
+ *   4. a NULL pointer; unequal element counts; beside a block type: ne[0] % 32 != 0 on either side, dst nb[0] not the block size, src
+ *      nb[0] not its element / block size (4 for F32); a base or stride that is not a multiple of the element alignment (4 for F32, 2
+ *      for F16 and the blocks); where nb[0] is the element size, a stride of a dimension of extent > 1 that is smaller than the row;
+ *      flags != 0 (reserved)                                                                -> LFAMD_ERR_INVALID */
+int lfamd_cpy(int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4],
+              int dst_type, void *d_dst, const long dst_ne[4], const size_t dst_nb[4],
+              unsigned flags, void *stream);
+
 /* ---- collectives (tensor parallel, one process per GPU) ---------------------------------------
  * The exchange step of the sharded path: attn_output / ffn_down are split by input columns and
  * the f32 partial sums of the residual stream are all-reduced; output.weight is split by vocabulary rows and the logits

@@ -84,6 +84,7 @@ _SIGS = {
     "lfamd_flash_attn_workspace": (_sz, [_l, _l, _l, _l, _l, _l]),
     "lfamd_flash_attn": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
                               C.c_float, C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u, _vp]),
+    "lfamd_cpy": (_i, [_i, _vp, C.POINTER(_l), C.POINTER(_sz), _i, _vp, C.POINTER(_l), C.POINTER(_sz), _u, _vp]),
     "lfamd_comm_unique_id": (_i, [_vp]),
     "lfamd_comm_init": (_i, [C.POINTER(_vp), _i, _i, _vp]),
     "lfamd_comm_destroy": (_i, [_vp]),

@@ -1,6 +1,7 @@
 // ggml_backend_lfamd.hip — the 12 GGML_CALL (ms_abi) symbols llamafile/cuda.c:726-737 imports from ggml-rocm.so, served by
-// this module: a ggml backend whose supports_op says yes to GGML_OP_MUL_MAT / GGML_OP_MUL_MAT_ID and, on an F16
-// K / V cache, GGML_OP_FLASH_ATTN_EXT (the graph of -fa; reference: ggml_cuda_flash_attn_ext, ggml-cuda.cu.patch:8280-8400).
+// this module: a ggml backend whose supports_op says yes to GGML_OP_MUL_MAT / GGML_OP_MUL_MAT_ID, on an F16
+// K / V cache GGML_OP_FLASH_ATTN_EXT (the graph of -fa; reference: ggml_cuda_flash_attn_ext, ggml-cuda.cu.patch:8280-8400), and
+// GGML_OP_CPY into a cache in this backend's buffers (the K / V store; reference: ggml_cuda_cpy, ggml-cuda.cu.patch:5150-5260).
 //
 // Reference counterparts: ggml_cuda_link (ggml-cuda.cu.patch:468), the buffer interface (:16890-17027, set_tensor :16971),
 // the buffer type (:17040-17100, row padding :17072-17081), supports_op (:19221-19262), graph_compute (:18945),
@@ -35,6 +36,7 @@ namespace {
 const ggml_backend_api *g_api = nullptr;
 int g_op_mul_mat = -1, g_op_mul_mat_id = -1;
 int g_op_flash_attn = -1; // -1: the host's table does not name FLASH_ATTN_EXT; the op is never offered
+int g_op_cpy = -1;        // the same for CPY
 bool g_linked = false;
 
 #define LFAMD_MAX_DEVS 16 // GGML_CUDA_MAX_DEVICES (ggml-cuda.h.patch: the length of llama.cpp's tensor_split array)
@@ -137,6 +139,7 @@ struct backend_ctx {
     long batched_calls = 0; // lfamd_mul_mat_batched calls: a node's slices in one launch (printed beside it)
     long block_k_calls = 0; // lfamd_mul_mat_batched_q calls: the same for a 32-block src0 outside the weights buffers (a third line)
     long flash_attn_calls = 0; // lfamd_flash_attn calls: one per FLASH_ATTN_EXT node (a fourth line)
+    long cpy_calls = 0;        // lfamd_cpy calls: one per CPY node (a fifth line)
 };
 
 bool grow(void *&p, size_t &cap, size_t need) {
@@ -891,6 +894,69 @@ enum ggml_status run_flash_attn(backend_ctx *ctx, struct ggml_tensor *dst) {
     return GGML_STATUS_SUCCESS;
 }
 
+// ------------------------------------------------------------------ GGML_OP_CPY
+// src[0] = the source, src[1] = the destination (a view into the K / V cache; the node itself is a view of src[1]); element i of the
+// flattened source becomes element i of the flattened destination (reference: ggml_cuda_cpy, ggml-cuda.cu.patch:5150-5260, its
+// supports_op clause :19284-19332).  Accepted is what lfamd_cpy takes (include/lfamd_hip.h: the type pairs, the block-type conditions,
+// the alignment — tested on the view's offset too, as fa_aligned does) on operands in this device's ORDINARY buffers: a tensor that has
+// a buffer (its own, or its view source's before the view is allocated) has this device's; one without a buffer yet is a graph
+// intermediate the scheduler then allocates here.  Never a split buffer's placeholder addresses.
+bool cpy_type_is_block(int t) {
+    return t == LFAMD_TYPE_Q8_0 || t == LFAMD_TYPE_Q4_0 || t == LFAMD_TYPE_Q4_1 || t == LFAMD_TYPE_Q5_0 || t == LFAMD_TYPE_Q5_1 || t == LFAMD_TYPE_IQ4_NL;
+}
+
+bool cpy_operand_ok(const struct ggml_tensor *t, int device) {
+    const struct ggml_backend_buffer *b = t->buffer ? t->buffer : t->view_src ? t->view_src->buffer : nullptr;
+    if (b && (b->iface.get_name != buf_get_name || ((const buffer_ctx *)b->context)->dev != device))
+        return false;
+    const size_t align = t->type == LFAMD_TYPE_F32 ? 4 : 2;
+    if (((uintptr_t)t->data | t->view_offs | t->nb[0] | t->nb[1] | t->nb[2] | t->nb[3]) % align != 0)
+        return false;
+    if (t->nb[0] == (size_t)lfamd_type_size(t->type))
+        for (int i = 1; i < 4; i++)
+            if (t->ne[i] > 1 && t->nb[i] < lfamd_row_size(t->type, (long)t->ne[0]))
+                return false;
+    return true;
+}
+
+bool cpy_supported(ggml_backend_t backend, const struct ggml_tensor *op) {
+    const char *off = g_api->getenv ? g_api->getenv("LFAMD_BACKEND_NO_CPY") : nullptr;
+    if (off && atoi(off))
+        return false;
+    const struct ggml_tensor *a = op->src[0], *b = op->src[1];
+    if (!a || !b || !type_ok(a->type) || !type_ok(b->type))
+        return false;
+    const bool blocks = cpy_type_is_block(b->type);
+    if (a->type == LFAMD_TYPE_F32 ? !(b->type == LFAMD_TYPE_F32 || b->type == LFAMD_TYPE_F16 || blocks)
+                                  : !(a->type == b->type && (a->type == LFAMD_TYPE_F16 || blocks)))
+        return false;
+    const int64_t n = g_api->ggml_nelements(a);
+    if (n != g_api->ggml_nelements(b) || n > 0x7fffffffLL)
+        return false;
+    for (int i = 0; i < 4; i++)
+        if (a->ne[i] < 0 || b->ne[i] < 0 || a->ne[i] > 0x7fffffffLL || b->ne[i] > 0x7fffffffLL)
+            return false;
+    if (blocks && (a->ne[0] % 32 != 0 || b->ne[0] % 32 != 0 || b->nb[0] != (size_t)lfamd_type_size(b->type) ||
+                   a->nb[0] != (size_t)lfamd_type_size(a->type)))
+        return false;
+    const int device = ((backend_ctx *)backend->context)->device;
+    return cpy_operand_ok(a, device) && cpy_operand_ok(b, device);
+}
+
+// ONE lfamd_cpy: src[1]'s storage written on its own ne / nb
+enum ggml_status run_cpy(backend_ctx *ctx, struct ggml_tensor *dst) {
+    const struct ggml_tensor *a = dst->src[0], *b = dst->src[1];
+    long a_ne[4], b_ne[4];
+    for (int i = 0; i < 4; i++)
+        a_ne[i] = (long)a->ne[i], b_ne[i] = (long)b->ne[i];
+    if (lfamd_cpy((int)a->type, a->data, a_ne, a->nb, (int)b->type, b->data, b_ne, b->nb, 0u, nullptr) != LFAMD_OK) {
+        logf("ggml_backend_lfamd: %s: %s\n", "lfamd_cpy", lfamd_last_error());
+        return GGML_STATUS_FAILED;
+    }
+    ctx->cpy_calls++;
+    return GGML_STATUS_SUCCESS;
+}
+
 // ------------------------------------------------------------------ backend interface
 GGML_CALL const char *be_get_name(ggml_backend_t) {
     return "ROCm-lfamd";
@@ -899,8 +965,8 @@ GGML_CALL void be_free(ggml_backend_t backend) {
     backend_ctx *c = (backend_ctx *)backend->context;
     if (g_api && g_api->getenv && g_api->getenv("LFAMD_BACKEND_STATS"))
         fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\nggml_backend_lfamd: %ld block-K calls\n"
-                        "ggml_backend_lfamd: %ld flash-attn calls\n",
-                c->sibling_calls, c->batched_calls, c->block_k_calls, c->flash_attn_calls);
+                        "ggml_backend_lfamd: %ld flash-attn calls\nggml_backend_lfamd: %ld cpy calls\n",
+                c->sibling_calls, c->batched_calls, c->block_k_calls, c->flash_attn_calls, c->cpy_calls);
     {
         on_device d(c->device);
         (void)hipDeviceSynchronize();
@@ -950,6 +1016,8 @@ GGML_CALL enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_
             }
         } else if (g_op_flash_attn >= 0 && node->op == g_op_flash_attn) {
             st = run_flash_attn(c, node);
+        } else if (g_op_cpy >= 0 && node->op == g_op_cpy) {
+            st = run_cpy(c, node);
         } else if (g_api->ggml_is_empty(node))
             continue;
         else {
@@ -964,7 +1032,7 @@ GGML_CALL enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_
     }
     return hipDeviceSynchronize() == hipSuccess ? GGML_STATUS_SUCCESS : GGML_STATUS_FAILED;
 }
-GGML_CALL bool be_supports_op(ggml_backend_t, const struct ggml_tensor *op) {
+GGML_CALL bool be_supports_op(ggml_backend_t backend, const struct ggml_tensor *op) {
     if (!op_layout_agrees(op))
         return false;
     if (op->op == g_op_mul_mat)
@@ -973,6 +1041,8 @@ GGML_CALL bool be_supports_op(ggml_backend_t, const struct ggml_tensor *op) {
         return mul_mat_id_supported(op);
     if (g_op_flash_attn >= 0 && op->op == g_op_flash_attn)
         return flash_attn_supported(op);
+    if (g_op_cpy >= 0 && op->op == g_op_cpy)
+        return cpy_supported(backend, op);
     return is_view_op(g_api->ggml_op_name(op->op));
 }
 GGML_CALL bool be_supports_buft(ggml_backend_t backend, ggml_backend_buffer_type_t buft) {
@@ -1014,17 +1084,17 @@ GGML_CALL bool ggml_cuda_link(const struct ggml_backend_api *backend_api) {
         logf("%s: the host's ggml_op_name table has no MUL_MAT / MUL_MAT_ID below 40: refusing to link\n", "ggml_cuda_link");
         return false;
     }
-    // FLASH_ATTN_EXT: looked up the same way, below 64 and up to the table's first NULL name (RECALLED bound: upstream's table is
-    // longer than that at every revision that has the op).  A host whose table lacks the name still links; the op is never offered.
-    g_op_flash_attn = -1;
+    // FLASH_ATTN_EXT and CPY: looked up the same way, below 64 and up to the table's first NULL name (RECALLED bound: upstream's table
+    // is longer than that at every revision that has the ops).  A host whose table lacks a name still links; that op is never offered.
+    g_op_flash_attn = g_op_cpy = -1;
     for (int i = 0; i < 64; i++) {
         const char *n = backend_api->ggml_op_name(i);
         if (!n)
             break;
-        if (!strcmp(n, "FLASH_ATTN_EXT")) {
+        if (g_op_flash_attn < 0 && !strcmp(n, "FLASH_ATTN_EXT"))
             g_op_flash_attn = i;
-            break;
-        }
+        else if (g_op_cpy < 0 && !strcmp(n, "CPY"))
+            g_op_cpy = i;
     }
     // type numbers, block and element sizes must be the ones this module was built for
     for (size_t i = 0; i < sizeof(k_types) / sizeof(k_types[0]); i++) {
