@@ -267,7 +267,11 @@ int lfamd_mul_mat_multi_types(int count, const int *Atype, const void *const *d_
  * asynchronous and graph-capturable — no host read-back (the reference
  * synchronises, ggml-cuda.cu.patch:18528-18531) — and accept Btype F32 (quantised on the device).  Rows whose expert id
  * is out of range are left untouched.  Other expert types gather rows per expert after a routing read-back and run one
- * mat-mul per expert. */
+ * mat-mul per expert.
+ * lfamd_mul_mat_id_takes_f32() says whether a call accepts Btype F32 (1) or wants the activations in the weight type's vec_dot format
+ * (0): Q4_K / Q5_K / Q6_K experts without LFAMD_FLAG_FORCE_GENERIC, up to 4 tokens, or more through the routed launch and its limits
+ * (cols % 256 == 0, fewer than 255 experts, tokens * thinkers <= 60 Ki).  It makes no device call; lfamd_mul_mat_id asks it. */
+int lfamd_mul_mat_id_takes_f32(int type, long cols, int experts, long tokens, int thinkers, unsigned flags);
 size_t lfamd_mul_mat_id_workspace(int type, long rows, long cols, int experts, long tokens, int thinkers);
 int lfamd_mul_mat_id(int type, const void *d_W_packed, long rows, long cols, int experts, int Btype,
                      const void *d_thought, size_t b_row_bytes, int tasks, long tokens,
@@ -546,7 +550,7 @@ int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long k, size_t a
  *   the other rows, or the device's CU count.  A call on many heads gives the bits of calls on one head each.
  * lfamd_flash_attn_workspace is the only source of the workspace size: 0 where no split runs (n_q > 8 or n_kv <= 256, or a
  * dimension < 1), else ne3 * n_head * n_q * ceil(n_kv / 256) * (D + 2) * 4 bytes.  It makes no device call.
- * Checks, before any device call and in this order:
+ * Checks, before any device call and in this order (lfamd_flash_attn_check: the same table, exported — below):
  *   1. a negative dimension (D, n_q, n_kv, n_head, n_head_kv, ne3)                          -> LFAMD_ERR_INVALID
  *   2. n_q, n_head or ne3 == 0 -> LFAMD_OK, nothing launched, no pointer looked at
  *   3. Ktype or Vtype is not LFAMD_TYPE_F16 (quantised K / V: refused; the parameters exist so that the block types can follow);
@@ -557,8 +561,22 @@ int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long k, size_t a
  *      v_nb1 < 2 D, q_nb1 < 4 D or dst_nb1 < 4 D; flags != 0 (reserved)                       -> LFAMD_ERR_INVALID
  *   5. workspace_bytes < lfamd_flash_attn_workspace(...)                                    -> LFAMD_ERR_WORKSPACE
  * Not served, by design (a host declines the node): quantised K / V, ALiBi, GGML_PREC_F32 (the n_q > 8 route rounds Q and p to
- * f16), head sizes other than 64 / 128, logit soft-capping (the call has no parameter for it). */
+ * f16), head sizes other than 64 / 128, logit soft-capping (the call has no parameter for it).
+ * lfamd_flash_attn_check is that list by itself — the call's arguments without scale and stream, no device call, host-only: the code
+ * lfamd_flash_attn would answer before it launches (LFAMD_OK: the call passes, or is empty), lfamd_last_error() set the same way.
+ * lfamd_flash_attn calls it first.  It is what a host's supports_op asks, and for that it alone takes LFAMD_CHECK_UNPLACED in `flags`
+ * (the tensors have no addresses yet): a NULL pointer is then no error and a pointer argument counts with its alignment bits only, and
+ * the workspace arguments are not looked at (neither the NULL test of step 4 nor step 5); every other row is evaluated as above.  To
+ * lfamd_flash_attn the flag is a reserved flag like any other. */
+#define LFAMD_CHECK_UNPLACED 0x40000000u
 size_t lfamd_flash_attn_workspace(long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3);
+int lfamd_flash_attn_check(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
+                           int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,
+                           int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
+                           const void *d_mask, size_t mask_nb1,
+                           long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3, float max_bias,
+                           const float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
+                           const void *d_workspace, size_t workspace_bytes, unsigned flags);
 int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
                      int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,
                      int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
@@ -604,14 +622,20 @@ int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
  * strided rows, not the bytes in front of an unaligned run or behind it; nothing outside the source's elements is read.  Source and
  * destination must not overlap.  Asynchronous on `stream`, graph-capturable: no allocation, no host read-back, no atomics, no
  * workspace; deterministic.
- * Checks, before any device call and in this order:
+ * Checks, before any device call and in this order (lfamd_cpy_check: the same table, exported — below):
  *   1. a NULL ne / nb array; a negative extent on either side                               -> LFAMD_ERR_INVALID
  *   2. a destination without elements (a zero extent) -> LFAMD_OK, nothing launched, no pointer, type or stride looked at
  *   3. a type pair outside the list; more than 2^31 - 1 elements on either side (the grid)  -> LFAMD_ERR_UNSUPPORTED
  *   4. a NULL pointer; unequal element counts; beside a block type: ne[0] % 32 != 0 on either side, dst nb[0] not the block size, src
  *      nb[0] not its element / block size (4 for F32); a base or stride that is not a multiple of the element alignment (4 for F32, 2
  *      for F16 and the blocks); where nb[0] is the element size, a stride of a dimension of extent > 1 that is smaller than the row;
- *      flags != 0 (reserved)                                                                -> LFAMD_ERR_INVALID */
+ *      flags != 0 (reserved)                                                                -> LFAMD_ERR_INVALID
+ * lfamd_cpy_check is that list by itself — the call's arguments without the stream, no device call, host-only: the code lfamd_cpy
+ * would answer before it launches (LFAMD_OK: the call passes, or is empty), lfamd_last_error() set the same way.  lfamd_cpy calls it
+ * first.  It alone takes LFAMD_CHECK_UNPLACED in `flags` (above: a NULL d_src / d_dst is no error, a pointer counts with its alignment
+ * bits only); to lfamd_cpy the flag is a reserved flag like any other. */
+int lfamd_cpy_check(int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4],
+                    int dst_type, const void *d_dst, const long dst_ne[4], const size_t dst_nb[4], unsigned flags);
 int lfamd_cpy(int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4],
               int dst_type, void *d_dst, const long dst_ne[4], const size_t dst_nb[4],
               unsigned flags, void *stream);

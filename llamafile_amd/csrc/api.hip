@@ -1117,6 +1117,13 @@ size_t lfamd_mul_mat_id_workspace(int type, long rows, long cols, int experts, l
     return lfamd_moe_workspace(type, rows, cols, experts, tokens, thinkers);
 }
 
+// f32 activations (the GGML_OP_MUL_MAT_ID boundary) are served by the decode path, which quantises in-kernel, and past 4 tokens by the
+// routed launch within its limits
+int lfamd_mul_mat_id_takes_f32(int type, long cols, int experts, long tokens, int thinkers, unsigned flags) {
+    const bool kq = type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K;
+    return kq && !(flags & LFAMD_FLAG_FORCE_GENERIC) && (tokens <= 4 || (cols % 256 == 0 && experts < 255 && tokens * thinkers <= 60 * 1024));
+}
+
 int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int experts, int Btype, const void *d_thought,
                      size_t b_row_bytes, int tasks, long tokens, const int32_t *d_plan, int thinkers, float *d_result,
                      void *d_ws, size_t ws_bytes, unsigned flags, void *stream) {
@@ -1126,11 +1133,7 @@ int lfamd_mul_mat_id(int type, const void *d_W, long rows, long cols, int expert
     if (rows < 0 || cols < 0 || cols % lfamd_blck_size(lfamd_base_type(type)) || experts <= 0 || tasks <= 0 || thinkers <= 0 ||
         tasks > thinkers || thinkers > experts)
         return fail(LFAMD_ERR_INVALID, "mul_mat_id: bad shape%s", "");
-    // f32 activations (the GGML_OP_MUL_MAT_ID boundary) are served by the decode path, which quantises in-kernel
-    const bool f32_decode = Btype == LFAMD_TYPE_F32 && !(flags & LFAMD_FLAG_FORCE_GENERIC) &&
-                            ((tokens <= 4 && (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K)) ||
-                             (tokens > 4 && cols % 256 == 0 && experts < 255 && tokens * thinkers <= 60 * 1024 &&
-                              (type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K)));
+    const bool f32_decode = Btype == LFAMD_TYPE_F32 && lfamd_mul_mat_id_takes_f32(type, cols, experts, tokens, thinkers, flags);
     if (Btype != lfamd_vec_dot_type(lfamd_base_type(type)) && !f32_decode)
         return fail(LFAMD_ERR_UNSUPPORTED,
                     "mul_mat_id: activations must be in the weight type's vec_dot format (F32 only for Q4_K / Q5_K / Q6_K experts)%s", "");

@@ -396,15 +396,10 @@ int cpy_fail(int code, const char *what) {
     return code;
 }
 
-bool is_block_type(int t) {
-    return t == LFAMD_TYPE_Q8_0 || t == LFAMD_TYPE_Q4_0 || t == LFAMD_TYPE_Q4_1 || t == LFAMD_TYPE_Q5_0 || t == LFAMD_TYPE_Q5_1 ||
-           t == LFAMD_TYPE_IQ4_NL;
-}
-
 bool pair_served(int s, int d) {
     if (s == LFAMD_TYPE_F32)
-        return d == LFAMD_TYPE_F32 || d == LFAMD_TYPE_F16 || is_block_type(d);
-    return s == d && (s == LFAMD_TYPE_F16 || is_block_type(s));
+        return d == LFAMD_TYPE_F32 || d == LFAMD_TYPE_F16 || lfamd_block_k_type(d);
+    return s == d && (s == LFAMD_TYPE_F16 || lfamd_block_k_type(s));
 }
 
 constexpr long CPY_MAX_ELEMENTS = 0x7fffffffL;
@@ -454,49 +449,79 @@ long gcd(long a, long b) {
 
 } // namespace
 
+// where nb[0] is the element size: is a stride of a dimension of extent > 1 smaller than the row?
+static bool cpy_short_row(int type, const long ne[4], const size_t nb[4]) {
+    if (nb[0] != lfamd_type_size(type))
+        return false;
+    for (int i = 1; i < 4; i++)
+        if (ne[i] > 1 && nb[i] < lfamd_row_size(type, ne[0]))
+            return true;
+    return false;
+}
+
+// The checks of include/lfamd_hip.h in their documented order, as one table (the idiom of lfamd_batched_check: evaluated whole, so
+// every row guards itself — a NULL ne / nb array is read as four zeros by the rows behind the first); no device call.  `entry`: asked
+// by lfamd_cpy, to which every flag is reserved; else by lfamd_cpy_check, which takes LFAMD_CHECK_UNPLACED.  true: launch.  false:
+// *rc is the answer (LFAMD_OK: an empty call).
+static bool cpy_check(bool entry, int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4], int dst_type,
+                      const void *d_dst, const long dst_ne[4], const size_t dst_nb[4], unsigned flags, int *rc) {
+    static const long no_ne[4] = {};
+    static const size_t no_nb[4] = {};
+    const bool arrays = src_ne && src_nb && dst_ne && dst_nb;
+    const long *s_ne = arrays ? src_ne : no_ne, *d_ne = arrays ? dst_ne : no_ne;
+    const size_t *s_nb = arrays ? src_nb : no_nb, *d_nb = arrays ? dst_nb : no_nb;
+    const bool unplaced = !entry && (flags & LFAMD_CHECK_UNPLACED);
+    const unsigned reserved = entry ? flags : flags & ~LFAMD_CHECK_UNPLACED;
+    bool negative = false, empty = false;
+    for (int i = 0; i < 4; i++)
+        negative |= s_ne[i] < 0 || d_ne[i] < 0, empty |= d_ne[i] == 0;
+    const long n_src = negative ? -1 : count_elements(s_ne), n_dst = negative ? -1 : count_elements(d_ne);
+    const bool blocks = lfamd_block_k_type(dst_type);
+    const size_t s_align = src_type == LFAMD_TYPE_F32 ? 4 : 2, d_align = dst_type == LFAMD_TYPE_F32 ? 4 : 2;
+    const struct {
+        bool hit;
+        int code;
+        const char *what;
+    } checks[] = {
+        {!arrays, LFAMD_ERR_INVALID, "null ne / nb array"},
+        {negative, LFAMD_ERR_INVALID, "negative extent"},
+        {empty, LFAMD_OK, nullptr},
+        {!pair_served(src_type, dst_type), LFAMD_ERR_UNSUPPORTED, "type pair not served"},
+        {n_src < 0 || n_dst < 0, LFAMD_ERR_UNSUPPORTED, "more than 2^31 - 1 elements"},
+        {!unplaced && (!d_src || !d_dst), LFAMD_ERR_INVALID, "null pointer"},
+        {n_src != n_dst, LFAMD_ERR_INVALID, "source and destination differ in their element count"},
+        {blocks && (s_ne[0] % 32 != 0 || d_ne[0] % 32 != 0), LFAMD_ERR_INVALID, "ne[0] is not a multiple of 32 beside a block type"},
+        {blocks && (d_nb[0] != lfamd_type_size(dst_type) || s_nb[0] != lfamd_type_size(src_type)), LFAMD_ERR_INVALID,
+         "nb[0] beside a block type: the block size, and 4 for its F32 source"},
+        {((uintptr_t)d_src | s_nb[0] | s_nb[1] | s_nb[2] | s_nb[3]) % s_align != 0 ||
+             ((uintptr_t)d_dst | d_nb[0] | d_nb[1] | d_nb[2] | d_nb[3]) % d_align != 0,
+         LFAMD_ERR_INVALID, "a base or stride is not a multiple of the element alignment"},
+        {cpy_short_row(src_type, s_ne, s_nb) || cpy_short_row(dst_type, d_ne, d_nb), LFAMD_ERR_INVALID, "a row stride is smaller than the row"},
+        {reserved != 0, LFAMD_ERR_INVALID, "flags are reserved (0)"},
+    };
+    for (const auto &c : checks)
+        if (c.hit) {
+            *rc = c.what ? cpy_fail(c.code, c.what) : c.code;
+            return false;
+        }
+    return true;
+}
+
+extern "C" int lfamd_cpy_check(int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4], int dst_type, const void *d_dst,
+                               const long dst_ne[4], const size_t dst_nb[4], unsigned flags) {
+    int rc = LFAMD_OK;
+    (void)cpy_check(false, src_type, d_src, src_ne, src_nb, dst_type, d_dst, dst_ne, dst_nb, flags, &rc);
+    return rc;
+}
+
 extern "C" int lfamd_cpy(int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4], int dst_type, void *d_dst,
                          const long dst_ne[4], const size_t dst_nb[4], unsigned flags, void *stream) {
-    // the checks of include/lfamd_hip.h, in their documented order; no device call before they are through
-    if (!src_ne || !src_nb || !dst_ne || !dst_nb)
-        return cpy_fail(LFAMD_ERR_INVALID, "null ne / nb array");
-    for (int i = 0; i < 4; i++)
-        if (src_ne[i] < 0 || dst_ne[i] < 0)
-            return cpy_fail(LFAMD_ERR_INVALID, "negative extent");
-    for (int i = 0; i < 4; i++)
-        if (dst_ne[i] == 0)
-            return LFAMD_OK;
-    if (!pair_served(src_type, dst_type))
-        return cpy_fail(LFAMD_ERR_UNSUPPORTED, "type pair not served");
-    const long n_src = count_elements(src_ne), n_dst = count_elements(dst_ne);
-    if (n_src < 0 || n_dst < 0)
-        return cpy_fail(LFAMD_ERR_UNSUPPORTED, "more than 2^31 - 1 elements");
-    if (!d_src || !d_dst)
-        return cpy_fail(LFAMD_ERR_INVALID, "null pointer");
-    if (n_src != n_dst)
-        return cpy_fail(LFAMD_ERR_INVALID, "source and destination differ in their element count");
-    const bool blocks = is_block_type(dst_type), same = src_type == dst_type;
+    int rc;
+    if (!cpy_check(true, src_type, d_src, src_ne, src_nb, dst_type, d_dst, dst_ne, dst_nb, flags, &rc))
+        return rc;
+    const long n_dst = count_elements(dst_ne);
+    const bool blocks = lfamd_block_k_type(dst_type), same = src_type == dst_type;
     const size_t s_size = lfamd_type_size(src_type), d_size = lfamd_type_size(dst_type);
-    if (blocks && (src_ne[0] % 32 != 0 || dst_ne[0] % 32 != 0))
-        return cpy_fail(LFAMD_ERR_INVALID, "ne[0] is not a multiple of 32 beside a block type");
-    if (blocks && (dst_nb[0] != d_size || src_nb[0] != s_size))
-        return cpy_fail(LFAMD_ERR_INVALID, "nb[0] beside a block type: the block size, and 4 for its F32 source");
-    const size_t s_align = src_type == LFAMD_TYPE_F32 ? 4 : 2, d_align = dst_type == LFAMD_TYPE_F32 ? 4 : 2;
-    if (((uintptr_t)d_src | src_nb[0] | src_nb[1] | src_nb[2] | src_nb[3]) % s_align != 0 ||
-        ((uintptr_t)d_dst | dst_nb[0] | dst_nb[1] | dst_nb[2] | dst_nb[3]) % d_align != 0)
-        return cpy_fail(LFAMD_ERR_INVALID, "a base or stride is not a multiple of the element alignment");
-    for (int side = 0; side < 2; side++) {
-        const long *ne = side ? dst_ne : src_ne;
-        const size_t *nb = side ? dst_nb : src_nb;
-        const int type = side ? dst_type : src_type;
-        if (nb[0] != lfamd_type_size(type))
-            continue;
-        const size_t row = lfamd_row_size(type, ne[0]);
-        for (int i = 1; i < 4; i++)
-            if (ne[i] > 1 && nb[i] < row)
-                return cpy_fail(LFAMD_ERR_INVALID, "a row stride is smaller than the row");
-    }
-    if (flags != 0)
-        return cpy_fail(LFAMD_ERR_INVALID, "flags are reserved (0)");
 
     // both sides in units: an element, or a 32-block (128 bytes of an F32 source)
     cpy_args A{};

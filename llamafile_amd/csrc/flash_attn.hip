@@ -538,42 +538,69 @@ extern "C" size_t lfamd_flash_attn_workspace(long D, long n_q, long n_kv, long n
     return chunks > 1 ? (size_t)ne3 * (size_t)n_head * (size_t)n_q * (size_t)chunks * (size_t)(D + 2) * 4 : 0;
 }
 
+// The checks of include/lfamd_hip.h in their documented order, as one table (the idiom of lfamd_batched_check: evaluated whole, so
+// every row guards itself); no device call.  `entry`: asked by lfamd_flash_attn, to which every flag is reserved; else by
+// lfamd_flash_attn_check, which takes LFAMD_CHECK_UNPLACED.  true: launch.  false: *rc is the answer (LFAMD_OK: an empty call).
+static bool fa_check(bool entry, const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2,
+                     size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3, const void *d_mask, size_t mask_nb1, long D,
+                     long n_q, long n_kv, long n_head, long n_head_kv, long ne3, float max_bias, const float *d_dst, size_t dst_nb1, size_t dst_nb2,
+                     size_t dst_nb3, const void *d_workspace, size_t workspace_bytes, unsigned flags, int *rc) {
+    const bool unplaced = !entry && (flags & LFAMD_CHECK_UNPLACED);
+    const unsigned reserved = entry ? flags : flags & ~LFAMD_CHECK_UNPLACED;
+    const size_t need = lfamd_flash_attn_workspace(D, n_q, n_kv, n_head, n_head_kv, ne3);
+    const struct {
+        bool hit;
+        int code;
+        const char *what;
+    } checks[] = {
+        {D < 0 || n_q < 0 || n_kv < 0 || n_head < 0 || n_head_kv < 0 || ne3 < 0, LFAMD_ERR_INVALID, "negative dimension"},
+        {n_q == 0 || n_head == 0 || ne3 == 0, LFAMD_OK, nullptr},
+        {Ktype != LFAMD_TYPE_F16 || Vtype != LFAMD_TYPE_F16, LFAMD_ERR_UNSUPPORTED, "F16 K and V only"},
+        {D != 64 && D != 128, LFAMD_ERR_UNSUPPORTED, "head size is not 64 or 128"},
+        {max_bias != 0.0f, LFAMD_ERR_UNSUPPORTED, "max_bias != 0 (ALiBi)"},
+        {n_head > 65535 || ne3 > 65535 || (size_t)n_head * (size_t)ne3 > 65535 || (n_q + 127) / 128 > 65535, LFAMD_ERR_UNSUPPORTED,
+         "more than 65535 slices (n_head * ne3) or 128-row query blocks"},
+        {n_kv == 0, LFAMD_ERR_UNSUPPORTED, "n_kv == 0"},
+        {!unplaced && (!d_Q || !d_K || !d_V || !d_dst || (!d_workspace && workspace_bytes != 0)), LFAMD_ERR_INVALID, "null pointer"},
+        {n_head_kv < 1 || n_head % n_head_kv != 0, LFAMD_ERR_INVALID, "n_head is not a multiple of n_head_kv"},
+        {((uintptr_t)d_Q | q_nb1 | q_nb2 | q_nb3 | (uintptr_t)d_K | k_nb1 | k_nb2 | k_nb3 | (uintptr_t)d_V | v_nb1 | v_nb2 | v_nb3 |
+          (uintptr_t)d_dst | dst_nb1 | dst_nb2 | dst_nb3) % 16 != 0,
+         LFAMD_ERR_INVALID, "a Q / K / V / dst base or stride is not a multiple of 16"},
+        {d_mask && (((uintptr_t)d_mask | mask_nb1) % 2 != 0 || mask_nb1 < (size_t)n_kv * 2), LFAMD_ERR_INVALID,
+         "mask base / row stride is odd or the stride is smaller than the row"},
+        {k_nb1 < (size_t)D * 2 || v_nb1 < (size_t)D * 2 || q_nb1 < (size_t)D * 4 || dst_nb1 < (size_t)D * 4, LFAMD_ERR_INVALID,
+         "a row stride is smaller than the row"},
+        {reserved != 0, LFAMD_ERR_INVALID, "flags are reserved (0)"},
+        {!unplaced && workspace_bytes < need, LFAMD_ERR_WORKSPACE, "workspace smaller than lfamd_flash_attn_workspace()"},
+    };
+    for (const auto &c : checks)
+        if (c.hit) {
+            *rc = c.what ? fa_fail(c.code, c.what) : c.code;
+            return false;
+        }
+    return true;
+}
+
+extern "C" int lfamd_flash_attn_check(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1,
+                                      size_t k_nb2, size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
+                                      const void *d_mask, size_t mask_nb1, long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3,
+                                      float max_bias, const float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
+                                      const void *d_workspace, size_t workspace_bytes, unsigned flags) {
+    int rc = LFAMD_OK;
+    (void)fa_check(false, d_Q, q_nb1, q_nb2, q_nb3, Ktype, d_K, k_nb1, k_nb2, k_nb3, Vtype, d_V, v_nb1, v_nb2, v_nb3, d_mask, mask_nb1, D, n_q, n_kv,
+                   n_head, n_head_kv, ne3, max_bias, d_dst, dst_nb1, dst_nb2, dst_nb3, d_workspace, workspace_bytes, flags, &rc);
+    return rc;
+}
+
 extern "C" int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1,
                                 size_t k_nb2, size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
                                 const void *d_mask, size_t mask_nb1, long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3,
                                 float scale, float max_bias, float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
                                 void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream) {
-    // the checks of include/lfamd_hip.h, in their documented order; no device call before they are through
-    if (D < 0 || n_q < 0 || n_kv < 0 || n_head < 0 || n_head_kv < 0 || ne3 < 0)
-        return fa_fail(LFAMD_ERR_INVALID, "negative dimension");
-    if (n_q == 0 || n_head == 0 || ne3 == 0)
-        return LFAMD_OK;
-    if (Ktype != LFAMD_TYPE_F16 || Vtype != LFAMD_TYPE_F16)
-        return fa_fail(LFAMD_ERR_UNSUPPORTED, "F16 K and V only");
-    if (D != 64 && D != 128)
-        return fa_fail(LFAMD_ERR_UNSUPPORTED, "head size is not 64 or 128");
-    if (max_bias != 0.0f)
-        return fa_fail(LFAMD_ERR_UNSUPPORTED, "max_bias != 0 (ALiBi)");
-    if (n_head > 65535 || ne3 > 65535 || n_head * ne3 > 65535 || (n_q + 127) / 128 > 65535)
-        return fa_fail(LFAMD_ERR_UNSUPPORTED, "more than 65535 slices (n_head * ne3) or 128-row query blocks");
-    if (n_kv == 0)
-        return fa_fail(LFAMD_ERR_UNSUPPORTED, "n_kv == 0");
-    const size_t need = lfamd_flash_attn_workspace(D, n_q, n_kv, n_head, n_head_kv, ne3);
-    if (!d_Q || !d_K || !d_V || !d_dst || (!d_workspace && workspace_bytes != 0))
-        return fa_fail(LFAMD_ERR_INVALID, "null pointer");
-    if (n_head_kv < 1 || n_head % n_head_kv != 0)
-        return fa_fail(LFAMD_ERR_INVALID, "n_head is not a multiple of n_head_kv");
-    if (((uintptr_t)d_Q | q_nb1 | q_nb2 | q_nb3 | (uintptr_t)d_K | k_nb1 | k_nb2 | k_nb3 | (uintptr_t)d_V | v_nb1 | v_nb2 | v_nb3 |
-         (uintptr_t)d_dst | dst_nb1 | dst_nb2 | dst_nb3) % 16 != 0)
-        return fa_fail(LFAMD_ERR_INVALID, "a Q / K / V / dst base or stride is not a multiple of 16");
-    if (d_mask && (((uintptr_t)d_mask | mask_nb1) % 2 != 0 || mask_nb1 < (size_t)n_kv * 2))
-        return fa_fail(LFAMD_ERR_INVALID, "mask base / row stride is odd or the stride is smaller than the row");
-    if (k_nb1 < (size_t)D * 2 || v_nb1 < (size_t)D * 2 || q_nb1 < (size_t)D * 4 || dst_nb1 < (size_t)D * 4)
-        return fa_fail(LFAMD_ERR_INVALID, "a row stride is smaller than the row");
-    if (flags != 0)
-        return fa_fail(LFAMD_ERR_INVALID, "flags are reserved (0)");
-    if (workspace_bytes < need)
-        return fa_fail(LFAMD_ERR_WORKSPACE, "workspace smaller than lfamd_flash_attn_workspace()");
+    int rc;
+    if (!fa_check(true, d_Q, q_nb1, q_nb2, q_nb3, Ktype, d_K, k_nb1, k_nb2, k_nb3, Vtype, d_V, v_nb1, v_nb2, v_nb3, d_mask, mask_nb1, D, n_q, n_kv,
+                  n_head, n_head_kv, ne3, max_bias, d_dst, dst_nb1, dst_nb2, dst_nb3, d_workspace, workspace_bytes, flags, &rc))
+        return rc;
 
     fa_args a{};
     a.Q = (const uint8_t *)d_Q, a.K = (const uint8_t *)d_K, a.V = (const uint8_t *)d_V, a.mask = (const uint8_t *)d_mask;

@@ -60,10 +60,21 @@ void logf(const char *fmt, const char *a = "", const char *b = "") {
     fprintf(stderr, fmt, a, b);
 }
 
+// The one reader of this file's environment switches: on = set to a number other than 0 (INTEGRATION.md writes every one as "=1").  The
+// variable is read through the HOST's getenv from the linked table (the reference passes it across this boundary because the module's
+// libc is not the host's), through libc's only where the table has none; so nothing is read before ggml_cuda_link has stored the table
+// (the function-local statics below are first reached from calls that need a linked module).  value: the variable's text (a list).
+bool env_on(const char *name, const char **value = nullptr) {
+    const char *v = g_api && g_api->getenv ? g_api->getenv(name) : getenv(name);
+    if (value)
+        *value = v;
+    return v && atoi(v) != 0;
+}
+
 // What every mat-mul of the glue carries: the reference's AVX512 build of tinyBLAS_Q0, and — LFAMD_Q80_RELAXED=1 in the environment,
 // read once — the relaxed-order Q8_0 decode GEMV (lfamd_hip.h: LFAMD_FLAG_Q80_RELAXED; exact_only matrices override it).
 unsigned base_flags() {
-    static const unsigned relaxed = getenv("LFAMD_Q80_RELAXED") && atoi(getenv("LFAMD_Q80_RELAXED")) ? LFAMD_FLAG_Q80_RELAXED : 0u;
+    static const unsigned relaxed = env_on("LFAMD_Q80_RELAXED") ? LFAMD_FLAG_Q80_RELAXED : 0u;
     return LFAMD_FLAG_Q0_VREGS32 | relaxed;
 }
 
@@ -402,48 +413,55 @@ int resident_type(const struct ggml_tensor *a) {
     return lfamd_resident_type(a->type, (long)a->ne[0]);
 }
 
-// packed device copy of `rows` raw rows at `raw` (on the CURRENT device); kept under the raw address when `keep`
-// (type: the resident id, resident_type)
-const packed *get_packed_rows(void *&scratch, size_t &scratch_cap, int type, const uint8_t *raw, long rows, long cols, size_t row_bytes,
-                              bool keep, packed *tmp) {
-    const size_t need = lfamd_packed_size(type, rows, cols);
+// The packed-weight cache (g_mu held, on the CURRENT device): the packed image of `slices` raw matrices of rows x cols, slice_bytes
+// apart from `raw` on, back to back (slices == 1: a matrix, or a device's row slice; more: an expert stack).  type: the resident id
+// (resident_type).  keep: the image stays under the raw address until those bytes change (weights); else it is packed into the
+// scratch area of `ctx` and described in *tmp (ctx == nullptr: the split path, which always keeps).
+// exact_only: only the K-quant and Q8_0 batch bodies have a scaled-operand form whose range must be checked (the check synchronises
+// the stream) — a matrix over its rows; a stack, K-quants only, over every expert's rows rounded to the 32-row tiles (a Q8_0 expert
+// stack is not checked).
+const packed *get_packed_image(backend_ctx *ctx, bool keep, int type, const uint8_t *raw, long rows, long cols, size_t row_bytes, int slices,
+                               size_t slice_bytes, packed *tmp) {
+    const size_t one = lfamd_packed_size(type, rows, cols);
     if (keep) {
         auto it = g_packed.find(raw);
-        if (it != g_packed.end() && it->second.type == type && it->second.rows == rows && it->second.cols == cols &&
+        if (it != g_packed.end() && it->second.type == type && it->second.rows == rows * slices && it->second.cols == cols &&
             it->second.row_bytes == row_bytes)
             return &it->second;
     }
     packed p;
-    p.bytes = need, p.type = type, p.rows = rows, p.cols = cols, p.row_bytes = row_bytes;
+    p.bytes = one * slices, p.type = type, p.rows = rows * slices, p.cols = cols, p.row_bytes = row_bytes;
     if (keep) {
-        if (hipMalloc(&p.d, need ? need : 16) != hipSuccess)
+        if (hipMalloc(&p.d, p.bytes ? p.bytes : 16) != hipSuccess)
             return nullptr;
     } else {
-        if (!grow(scratch, scratch_cap, need))
+        if (!grow(ctx->scratch, ctx->scratch_cap, p.bytes))
             return nullptr;
-        p.d = scratch;
+        p.d = ctx->scratch;
     }
-    if (lfamd_pack_weights(type, rows, cols, raw, row_bytes, p.d, nullptr) != LFAMD_OK) {
-        if (keep)
-            (void)hipFree(p.d);
-        return nullptr;
-    }
-    // (only the K-quant and Q8_0 batch bodies have a scaled-operand form whose range must be checked; the check synchronises the stream)
-    const bool scaled_form = type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K || type == LFAMD_TYPE_Q8_0;
-    p.exact_only = scaled_form && lfamd_scaled_gemm_ok(type, rows, cols, p.d, nullptr) == 0;
+    for (int e = 0; e < slices; e++)
+        if (lfamd_pack_weights(type, rows, cols, raw + (size_t)e * slice_bytes, row_bytes, (uint8_t *)p.d + (size_t)e * one, nullptr) != LFAMD_OK) {
+            if (keep)
+                (void)hipFree(p.d);
+            return nullptr;
+        }
+    const bool kq = type == LFAMD_TYPE_Q4_K || type == LFAMD_TYPE_Q5_K || type == LFAMD_TYPE_Q6_K;
+    const bool scaled_form = kq || (type == LFAMD_TYPE_Q8_0 && slices == 1);
+    const long checked_rows = slices == 1 ? rows : (long)slices * ((rows + 31) / 32) * 32;
+    p.exact_only = scaled_form && lfamd_scaled_gemm_ok(type, checked_rows, cols, p.d, nullptr) == 0;
     if (keep)
         return &(g_packed[raw] = p);
     *tmp = p;
     return tmp;
 }
 
-// packed device copy of the (i02, i03) slice of src0
-const packed *get_packed(backend_ctx *ctx, const struct ggml_tensor *a, int64_t i02, int64_t i03, packed *tmp) {
-    const uint8_t *base = weight_bytes(a);
+// packed device copy of the (i02, i03) slice of src0, or (slices > 1) of the whole stack from that slice on
+const packed *get_packed(backend_ctx *ctx, const struct ggml_tensor *a, int64_t i02, int64_t i03, packed *tmp, int slices = 1) {
+    const uint8_t *base = weight_bytes(a); // (an expert stack of a row-split buffer stays whole on the first device)
     if (!base)
         return nullptr;
-    return get_packed_rows(ctx->scratch, ctx->scratch_cap, resident_type(a), base + i02 * a->nb[2] + i03 * a->nb[3], (long)a->ne[1],
-                           (long)a->ne[0], a->nb[1], in_weights_buffer(a), tmp);
+    return get_packed_image(ctx, in_weights_buffer(a), resident_type(a), base + i02 * a->nb[2] + i03 * a->nb[3], (long)a->ne[1], (long)a->ne[0],
+                            a->nb[1], slices, a->nb[2], tmp);
 }
 
 // The struct layouts this module reads (include/ggml_backend_lfamd.h, marked RECALLED: llama.cpp is not vendored in the reference
@@ -556,11 +574,8 @@ enum ggml_status run_mul_mat_split(backend_ctx *ctx, struct ggml_tensor *dst) {
                         return GGML_STATUS_FAILED;
                     B = ps.x, brb = (size_t)k * 4, C = (float *)ps.c, c_ld = rows;
                 }
-                packed tmp;
-                void *no_scratch = nullptr; // (split buffers hold weights: always kept)
-                size_t no_cap = 0;
                 const int rt = resident_type(a);
-                const packed *w = get_packed_rows(no_scratch, no_cap, rt, (const uint8_t *)e->d[d], rows, k, e->row_bytes, true, &tmp);
+                const packed *w = get_packed_image(nullptr, true, rt, (const uint8_t *)e->d[d], rows, k, e->row_bytes, 1, 0, nullptr);
                 if (!w)
                     return GGML_STATUS_ALLOC_FAILED;
                 void *&ws = own ? ctx->ws : ps.ws;
@@ -593,7 +608,7 @@ enum ggml_status run_mul_mat_split(backend_ctx *ctx, struct ggml_tensor *dst) {
 // indexes) — run_mul_mat's loop over the slices serves the node.  Any other refusal fails the graph.
 enum ggml_status run_batched(struct ggml_tensor *dst, decltype(&lfamd_mul_mat_batched) call, const char *name, long &calls) {
     const struct ggml_tensor *a = dst->src[0], *b = dst->src[1];
-    static const bool no_batched = getenv("LFAMD_BACKEND_NO_BATCHED") && atoi(getenv("LFAMD_BACKEND_NO_BATCHED"));
+    static const bool no_batched = env_on("LFAMD_BACKEND_NO_BATCHED");
     if (no_batched || !row_major(a) || is_split(a) || b->ne[2] * b->ne[3] <= 1 || a->ne[2] <= 0 || a->ne[3] <= 0 ||
         b->ne[2] % a->ne[2] != 0 || b->ne[3] % a->ne[3] != 0)
         return GGML_STATUS_ABORTED;
@@ -670,51 +685,12 @@ bool mul_mat_id_supported(const struct ggml_tensor *op) {
         return false;
     if (ids->nb[0] != 4 || !rows_aligned(ids, 4) || !rows_aligned(b, 16))
         return false;
-    // src1 is F32 here, and lfamd_mul_mat_id takes F32 activations for Q4_K / Q5_K / Q6_K experts only (other types want rows in
-    // their vec_dot format: LFAMD_ERR_UNSUPPORTED); batches of more than 4 tokens go through the routed launch and its limits
-    if (as->type != LFAMD_TYPE_Q4_K && as->type != LFAMD_TYPE_Q5_K && as->type != LFAMD_TYPE_Q6_K)
-        return false;
-    if (b->ne[2] > 4 && (as->ne[2] >= 255 || b->ne[2] * ids->ne[0] > 60 * 1024))
+    // src1 is F32 here: does lfamd_mul_mat_id take it for these experts (other types want rows in their vec_dot format), and for a
+    // batch that goes through the routed launch, within its limits?  More thinkers than experts the call refuses outright.
+    if (ids->ne[0] > as->ne[2] ||
+        !lfamd_mul_mat_id_takes_f32((int)as->type, (long)as->ne[0], (int)as->ne[2], (long)b->ne[2], (int)ids->ne[0], base_flags()))
         return false;
     return as->ne[0] % lfamd_blck_size(as->type) == 0 && lfamd_packed_size(as->type, (long)as->ne[1], (long)as->ne[0]) != 0;
-}
-
-// the whole expert stack packed back to back under the stack's address (g_mu held)
-const packed *get_packed_stack(backend_ctx *ctx, const struct ggml_tensor *as, packed *tmp) {
-    const long rows = (long)as->ne[1], cols = (long)as->ne[0];
-    const int experts = (int)as->ne[2], rt = resident_type(as);
-    const size_t one = lfamd_packed_size(rt, rows, cols);
-    const uint8_t *as_bytes = weight_bytes(as); // (an expert stack of a row-split buffer stays whole on the first device)
-    if (!as_bytes)
-        return nullptr;
-    const bool keep = in_weights_buffer(as);
-    auto it = g_packed.find(as_bytes);
-    if (keep && it != g_packed.end() && it->second.type == rt && it->second.rows == rows * experts && it->second.cols == cols)
-        return &it->second;
-    packed p;
-    p.bytes = one * experts, p.type = rt, p.rows = rows * experts, p.cols = cols, p.row_bytes = as->nb[1];
-    if (keep) {
-        if (hipMalloc(&p.d, p.bytes) != hipSuccess)
-            return nullptr;
-    } else {
-        if (!grow(ctx->scratch, ctx->scratch_cap, p.bytes))
-            return nullptr;
-        p.d = ctx->scratch;
-    }
-    for (int e = 0; e < experts; e++)
-        if (lfamd_pack_weights(rt, rows, cols, as_bytes + (size_t)e * as->nb[2], as->nb[1], (uint8_t *)p.d + (size_t)e * one,
-                               nullptr) != LFAMD_OK) {
-            if (keep)
-                (void)hipFree(p.d);
-            return nullptr;
-        }
-    // (K-quant stacks: rows of every expert rounded to the 32-row tiles; a Q8_0 expert stack is not checked)
-    const bool kq = as->type == LFAMD_TYPE_Q4_K || as->type == LFAMD_TYPE_Q5_K || as->type == LFAMD_TYPE_Q6_K;
-    p.exact_only = kq && lfamd_scaled_gemm_ok(as->type, (long)experts * ((rows + 31) / 32) * 32, cols, p.d, nullptr) == 0;
-    if (keep)
-        return &(g_packed[as_bytes] = p);
-    *tmp = p;
-    return tmp;
 }
 
 // `count` MUL_MAT_ID nodes over the same activations and routing table (count == 1: the plain node; 2: ffn_gate_exps +
@@ -732,7 +708,7 @@ enum ggml_status run_mul_mat_id(backend_ctx *ctx, struct ggml_tensor *const *dst
     unsigned flags = base_flags();
     for (int j = 0; j < count; j++) {
         packed tmp;
-        const packed *w = get_packed_stack(ctx, dsts[j]->src[0], &tmp);
+        const packed *w = get_packed(ctx, dsts[j]->src[0], 0, 0, &tmp, (int)dsts[j]->src[0]->ne[2]); // the whole expert stack
         if (!w)
             return GGML_STATUS_ALLOC_FAILED;
         wp[j] = w->d, rp[j] = (float *)dsts[j]->data;
@@ -769,7 +745,7 @@ enum ggml_status run_mul_mat_id(backend_ctx *ctx, struct ggml_tensor *const *dst
 //   MUL_MAT: plain 2-D weights of this device, the same src1 tensor, at most 8 activation rows -> lfamd_mul_mat_multi_types
 //   MUL_MAT_ID: the same src1 and ids, one type and shape, at most 4 tokens                    -> lfamd_mul_mat_id_multi
 int sibling_run(const struct ggml_cgraph *g, int i) {
-    static const bool off = getenv("LFAMD_BACKEND_NO_SIBLING_FUSION") && atoi(getenv("LFAMD_BACKEND_NO_SIBLING_FUSION"));
+    static const bool off = env_on("LFAMD_BACKEND_NO_SIBLING_FUSION");
     const struct ggml_tensor *first = g->nodes[i];
     const struct ggml_tensor *a0 = first->src[0], *b0 = first->src[1];
     if (off || !a0 || !b0)
@@ -838,54 +814,74 @@ enum ggml_status run_mul_mat_siblings(backend_ctx *ctx, struct ggml_tensor *cons
     return GGML_STATUS_SUCCESS;
 }
 
+// ------------------------------------------------------------------ what supports_op asks of the library
+// An operator's acceptance is the library's own argument check (lfamd_flash_attn_check, lfamd_cpy_check: the table the entry point
+// runs first) plus what only ggml's structs show.  The node becomes the call's argument list in ONE place per operator (fa_call_of,
+// cpy_call_of), used by supports_op and by graph_compute: the two cannot describe it differently, and a node is not accepted here and
+// then failed there over its layout.  supports_op may be asked before a tensor has its address: it passes LFAMD_CHECK_UNPLACED and, as
+// the address, the bits that decide its alignment — the data pointer, if there is one, and a view's offset.
+const void *address_of(const struct ggml_tensor *t, bool placed) {
+    return placed ? t->data : (const void *)((uintptr_t)t->data | t->view_offs);
+}
+
 // ------------------------------------------------------------------ GGML_OP_FLASH_ATTN_EXT
 // src[0] = Q f32 [D, n_q, n_head, ne3], src[1] = K f16 [D, n_kv, n_head_kv, ne3], src[2] = V f16 (not transposed), src[3] = mask f16
 // [n_kv, >= n_q] or NULL, dst f32 [D, n_head, n_q, ne3]; op_params: scale (f32) at [0], max_bias (f32) at [1], precision at [2]
-// (ggml-cuda.cu.patch:8352-8353, :9987).  The call takes bases and strides that are multiples of 16 (include/lfamd_hip.h), a view's
-// offset included: supports_op may be asked before the tensor has its address (rows_aligned's test, on every stride).
-bool fa_aligned(const struct ggml_tensor *t) {
-    return ((uintptr_t)t->data | t->view_offs | t->nb[1] | t->nb[2] | t->nb[3]) % 16 == 0;
+// (ggml-cuda.cu.patch:8352-8353, :9987).
+struct fa_call { // lfamd_flash_attn's arguments, but the workspace
+    const void *q, *k, *v, *mask, *dst;
+    const size_t *q_nb, *k_nb, *v_nb, *dst_nb; // the tensors' nb[]
+    size_t mask_nb1;
+    int ktype, vtype;
+    long D, n_q, n_kv, n_head, n_head_kv, ne3;
+    float scale, max_bias;
+};
+
+fa_call fa_call_of(const struct ggml_tensor *op, bool placed) {
+    const struct ggml_tensor *q = op->src[0], *k = op->src[1], *v = op->src[2], *mask = op->src[3];
+    fa_call c{address_of(q, placed), address_of(k, placed), address_of(v, placed), nullptr, address_of(op, placed), q->nb, k->nb, v->nb, op->nb,
+              mask ? mask->nb[1] : 0, (int)k->type, (int)v->type, (long)q->ne[0], (long)q->ne[1], (long)k->ne[1], (long)q->ne[2], (long)k->ne[2],
+              (long)q->ne[3], 0.0f, 0.0f};
+    // (a mask without an address yet is still a mask to the check: a bit above the alignment it asks for stands for the address)
+    if (mask)
+        c.mask = placed ? mask->data : (const void *)((uintptr_t)address_of(mask, false) | 16);
+    memcpy(&c.scale, &op->op_params[0], sizeof(float));
+    memcpy(&c.max_bias, &op->op_params[1], sizeof(float));
+    return c;
 }
 
+// beside lfamd_flash_attn_check: the switch, the ggml types and nb[0], the extents of K / V / dst / mask against Q, a contiguous dst
+// and the precision — what the call's argument list does not carry
 bool flash_attn_supported(const struct ggml_tensor *op) {
-    const char *off = g_api->getenv ? g_api->getenv("LFAMD_BACKEND_NO_FLASH_ATTN") : nullptr;
-    if (off && atoi(off))
+    if (env_on("LFAMD_BACKEND_NO_FLASH_ATTN"))
         return false;
     const struct ggml_tensor *q = op->src[0], *k = op->src[1], *v = op->src[2], *mask = op->src[3];
-    if (!q || !k || !v || q->type != LFAMD_TYPE_F32 || k->type != LFAMD_TYPE_F16 || v->type != LFAMD_TYPE_F16 || op->type != LFAMD_TYPE_F32)
-        return false;
-    if (q->nb[0] != 4 || k->nb[0] != 2 || v->nb[0] != 2 || !g_api->ggml_is_contiguous(op))
+    if (!q || !k || !v || q->type != LFAMD_TYPE_F32 || op->type != LFAMD_TYPE_F32 || !row_major(q) || !row_major(k) || !row_major(v) ||
+        !g_api->ggml_is_contiguous(op))
         return false;
     const int64_t D = q->ne[0], n_q = q->ne[1], n_head = q->ne[2], ne3 = q->ne[3], n_kv = k->ne[1], n_head_kv = k->ne[2];
-    if ((D != 64 && D != 128) || k->ne[0] != D || v->ne[0] != D || v->ne[1] != n_kv || v->ne[2] != n_head_kv || k->ne[3] != ne3 || v->ne[3] != ne3)
-        return false;
-    if (n_kv < 1 || n_head_kv < 1 || n_head % n_head_kv != 0 || n_head * ne3 > 65535 || (n_q + 127) / 128 > 65535)
+    if (k->ne[0] != D || v->ne[0] != D || v->ne[1] != n_kv || v->ne[2] != n_head_kv || k->ne[3] != ne3 || v->ne[3] != ne3)
         return false;
     if (op->ne[0] != D || op->ne[1] != n_head || op->ne[2] != n_q || op->ne[3] != ne3)
         return false;
-    if (mask && (mask->type != LFAMD_TYPE_F16 || mask->nb[0] != 2 || mask->ne[0] < n_kv || mask->ne[1] < n_q || mask->ne[2] != 1 ||
-                 mask->ne[3] != 1 || mask->nb[1] < (size_t)n_kv * 2 || ((uintptr_t)mask->data | mask->view_offs | mask->nb[1]) % 2 != 0))
+    if (mask && (mask->type != LFAMD_TYPE_F16 || !row_major(mask) || mask->ne[0] < n_kv || mask->ne[1] < n_q || mask->ne[2] != 1 || mask->ne[3] != 1))
         return false;
-    float max_bias;
-    memcpy(&max_bias, &op->op_params[1], sizeof(float));
-    if (max_bias != 0.0f || op->op_params[2] != 0 /* GGML_PREC_DEFAULT */)
+    if (op->op_params[2] != 0 /* GGML_PREC_DEFAULT */)
         return false;
-    return fa_aligned(q) && fa_aligned(k) && fa_aligned(v) && fa_aligned(op);
+    const fa_call c = fa_call_of(op, false);
+    return lfamd_flash_attn_check((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v,
+                                  c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.max_bias,
+                                  (const float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], nullptr, 0, LFAMD_CHECK_UNPLACED) == LFAMD_OK;
 }
 
 // ONE lfamd_flash_attn on the tensors' own pointers and nb[]
 enum ggml_status run_flash_attn(backend_ctx *ctx, struct ggml_tensor *dst) {
-    const struct ggml_tensor *q = dst->src[0], *k = dst->src[1], *v = dst->src[2], *mask = dst->src[3];
-    const long D = (long)q->ne[0], n_q = (long)q->ne[1], n_head = (long)q->ne[2], ne3 = (long)q->ne[3], n_kv = (long)k->ne[1], n_head_kv = (long)k->ne[2];
-    float scale, max_bias;
-    memcpy(&scale, &dst->op_params[0], sizeof(float));
-    memcpy(&max_bias, &dst->op_params[1], sizeof(float));
-    if (!grow(ctx->ws, ctx->ws_cap, lfamd_flash_attn_workspace(D, n_q, n_kv, n_head, n_head_kv, ne3)))
+    const fa_call c = fa_call_of(dst, true);
+    if (!grow(ctx->ws, ctx->ws_cap, lfamd_flash_attn_workspace(c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3)))
         return GGML_STATUS_ALLOC_FAILED;
-    const int rc = lfamd_flash_attn((const float *)q->data, q->nb[1], q->nb[2], q->nb[3], (int)k->type, k->data, k->nb[1], k->nb[2], k->nb[3],
-                                    (int)v->type, v->data, v->nb[1], v->nb[2], v->nb[3], mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, D, n_q,
-                                    n_kv, n_head, n_head_kv, ne3, scale, max_bias, (float *)dst->data, dst->nb[1], dst->nb[2], dst->nb[3],
-                                    ctx->ws, ctx->ws_cap, 0u, nullptr);
+    const int rc = lfamd_flash_attn((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v,
+                                    c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.scale,
+                                    c.max_bias, (float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], ctx->ws, ctx->ws_cap, 0u, nullptr);
     if (rc != LFAMD_OK) {
         logf("ggml_backend_lfamd: %s: %s\n", "lfamd_flash_attn", lfamd_last_error());
         return GGML_STATUS_FAILED;
@@ -897,59 +893,48 @@ enum ggml_status run_flash_attn(backend_ctx *ctx, struct ggml_tensor *dst) {
 // ------------------------------------------------------------------ GGML_OP_CPY
 // src[0] = the source, src[1] = the destination (a view into the K / V cache; the node itself is a view of src[1]); element i of the
 // flattened source becomes element i of the flattened destination (reference: ggml_cuda_cpy, ggml-cuda.cu.patch:5150-5260, its
-// supports_op clause :19284-19332).  Accepted is what lfamd_cpy takes (include/lfamd_hip.h: the type pairs, the block-type conditions,
-// the alignment — tested on the view's offset too, as fa_aligned does) on operands in this device's ORDINARY buffers: a tensor that has
-// a buffer (its own, or its view source's before the view is allocated) has this device's; one without a buffer yet is a graph
-// intermediate the scheduler then allocates here.  Never a split buffer's placeholder addresses.
-bool cpy_type_is_block(int t) {
-    return t == LFAMD_TYPE_Q8_0 || t == LFAMD_TYPE_Q4_0 || t == LFAMD_TYPE_Q4_1 || t == LFAMD_TYPE_Q5_0 || t == LFAMD_TYPE_Q5_1 || t == LFAMD_TYPE_IQ4_NL;
+// supports_op clause :19284-19332).
+struct cpy_call { // lfamd_cpy's arguments
+    const void *src, *dst;
+    int src_type, dst_type;
+    long src_ne[4], dst_ne[4];
+    const size_t *src_nb, *dst_nb; // the tensors' nb[]
+};
+
+cpy_call cpy_call_of(const struct ggml_tensor *op, bool placed) {
+    const struct ggml_tensor *a = op->src[0], *b = op->src[1];
+    cpy_call c{address_of(a, placed), address_of(b, placed), (int)a->type, (int)b->type, {}, {}, a->nb, b->nb};
+    for (int i = 0; i < 4; i++)
+        c.src_ne[i] = (long)a->ne[i], c.dst_ne[i] = (long)b->ne[i];
+    return c;
 }
 
+// Operands in this device's ORDINARY buffers: a tensor that has a buffer (its own, or its view source's before the view is allocated)
+// has this device's; one without a buffer yet is a graph intermediate the scheduler then allocates here.  Never a split buffer's
+// placeholder addresses.
 bool cpy_operand_ok(const struct ggml_tensor *t, int device) {
     const struct ggml_backend_buffer *b = t->buffer ? t->buffer : t->view_src ? t->view_src->buffer : nullptr;
-    if (b && (b->iface.get_name != buf_get_name || ((const buffer_ctx *)b->context)->dev != device))
-        return false;
-    const size_t align = t->type == LFAMD_TYPE_F32 ? 4 : 2;
-    if (((uintptr_t)t->data | t->view_offs | t->nb[0] | t->nb[1] | t->nb[2] | t->nb[3]) % align != 0)
-        return false;
-    if (t->nb[0] == (size_t)lfamd_type_size(t->type))
-        for (int i = 1; i < 4; i++)
-            if (t->ne[i] > 1 && t->nb[i] < lfamd_row_size(t->type, (long)t->ne[0]))
-                return false;
-    return true;
+    return !b || (b->iface.get_name == buf_get_name && ((const buffer_ctx *)b->context)->dev == device);
 }
 
+// beside lfamd_cpy_check: the switch, types the host knows, ggml's own element counts, and the operands' buffers
 bool cpy_supported(ggml_backend_t backend, const struct ggml_tensor *op) {
-    const char *off = g_api->getenv ? g_api->getenv("LFAMD_BACKEND_NO_CPY") : nullptr;
-    if (off && atoi(off))
+    if (env_on("LFAMD_BACKEND_NO_CPY"))
         return false;
     const struct ggml_tensor *a = op->src[0], *b = op->src[1];
-    if (!a || !b || !type_ok(a->type) || !type_ok(b->type))
-        return false;
-    const bool blocks = cpy_type_is_block(b->type);
-    if (a->type == LFAMD_TYPE_F32 ? !(b->type == LFAMD_TYPE_F32 || b->type == LFAMD_TYPE_F16 || blocks)
-                                  : !(a->type == b->type && (a->type == LFAMD_TYPE_F16 || blocks)))
-        return false;
-    const int64_t n = g_api->ggml_nelements(a);
-    if (n != g_api->ggml_nelements(b) || n > 0x7fffffffLL)
-        return false;
-    for (int i = 0; i < 4; i++)
-        if (a->ne[i] < 0 || b->ne[i] < 0 || a->ne[i] > 0x7fffffffLL || b->ne[i] > 0x7fffffffLL)
-            return false;
-    if (blocks && (a->ne[0] % 32 != 0 || b->ne[0] % 32 != 0 || b->nb[0] != (size_t)lfamd_type_size(b->type) ||
-                   a->nb[0] != (size_t)lfamd_type_size(a->type)))
+    if (!a || !b || !type_ok(a->type) || !type_ok(b->type) || g_api->ggml_nelements(a) != g_api->ggml_nelements(b))
         return false;
     const int device = ((backend_ctx *)backend->context)->device;
-    return cpy_operand_ok(a, device) && cpy_operand_ok(b, device);
+    if (!cpy_operand_ok(a, device) || !cpy_operand_ok(b, device))
+        return false;
+    const cpy_call c = cpy_call_of(op, false);
+    return lfamd_cpy_check(c.src_type, c.src, c.src_ne, c.src_nb, c.dst_type, c.dst, c.dst_ne, c.dst_nb, LFAMD_CHECK_UNPLACED) == LFAMD_OK;
 }
 
 // ONE lfamd_cpy: src[1]'s storage written on its own ne / nb
 enum ggml_status run_cpy(backend_ctx *ctx, struct ggml_tensor *dst) {
-    const struct ggml_tensor *a = dst->src[0], *b = dst->src[1];
-    long a_ne[4], b_ne[4];
-    for (int i = 0; i < 4; i++)
-        a_ne[i] = (long)a->ne[i], b_ne[i] = (long)b->ne[i];
-    if (lfamd_cpy((int)a->type, a->data, a_ne, a->nb, (int)b->type, b->data, b_ne, b->nb, 0u, nullptr) != LFAMD_OK) {
+    const cpy_call c = cpy_call_of(dst, true);
+    if (lfamd_cpy(c.src_type, c.src, c.src_ne, c.src_nb, c.dst_type, (void *)c.dst, c.dst_ne, c.dst_nb, 0u, nullptr) != LFAMD_OK) {
         logf("ggml_backend_lfamd: %s: %s\n", "lfamd_cpy", lfamd_last_error());
         return GGML_STATUS_FAILED;
     }
@@ -963,7 +948,7 @@ GGML_CALL const char *be_get_name(ggml_backend_t) {
 }
 GGML_CALL void be_free(ggml_backend_t backend) {
     backend_ctx *c = (backend_ctx *)backend->context;
-    if (g_api && g_api->getenv && g_api->getenv("LFAMD_BACKEND_STATS"))
+    if (env_on("LFAMD_BACKEND_STATS"))
         fprintf(stderr, "ggml_backend_lfamd: %ld sibling calls\nggml_backend_lfamd: %ld batched calls\nggml_backend_lfamd: %ld block-K calls\n"
                         "ggml_backend_lfamd: %ld flash-attn calls\nggml_backend_lfamd: %ld cpy calls\n",
                 c->sibling_calls, c->batched_calls, c->block_k_calls, c->flash_attn_calls, c->cpy_calls);
@@ -1113,7 +1098,8 @@ GGML_CALL bool ggml_cuda_link(const struct ggml_backend_api *backend_api) {
     // repeat: two logical devices on one GPU, the single-GPU rehearsal of the multi-device paths); gfx950 only
     const int visible = lfamd_device_count();
     g_ndev = 0;
-    const char *want = backend_api->getenv ? backend_api->getenv("LFAMD_BACKEND_DEVICES") : nullptr;
+    const char *want = nullptr;
+    (void)env_on("LFAMD_BACKEND_DEVICES", &want);
     auto add = [&](int ordinal) {
         hipDeviceProp_t p;
         if (ordinal < 0 || ordinal >= visible || g_ndev >= LFAMD_MAX_DEVS || hipGetDeviceProperties(&p, ordinal) != hipSuccess)
@@ -1170,10 +1156,7 @@ GGML_CALL ggml_backend_buffer_type_t ggml_backend_cuda_buffer_type(int device) {
     // LFAMD_BACKEND_MATRICES_ONLY=1: the per-layer ("offload") buffer type is host memory, so that norm weights, the KV cache
     // and compute buffers stay with the CPU backend; matrices reach the device through the split buffer type below
     // (llama.cpp --split-mode row: buft_matrix).  INTEGRATION.md section 2.
-    static const bool matrices_only = [] {
-        const char *e = getenv("LFAMD_BACKEND_MATRICES_ONLY");
-        return e && *e && *e != '0';
-    }();
+    static const bool matrices_only = env_on("LFAMD_BACKEND_MATRICES_ONLY");
     return matrices_only ? g_api->ggml_backend_cpu_buffer_type() : &g_bufts[device];
 }
 

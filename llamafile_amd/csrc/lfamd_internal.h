@@ -77,7 +77,8 @@ static inline lfamd_image lfamd_image_of(int id, long cols) {
 static inline bool lfamd_type_known(int id) { // (at every row length: cols only picks between a type's layouts)
     return lfamd_image_of(id, 0).ly != LY_NONE;
 }
-// the K cache types lfamd_mul_mat_batched_q reads as raw GGUF rows (the 32-block types; an id with LFAMD_TYPE_PAD256 is not one)
+// the K cache types: what lfamd_mul_mat_batched_q reads as raw GGUF rows and lfamd_cpy writes (the 32-block types; an id with
+// LFAMD_TYPE_PAD256 is not one).  The one definition of the list: cpy.hip and the ggml backend ask it too.
 static inline bool lfamd_block_k_type(int id) {
     return id == LFAMD_TYPE_Q8_0 || id == LFAMD_TYPE_Q4_0 || id == LFAMD_TYPE_Q4_1 || id == LFAMD_TYPE_Q5_0 || id == LFAMD_TYPE_Q5_1 ||
            id == LFAMD_TYPE_IQ4_NL;

@@ -376,6 +376,9 @@ static int mode_decline(ggml_backend_t be, ggml_backend_buffer_type_t buft, cons
         IDS.type = LFAMD_TYPE_F32;
     } else if (!strcmp(what, "id_stack_noncontig")) {
         W.nb[2] += 256, W.nb[3] = W.nb[2] * experts;
+    } else if (!strcmp(what, "id_more_thinkers_than_experts")) { /* five routes per token into four experts: lfamd_mul_mat_id refuses it */
+        IDS.ne[0] = experts + 1, IDS.nb[1] = IDS.nb[0] * IDS.ne[0], IDS.nb[2] = IDS.nb[3] = IDS.nb[1] * n;
+        OUT.ne[1] = experts + 1, OUT.nb[2] = OUT.nb[1] * OUT.ne[1], OUT.nb[3] = OUT.nb[2] * n;
     } else {
         fprintf(stderr, "unknown case %s\n", what);
         return 2;

@@ -7,7 +7,8 @@
  *       control (F16 K / V, D = 128, F16 mask), control_nomask, d96, max_bias, prec_f32, q4_0_k, view_offs (Q a view 8 bytes into
  *       its parent, no address yet), control_view_offs16; and, each the control node with one change: q_f16, v_f32, dst_f16, q_nb0,
  *       dst_strided, v_ne1, v_ne2, k_ne3, heads_3kv (8 heads on 3 KV heads), dst_ne1, mask_f32, mask_ne0, mask_ne1, mask_ne2,
- *       mask_nb1_odd, k_nb1_8 (not a multiple of 16), slices (n_head * ne3 = 65536)
+ *       mask_nb1_odd, k_nb1_8 (not a multiple of 16), slices (n_head * ne3 = 65536), q_nb1_short and k_nb1_short (rows 256 / 128 bytes
+ *       apart: multiples of 16, half a row of D = 128)
  *   fattn_host <module.so> run <Q.bin> <K.bin> <V.bin> <mask.bin> <out.bin> [<n_q> <n_kv> <mask rows> [<Q.bin> ... <mask rows>]]
  *       one graph_compute of one grouped-query node per group of arguments, in their order: 2 KV heads x 4, D = 128, n_q = 17,
  *       n_kv = 65 and a mask of 32 rows where the three numbers are not given; Q memory [n_q][n_head][D], K / V the permuted cache
@@ -104,6 +105,10 @@ static int fa_decline(ggml_backend_t be, ggml_backend_buffer_type_t buft, const 
         M.nb[1] = 2 * N_KV + 1;
     } else if (!strcmp(what, "k_nb1_8")) {
         K.nb[1] += 8;
+    } else if (!strcmp(what, "q_nb1_short")) {
+        Q.nb[1] = 256; /* a row of 128 floats is 512 bytes */
+    } else if (!strcmp(what, "k_nb1_short")) {
+        K.nb[1] = 128; /* a row of 128 halves is 256 bytes */
     } else if (!strcmp(what, "slices")) {
         Q.ne[3] = K.ne[3] = V.ne[3] = OUT.ne[3] = 8192; /* 8 heads x 8192 = 65536 */
     } else {

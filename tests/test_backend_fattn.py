@@ -56,9 +56,11 @@ def test_a_host_without_the_name_links_and_is_never_offered_the_op(gpu, host_exe
     assert supports(host_exe, "control_nomask", FATTN_HOST_NO_NAME="1") == "declined"
 
 
-# each the accepted 'control' node with one change: the clauses of flash_attn_supported (csrc/ggml_backend_lfamd.hip) in their order
+# each the accepted 'control' node with one change: what flash_attn_supported (csrc/ggml_backend_lfamd.hip) reads from ggml's structs,
+# and what it leaves to lfamd_flash_attn_check (heads_3kv, slices, mask_nb1_odd, k_nb1_8; q_nb1_short and k_nb1_short: rows half a row
+# apart, multiples of 16 — nodes that graph_compute would fail)
 ONE_CHANGE = ["q_f16", "v_f32", "dst_f16", "q_nb0", "dst_strided", "v_ne1", "v_ne2", "k_ne3", "heads_3kv", "slices", "dst_ne1", "mask_f32",
-              "mask_ne0", "mask_ne1", "mask_ne2", "mask_nb1_odd", "k_nb1_8"]
+              "mask_ne0", "mask_ne1", "mask_ne2", "mask_nb1_odd", "k_nb1_8", "q_nb1_short", "k_nb1_short"]
 
 
 @pytest.mark.gpu

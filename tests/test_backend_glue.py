@@ -428,7 +428,7 @@ def test_float_weights_take_f32_rows_at_any_stride(gpu, oracle, host_exe, tmp_pa
 
 # every declined case alters one thing of an accepted node; the control beside it alters the same thing harmlessly
 DECLINED = ["f16_src1", "dst_noncontig", "f16w_src0_transposed", "k_mismatch", "k_not_block", "id_ids_not_i32", "id_stack_noncontig",
-            "src1_row_stride", "src1_base", "src1_view_offs", "id_src1_base", "id_q4_0_experts"]
+            "src1_row_stride", "src1_base", "src1_view_offs", "id_src1_base", "id_q4_0_experts", "id_more_thinkers_than_experts"]
 ACCEPTED = ["control_mm", "control_id", "control_f16w", "control_k_block", "control_f16w_src1_row_stride", "control_src1_row_stride16",
             "control_src1_base16", "control_id_src1_base16", "control_src1_view_offs16"]
 

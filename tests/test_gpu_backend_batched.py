@@ -59,6 +59,21 @@ def test_attention_node_is_one_batched_call(gpu, host_exe, tmp_path, group, n):
             check_f16_rule(got[h], K[:, h // group, :], Q[:, h, :], n)
 
 
+@pytest.mark.gpu
+def test_the_switch_is_on_for_a_number_other_than_zero(gpu, host_exe, tmp_path):
+    """The truth rule of every LFAMD_* switch of the backend (env_on): LFAMD_BACKEND_NO_BATCHED=0 leaves the batched call in, =1
+    takes it out."""
+    k, n_kv, kv_heads, heads, n = 128, 96, 2, 2, 1
+    rng = np.random.default_rng(7)
+    K = (rng.random((n_kv, kv_heads, k), dtype=np.float32) * 2 - 1).astype(np.float16)
+    Q = (rng.random((n, heads, k), dtype=np.float32) * 2 - 1).astype(np.float32)
+    kp, qp, op = tmp_path / "k.bin", tmp_path / "q.bin", tmp_path / "o.bin"
+    K.tofile(kp), Q.tofile(qp)
+    for value, calls in (("0", 2), ("1", 0)):
+        r = run_host(host_exe, ["attn", k, n_kv, kv_heads, heads, n, kp, qp, op], {"LFAMD_BACKEND_NO_BATCHED": value})
+        assert f"ggml_backend_lfamd: {calls} batched calls" in r.stderr, (value, r.stderr)
+
+
 def _mulmat(host_exe, tmp_path, t, m, k, n, nb2):
     W = synth.random_weights(t, m, k, 7)
     x = synth.random_activations(n * nb2, k, 8)
