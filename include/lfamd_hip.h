@@ -553,14 +553,14 @@ int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long k, size_t a
  * Checks, before any device call and in this order (lfamd_flash_attn_check: the same table, exported — below):
  *   1. a negative dimension (D, n_q, n_kv, n_head, n_head_kv, ne3)                          -> LFAMD_ERR_INVALID
  *   2. n_q, n_head or ne3 == 0 -> LFAMD_OK, nothing launched, no pointer looked at
- *   3. Ktype or Vtype is not LFAMD_TYPE_F16 (quantised K / V: refused; the parameters exist so that the block types can follow);
+ *   3. Ktype or Vtype is not LFAMD_TYPE_F16 (quantised K / V: refused here; Q8_0 and Q4_0 caches are lfamd_flash_attn_q's, below);
  *      D is not 64 or 128; max_bias != 0 (ALiBi: refused); more than 65535 slices (n_head * ne3: a grid dimension) or 128-row query
  *      blocks; n_kv == 0                                                                    -> LFAMD_ERR_UNSUPPORTED
  *   4. a NULL pointer other than the mask or a zero-size workspace; n_head_kv < 1 or n_head % n_head_kv != 0; a Q / K / V / dst base
  *      or stride that is not a multiple of 16; a mask base or mask_nb1 that is not a multiple of 2, or mask_nb1 < 2 n_kv; k_nb1 or
  *      v_nb1 < 2 D, q_nb1 < 4 D or dst_nb1 < 4 D; flags != 0 (reserved)                       -> LFAMD_ERR_INVALID
  *   5. workspace_bytes < lfamd_flash_attn_workspace(...)                                    -> LFAMD_ERR_WORKSPACE
- * Not served, by design (a host declines the node): quantised K / V, ALiBi, GGML_PREC_F32 (the n_q > 8 route rounds Q and p to
+ * Not served, by design (a host declines the node): quantised K / V (by this call: see lfamd_flash_attn_q), ALiBi, GGML_PREC_F32 (the n_q > 8 route rounds Q and p to
  * f16), head sizes other than 64 / 128, logit soft-capping (the call has no parameter for it).
  * lfamd_flash_attn_check is that list by itself — the call's arguments without scale and stream, no device call, host-only: the code
  * lfamd_flash_attn would answer before it launches (LFAMD_OK: the call passes, or is empty), lfamd_last_error() set the same way.
@@ -585,6 +585,53 @@ int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
                      float scale, float max_bias,
                      float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
                      void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream);
+
+/* ---- GGML_OP_FLASH_ATTN_EXT on a Q8_0 / Q4_0 K and V cache (-fa -ctk q8_0 -ctv q8_0, or q4_0) --------------------
+ * lfamd_flash_attn for a cache of 32-blocks, an entry point of its own as lfamd_mul_mat_batched_q is beside lfamd_mul_mat_batched
+ * (csrc/flash_attn.hip: the same kernels, instantiated on the operand types; reference: the stock pairs of ggml_cuda_flash_attn_ext,
+ * ggml-cuda.cu.patch:8240-8265, dispatch :9930-9980).  The argument list, semantics, shapes, strides, mask, dst layout, domain, the
+ * two routes picked by n_q alone, the workspace (lfamd_flash_attn_workspace, unchanged: the types do not enter it) and the bit
+ * guarantees (a row's bits are a function of its own operands, D, n_kv and the pair alone; many heads give the bits of calls on one
+ * head each; asynchronous, capturable, no atomics, no allocation) are lfamd_flash_attn's.  What differs:
+ *   Pairs: (Ktype, Vtype) is (Q8_0, Q8_0) or (Q4_0, Q4_0).  Everything else — F16 on either side, mixed pairs, Q4_1 / Q5_0 / Q5_1 /
+ *          IQ4_NL, the K-quants — is LFAMD_ERR_UNSUPPORTED; for (F16, F16) the message names lfamd_flash_attn.
+ *   Rows:  a K / V row is D / 32 blocks {f16 d, payload}, 34 bytes each for Q8_0 (32 int8 codes) and 18 for Q4_0 (element j < 16 is
+ *          the low nibble of payload byte j, element j + 16 its high nibble; the value is d * (nibble - 8)): the bytes lfamd_cpy
+ *          stores.  Row (i3, hk, t) at + i3 * nb3 + hk * nb2 + t * nb1.  A block lies on a 2-byte boundary and no better: K / V bases
+ *          and strides are multiples of 2 (not 16), k_nb1 / v_nb1 >= D / 32 * the block size.  Q and dst keep their 16-byte rule.
+ *   Memory contract: no byte outside the D / 32 blocks of rows 0 .. n_kv - 1 of K or V is read (a payload is read by dword loads
+ *          off their boundary, exactly its own bytes and, in front of them, bytes of the same block).
+ *   Domain, in addition: every d * code is finite in f16 (it is for any cache lfamd_cpy wrote from values inside f16's range).
+ * Arithmetic:
+ *   n_q <= 8: a K / V element is f32(d) * (float)code, which is exact in f32; everything from there is lfamd_flash_attn's n_q <= 8
+ *             route (f32 fmaf dots, log2-unit scores, four keys per online-softmax step, the wave-order merge, the same workspace
+ *             records and the same merge of the chunks).  Q is NOT quantised: ggml's CPU path and the reference's vector kernels
+ *             quantise Q to Q8_0 / Q8_1 first; this route does not, and is the more accurate for it.
+ *   n_q > 8:  the 64-key K and V tiles are written to on-chip memory as f16, each element f16(d * code) rounded once to nearest
+ *             even; from there the arithmetic is lfamd_flash_attn's n_q > 8 route, instruction for instruction.  THE RESULT IS BIT
+ *             FOR BIT THAT OF lfamd_flash_attn ON AN F16 CACHE HOLDING f16(d * code).  Limits: this route does not use the int8
+ *             matrix cores with a quantised Q; and the f16 rounding of d * code is its property — 2^-11 relative, far below the
+ *             cache's own quantisation step (2^-8 of a block's largest value for Q8_0); DESIGN.md section 31 has the measured distance
+ *             from the f64 value on the exact block values.
+ * Checks: lfamd_flash_attn's five steps in their order, messages prefixed "lfamd_flash_attn_q:".  Step 3's first clause is the pair
+ * rule above; step 4's alignment clause is two — a Q / dst base or stride that is not a multiple of 16, then a K / V base or stride
+ * that is not a multiple of 2; step 4's row-stride clause takes k_nb1 / v_nb1 against the row of blocks.  lfamd_flash_attn_q_check
+ * is that list by itself and takes LFAMD_CHECK_UNPLACED exactly as lfamd_flash_attn_check does; lfamd_flash_attn_q calls it first. */
+int lfamd_flash_attn_q_check(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
+                             int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,
+                             int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
+                             const void *d_mask, size_t mask_nb1,
+                             long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3, float max_bias,
+                             const float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
+                             const void *d_workspace, size_t workspace_bytes, unsigned flags);
+int lfamd_flash_attn_q(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3,
+                       int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,
+                       int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
+                       const void *d_mask, size_t mask_nb1,
+                       long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3,
+                       float scale, float max_bias,
+                       float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
+                       void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream);
 
 /* ---- GGML_OP_CPY: the store into an offloaded K / V cache, and the same-type moves of its defragmentation ----------
  * What a llama.cpp graph holds per layer to fill the cache: src = the F32 k_cur / v_cur, dst = a view into the cache tensor

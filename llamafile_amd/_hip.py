@@ -25,7 +25,7 @@ TYPE_STAGED_Q8K = 0x1000  # the int8 batch body's staged activation image (lfamd
 TYPE_STAGED_SCALED = 0x1001  # the scaled-operand f16 batch bodies' staged activation image
 TYPE_STAGED_B32 = 0x1002  # the 32-block batch bodies' staged activation image (Q8_0 / Q8_1-quantised activations)
 TYPE_STAGED_Q80 = 0x1003  # the Q8_0-weight loader-wave batch body's staged activation image
-CHECK_UNPLACED = 0x40000000  # lfamd_flash_attn_check / lfamd_cpy_check: the tensors have no addresses yet (lfamd_hip.h)
+CHECK_UNPLACED = 0x40000000  # lfamd_flash_attn_check / lfamd_flash_attn_q_check / lfamd_cpy_check: the tensors have no addresses yet (lfamd_hip.h)
 TYPE_PAD256 = 0x2000  # layout modifier OR-ed into a legacy 32-block weight type: the tile image with the last super-block padded
 
 
@@ -88,6 +88,10 @@ _SIGS = {
                               C.c_float, C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u, _vp]),
     "lfamd_flash_attn_check": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
                                     C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u]),
+    "lfamd_flash_attn_q": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
+                                C.c_float, C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u, _vp]),
+    "lfamd_flash_attn_q_check": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
+                                      C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u]),
     "lfamd_cpy": (_i, [_i, _vp, C.POINTER(_l), C.POINTER(_sz), _i, _vp, C.POINTER(_l), C.POINTER(_sz), _u, _vp]),
     "lfamd_cpy_check": (_i, [_i, _vp, C.POINTER(_l), C.POINTER(_sz), _i, _vp, C.POINTER(_l), C.POINTER(_sz), _u]),
     "lfamd_comm_unique_id": (_i, [_vp]),

@@ -1,4 +1,5 @@
-// flash_attn.hip — lfamd_flash_attn: GGML_OP_FLASH_ATTN_EXT on an F16 K / V cache in one fused launch (include/lfamd_hip.h).
+// flash_attn.hip — lfamd_flash_attn: GGML_OP_FLASH_ATTN_EXT on an F16 K / V cache in one fused launch (include/lfamd_hip.h), and
+// lfamd_flash_attn_q: the same kernels on a Q8_0 / Q4_0 K and V cache (the operand types: fa_op, below).
 //
 // For each (i3, head h, query row j):  s_t = scale * <Q, K_t> + mask[j][t],  dst = sum_t softmax(s)_t V_t.  K and V are the -fa cache
 // views (V NOT transposed), head h reads KV head h / (n_head / n_head_kv).  Reference: ggml_cuda_flash_attn_ext
@@ -59,6 +60,149 @@ __device__ static inline float fa_neg_inf() {
     return -__builtin_inff();
 }
 
+// ----------------------------------------------------------------------------------------------------------- K / V operand types
+// What the two routes ask of an operand type (lfamd_flash_attn: F16; lfamd_flash_attn_q: Q8_0, Q4_0 — K and V each have their own
+// parameter, so a mixed pair is one more instantiation):
+//   decode   piece: the 8 consecutive elements sl * 8 .. of a row that one lane keeps, raw in registers; off8(sl): where its load
+//            starts in the row; ld8 / zero8; widen8: the f32 values (a block element is f32(d) * (float)code, exact)
+//   prefill  stage<D>: one thread's share of a 64-key tile, raw in registers, moved in NLD steps (load: keys past n_kv are zeros,
+//            never memory), and write<ROW, SWZ>: the same elements as f16 to LDS rows of ROW bytes, 16-byte chunk ch of row r at
+//            chunk ch ^ (r & 7) where SWZ.  A block element is f16(d * code), rounded once to nearest even.
+template <int T>
+struct fa_op;
+
+template <>
+struct fa_op<LFAMD_TYPE_F16> {
+    typedef uint4 piece;
+    __device__ static inline int off8(int sl) { return sl * 16; }
+    __device__ static inline piece ld8(const uint8_t *p) { return *(const uint4 *)p; }
+    __device__ static inline piece zero8() { return make_uint4(0, 0, 0, 0); }
+    __device__ static inline void widen8(const piece v, int, float (&f)[8]) {
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            f[2 * e] = h2f((uint16_t)(d[e] & 0xffff));
+            f[2 * e + 1] = h2f((uint16_t)(d[e] >> 16));
+        }
+    }
+    template <int D>
+    struct stage {
+        static constexpr int CH = D / 8;           // 16-byte chunks of a row
+        static constexpr int NLD = 64 * CH / 256;  // 16-byte loads per thread and tile
+        uint4 r[NLD];
+        __device__ inline void load(int i, const uint8_t *base, size_t nb1, long t0, long n_kv, int tid) {
+            const int idx = tid + 256 * i, row = idx / CH, ch = idx % CH;
+            const long t = t0 + row;
+            r[i] = t < n_kv ? *(const uint4 *)(base + t * nb1 + ch * 16) : make_uint4(0, 0, 0, 0);
+        }
+        template <int ROW, bool SWZ>
+        __device__ inline void write(int i, uint8_t *lds, int tid) const {
+            const int idx = tid + 256 * i, row = idx / CH, ch = idx % CH;
+            *(uint4 *)(lds + row * ROW + ((SWZ ? ch ^ (row & 7) : ch) * 16)) = r[i];
+        }
+    };
+};
+
+// 4 NW bytes from the EVEN address p and no other byte: dword loads off their boundary, which the target allows
+template <int NW>
+__device__ static inline void fa_ld_even(const uint8_t *p, uint32_t (&W)[NW]) {
+    struct __attribute__((packed, aligned(2))) words {
+        uint32_t w[NW];
+    };
+    const words v = *(const words *)p;
+#pragma unroll
+    for (int j = 0; j < NW; j++)
+        W[j] = v.w[j];
+}
+
+// A 32-block {f16 d, payload} of TS bytes on a 2-byte boundary; NIB: 16 bytes of nibbles (element j < 16 the low nibble of byte j,
+// j + 16 its high nibble, value d * (nibble - 8)), else 32 int8 codes.
+template <int TS, bool NIB>
+struct fa_block_op {
+    // A lane's 8 elements are 8 payload bytes; the four lanes of a block sit in one quad.  A lane loads those bytes and the two in
+    // front of them through ONE address: in the quad's first lane the two are the block's d, which the quad takes from there.
+    struct piece {
+        uint32_t x[2], hs; // 10 bytes: x[0] bits 0 .. 15 the two in front
+    };
+    __device__ static inline int sub8(int sl) { return NIB ? sl & 1 : sl & 3; } // which 8 payload bytes hold the lane's elements
+    __device__ static inline int off8(int sl) { return (sl >> 2) * TS + 8 * sub8(sl); }
+    __device__ static inline piece ld8(const uint8_t *p) {
+        piece r;
+        fa_ld_even<2>(p, r.x);
+        r.hs = *(const uint16_t *)(p + 8);
+        return r;
+    }
+    __device__ static inline piece zero8() { return piece{{0, 0}, 0}; } // d = +0: every element a zero, whatever the code
+    __device__ static inline void widen8(const piece v, int sl, float (&f)[8]) { // (every lane of the quad is here)
+        const float d = h2f((uint16_t)dpp_u32<0x00>(v.x[0])); // quad_perm [0,0,0,0]
+        uint32_t w[2] = {(v.x[0] >> 16) | (v.x[1] << 16), (v.x[1] >> 16) | (v.hs << 16)};
+        if constexpr (NIB) { // nibble - 8 per byte (bit 7 set first: no borrow crosses a byte)
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                w[j] = ((((w[j] >> (2 * (sl & 2))) & 0x0F0F0F0Fu) | 0x80808080u) - 0x08080808u) ^ 0x80808080u;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+            f[e] = d * (float)(int8_t)(w[e >> 2] >> (8 * (e & 3)));
+    }
+    // Thread tid of 256: key tid >> 2 of the tile, quarter q = tid & 3 of its row: D = 128 one block, D = 64 half a block.
+    template <int D>
+    struct stage {
+        static constexpr int HALVES = 128 / D, NE = 32 / HALVES; // threads per block; elements per thread
+        static constexpr int NW = NIB ? 4 : NE / 4;              // payload dwords per thread
+        static constexpr int NLD = 1;
+        uint32_t w[NW], d;
+        __device__ inline void load(int, const uint8_t *base, size_t nb1, long t0, long n_kv, int tid) {
+            const int q = tid & 3, b = q / HALVES, hf = q % HALVES;
+            const long t = t0 + (tid >> 2);
+            d = 0;
+#pragma unroll
+            for (int j = 0; j < NW; j++)
+                w[j] = NIB ? 0x88888888u : 0u; // code 0
+            if (t < n_kv) {
+                const uint8_t *blk = base + t * nb1 + b * TS;
+                d = *(const uint16_t *)blk;
+                fa_ld_even<NW>(blk + 2 + (NIB ? 0 : NE * hf), w);
+            }
+        }
+        // f16(d * code) for every code: 0x6400 | u is the f16 1024 + u (u < 1024), so a byte permute and one exact packed subtraction
+        // convert two codes, and the packed multiply by d rounds once.
+        template <int ROW, bool SWZ>
+        __device__ inline void write(int, uint8_t *lds, int tid) const {
+            typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+            const int row = tid >> 2, q = tid & 3, hf = q % HALVES;
+            const _Float16 dh = __builtin_bit_cast(_Float16, (uint16_t)d), bias = (_Float16)(NIB ? 1032.0f : 1152.0f);
+            const half2_t d2 = {dh, dh}, b2 = {bias, bias};
+            uint32_t u[NE / 4]; // four biased codes to a dword: code + 128, or the nibble
+#pragma unroll
+            for (int j = 0; j < NE / 4; j++) {
+                if constexpr (!NIB)
+                    u[j] = w[j] ^ 0x80808080u;
+                else if constexpr (HALVES == 1)
+                    u[j] = (w[j & 3] >> (4 * (j >> 2))) & 0x0F0F0F0Fu;
+                else
+                    u[j] = (w[j] >> (4 * hf)) & 0x0F0F0F0Fu;
+            }
+#pragma unroll
+            for (int c = 0; c < NE / 8; c++) {
+                uint32_t o[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const uint32_t x = __builtin_amdgcn_perm(0x64646464u, u[2 * c + (e >> 1)], (e & 1) ? 0x04030402u : 0x04010400u);
+                    o[e] = __builtin_bit_cast(uint32_t, (__builtin_bit_cast(half2_t, x) - b2) * d2);
+                }
+                const int ch = q * (NE / 8) + c;
+                *(uint4 *)(lds + row * ROW + ((SWZ ? ch ^ (row & 7) : ch) * 16)) = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+        }
+    };
+};
+
+template <>
+struct fa_op<LFAMD_TYPE_Q8_0> : fa_block_op<34, false> {};
+template <>
+struct fa_op<LFAMD_TYPE_Q4_0> : fa_block_op<18, true> {};
+
 // ------------------------------------------------------------------------------------------------------------------ decode route
 
 template <int LPK>
@@ -71,18 +215,11 @@ __device__ static inline float fa_lane_sum(float v) { // over the LPK (8 or 16) 
     return v;
 }
 
-__device__ static inline void fa_widen8(const uint4 v, float (&f)[8]) {
-    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        f[2 * e] = h2f((uint16_t)(d[e] & 0xffff));
-        f[2 * e + 1] = h2f((uint16_t)(d[e] >> 16));
-    }
-}
-
 // NC: columns (query row x head of the item) a lane keeps, the live count rounded up to 1, 2, 4 or 8
-template <int D, int NC>
+template <int KT, int VT, int D, int NC>
 __global__ __launch_bounds__(64 * FA_NW) void fa_decode_kernel(const fa_args a) {
+    using KO = fa_op<KT>;
+    using VO = fa_op<VT>;
     constexpr int LPK = D / 8, KPW = 64 / LPK, RU = 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slot = lane / LPK, sl = lane % LPK;
     const int items = a.shared ? a.n_head_kv : a.n_head;
@@ -109,21 +246,23 @@ __global__ __launch_bounds__(64 * FA_NW) void fa_decode_kernel(const fa_args a) 
             o[c][e] = 0.0f;
     }
     const long t_begin = (long)blockIdx.x * FA_CHUNK, t_end = t_begin + FA_CHUNK < a.n_kv ? t_begin + FA_CHUNK : a.n_kv;
-    const uint8_t *Kb = a.K + i3 * a.k_nb3 + (size_t)hk * a.k_nb2 + sl * 16;
-    const uint8_t *Vb = a.V + i3 * a.v_nb3 + (size_t)hk * a.v_nb2 + sl * 16;
+    const uint8_t *Kb = a.K + i3 * a.k_nb3 + (size_t)hk * a.k_nb2 + KO::off8(sl);
+    const uint8_t *Vb = a.V + i3 * a.v_nb3 + (size_t)hk * a.v_nb2 + VO::off8(sl);
     for (long tb = t_begin + wave * (KPW * RU); tb < t_end; tb += FA_NW * KPW * RU) {
-        uint4 kr[RU], vr[RU];
+        typename KO::piece kr[RU];
+        typename VO::piece vr[RU];
 #pragma unroll
         for (int u = 0; u < RU; u++) { // keys past the chunk: zeros, never memory
             const long t = tb + u * KPW + slot;
-            kr[u] = t < t_end ? *(const uint4 *)(Kb + t * a.k_nb1) : make_uint4(0, 0, 0, 0);
-            vr[u] = t < t_end ? *(const uint4 *)(Vb + t * a.v_nb1) : make_uint4(0, 0, 0, 0);
+            kr[u] = KO::zero8(), vr[u] = VO::zero8();
+            if (t < t_end)
+                kr[u] = KO::ld8(Kb + t * a.k_nb1), vr[u] = VO::ld8(Vb + t * a.v_nb1);
         }
         float s[NC][RU];
 #pragma unroll
         for (int u = 0; u < RU; u++) {
             float kf[8];
-            fa_widen8(kr[u], kf);
+            KO::widen8(kr[u], sl, kf);
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 if (c < nc) {
@@ -138,7 +277,7 @@ __global__ __launch_bounds__(64 * FA_NW) void fa_decode_kernel(const fa_args a) 
         float vf[RU][8];
 #pragma unroll
         for (int u = 0; u < RU; u++)
-            fa_widen8(vr[u], vf[u]);
+            VO::widen8(vr[u], sl, vf[u]);
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (c < nc) {
@@ -285,12 +424,17 @@ __global__ __launch_bounds__(512) void fa_combine_kernel(const fa_args a) {
 
 // ----------------------------------------------------------------------------------------------------------------- prefill route
 
-template <int D>
-__global__ __launch_bounds__(256) void fa_prefill_kernel(const fa_args a) {
-    constexpr int CH = D / 8;                 // 16-byte chunks of a row
+// Waves per SIMD the register allocator is held to.  1 asks for nothing (the F16 code is what it was).  2 for the block tiles at
+// D = 128, whose staged registers are 18 (Q8_0) or 10 (Q4_0) against the F16 tile's 32: held to 256 registers the compiler keeps the
+// MFMA accumulators in ordinary registers (no second register file, no copies between the two, no scratch), and two work-groups share
+// a CU.  D = 64 has not been timed and is left alone.
+template <int KT, int VT, int D>
+constexpr int fa_prefill_waves = KT != LFAMD_TYPE_F16 && VT != LFAMD_TYPE_F16 && D == 128 ? 2 : 1;
+
+template <int KT, int VT, int D>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fa_prefill_waves<KT, VT, D>))) void fa_prefill_kernel(const fa_args a) {
     constexpr int KROW = 2 * D;               // K tile: rows of 2 D bytes, chunk ch of row r at chunk ch ^ (r & 7)
     constexpr int VROW = 2 * D + 64;          // V tile: four consecutive rows start 16 banks apart (the transposed read takes 4 rows x 64 B per half)
-    constexpr int NLD = 64 * CH / 256;        // 16-byte loads per thread, tile and operand
     constexpr int KS = D / 16, DB = D / 32;   // MFMA k-steps of QK; 32-wide blocks of D
     __shared__ __attribute__((aligned(16))) uint8_t Ks[64 * KROW];
     __shared__ __attribute__((aligned(16))) uint8_t Vs[64 * VROW];
@@ -331,23 +475,26 @@ __global__ __launch_bounds__(256) void fa_prefill_kernel(const fa_args a) {
     // transposed V read: lane 16 g + i supplies row 4 h + (i >> 2), columns 16 (g & 1) + 4 (i & 3) .. + 3 of its block
     const int tr_off = (4 * h + ((lane & 15) >> 2)) * VROW + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
     const long n_tiles = (a.n_kv + 63) / 64;
-    uint4 kst[NLD], vst[NLD];
+    typename fa_op<KT>::template stage<D> kst; // the staged tile: raw in registers from stage_load to stage_write
+    typename fa_op<VT>::template stage<D> vst;
 
+    constexpr int KLD = decltype(kst)::NLD, VLD = decltype(vst)::NLD;
     auto stage_load = [&](long tile) {
 #pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int idx = tid + 256 * i, r = idx / CH, ch = idx % CH;
-            const long t = tile * 64 + r;
-            kst[i] = t < a.n_kv ? *(const uint4 *)(Kb + t * a.k_nb1 + ch * 16) : make_uint4(0, 0, 0, 0);
-            vst[i] = t < a.n_kv ? *(const uint4 *)(Vb + t * a.v_nb1 + ch * 16) : make_uint4(0, 0, 0, 0);
+        for (int i = 0; i < (KLD > VLD ? KLD : VLD); i++) {
+            if (i < KLD)
+                kst.load(i, Kb, a.k_nb1, tile * 64, a.n_kv, tid);
+            if (i < VLD)
+                vst.load(i, Vb, a.v_nb1, tile * 64, a.n_kv, tid);
         }
     };
     auto stage_write = [&]() {
 #pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int idx = tid + 256 * i, r = idx / CH, ch = idx % CH;
-            *(uint4 *)(Ks + r * KROW + ((ch ^ (r & 7)) * 16)) = kst[i];
-            *(uint4 *)(Vs + r * VROW + ch * 16) = vst[i];
+        for (int i = 0; i < (KLD > VLD ? KLD : VLD); i++) {
+            if (i < KLD)
+                kst.template write<KROW, true>(i, Ks, tid);
+            if (i < VLD)
+                vst.template write<VROW, false>(i, Vs, tid);
         }
     };
     auto compute = [&](long tile) {
@@ -509,23 +656,54 @@ static long fa_chunks(long n_q, long n_kv) {
     return n_q > 8 || n_kv <= FA_CHUNK ? 1 : (n_kv + FA_CHUNK - 1) / FA_CHUNK;
 }
 
-static int fa_fail(int code, const char *what) {
+static int fa_fail(bool q, int code, const char *what) {
     char msg[160];
-    snprintf(msg, sizeof(msg), "lfamd_flash_attn: %s", what);
+    snprintf(msg, sizeof(msg), "lfamd_flash_attn%s: %s", q ? "_q" : "", what);
     lfamd_set_error(msg);
     return code;
 }
 
-template <int D>
+// bytes of a K / V row of D elements
+static size_t fa_row_size(int type, long D) {
+    return type == LFAMD_TYPE_Q8_0 ? (size_t)(D / 32) * 34 : type == LFAMD_TYPE_Q4_0 ? (size_t)(D / 32) * 18 : (size_t)D * 2;
+}
+
+template <int KT, int VT, int D>
 static void fa_decode_go(const fa_args &a, int nc, dim3 grid, hipStream_t s) {
     if (nc <= 1)
-        fa_decode_kernel<D, 1><<<grid, 64 * FA_NW, 0, s>>>(a);
+        fa_decode_kernel<KT, VT, D, 1><<<grid, 64 * FA_NW, 0, s>>>(a);
     else if (nc <= 2)
-        fa_decode_kernel<D, 2><<<grid, 64 * FA_NW, 0, s>>>(a);
+        fa_decode_kernel<KT, VT, D, 2><<<grid, 64 * FA_NW, 0, s>>>(a);
     else if (nc <= 4)
-        fa_decode_kernel<D, 4><<<grid, 64 * FA_NW, 0, s>>>(a);
+        fa_decode_kernel<KT, VT, D, 4><<<grid, 64 * FA_NW, 0, s>>>(a);
     else
-        fa_decode_kernel<D, 8><<<grid, 64 * FA_NW, 0, s>>>(a);
+        fa_decode_kernel<KT, VT, D, 8><<<grid, 64 * FA_NW, 0, s>>>(a);
+}
+
+// the launches of a checked call on the pair (KT, VT)
+template <int KT, int VT>
+static void fa_go(const fa_args &a, long D, long ne3, hipStream_t s) {
+    if (a.n_q <= 8) {
+        const int nc = (int)(a.shared ? a.n_q * a.group : a.n_q);
+        const dim3 grid((unsigned)a.n_chunks, (unsigned)(ne3 * (a.shared ? a.n_head_kv : a.n_head)), 1);
+        if (D == 64)
+            fa_decode_go<KT, VT, 64>(a, nc, grid, s);
+        else
+            fa_decode_go<KT, VT, 128>(a, nc, grid, s);
+        if (a.n_chunks > 1) {
+            const unsigned rows = (unsigned)(ne3 * a.n_head * a.n_q);
+            if (D == 64)
+                fa_combine_kernel<64><<<rows, 512, 0, s>>>(a);
+            else
+                fa_combine_kernel<128><<<rows, 512, 0, s>>>(a);
+        }
+    } else {
+        const dim3 grid((unsigned)(a.n_head * ne3), (unsigned)((a.n_q + 127) / 128), 1);
+        if (D == 64)
+            fa_prefill_kernel<KT, VT, 64><<<grid, 256, 0, s>>>(a);
+        else
+            fa_prefill_kernel<KT, VT, 128><<<grid, 256, 0, s>>>(a);
+    }
 }
 
 } // namespace
@@ -540,14 +718,19 @@ extern "C" size_t lfamd_flash_attn_workspace(long D, long n_q, long n_kv, long n
 
 // The checks of include/lfamd_hip.h in their documented order, as one table (the idiom of lfamd_batched_check: evaluated whole, so
 // every row guards itself); no device call.  `entry`: asked by lfamd_flash_attn, to which every flag is reserved; else by
-// lfamd_flash_attn_check, which takes LFAMD_CHECK_UNPLACED.  true: launch.  false: *rc is the answer (LFAMD_OK: an empty call).
-static bool fa_check(bool entry, const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2,
+// lfamd_flash_attn_check, which takes LFAMD_CHECK_UNPLACED.  `q`: the table of lfamd_flash_attn_q — the pair rule, K / V on 2-byte
+// boundaries, rows of blocks.  true: launch.  false: *rc is the answer (LFAMD_OK: an empty call).
+static bool fa_check(bool q, bool entry, const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2,
                      size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3, const void *d_mask, size_t mask_nb1, long D,
                      long n_q, long n_kv, long n_head, long n_head_kv, long ne3, float max_bias, const float *d_dst, size_t dst_nb1, size_t dst_nb2,
                      size_t dst_nb3, const void *d_workspace, size_t workspace_bytes, unsigned flags, int *rc) {
     const bool unplaced = !entry && (flags & LFAMD_CHECK_UNPLACED);
     const unsigned reserved = entry ? flags : flags & ~LFAMD_CHECK_UNPLACED;
     const size_t need = lfamd_flash_attn_workspace(D, n_q, n_kv, n_head, n_head_kv, ne3);
+    const bool f16_pair = Ktype == LFAMD_TYPE_F16 && Vtype == LFAMD_TYPE_F16;
+    const bool block_pair = Ktype == Vtype && (Ktype == LFAMD_TYPE_Q8_0 || Ktype == LFAMD_TYPE_Q4_0);
+    const uintptr_t qd_bits = (uintptr_t)d_Q | q_nb1 | q_nb2 | q_nb3 | (uintptr_t)d_dst | dst_nb1 | dst_nb2 | dst_nb3;
+    const uintptr_t kv_bits = (uintptr_t)d_K | k_nb1 | k_nb2 | k_nb3 | (uintptr_t)d_V | v_nb1 | v_nb2 | v_nb3;
     const struct {
         bool hit;
         int code;
@@ -555,7 +738,9 @@ static bool fa_check(bool entry, const float *d_Q, size_t q_nb1, size_t q_nb2, s
     } checks[] = {
         {D < 0 || n_q < 0 || n_kv < 0 || n_head < 0 || n_head_kv < 0 || ne3 < 0, LFAMD_ERR_INVALID, "negative dimension"},
         {n_q == 0 || n_head == 0 || ne3 == 0, LFAMD_OK, nullptr},
-        {Ktype != LFAMD_TYPE_F16 || Vtype != LFAMD_TYPE_F16, LFAMD_ERR_UNSUPPORTED, "F16 K and V only"},
+        {!q && !f16_pair, LFAMD_ERR_UNSUPPORTED, "F16 K and V only"},
+        {q && f16_pair, LFAMD_ERR_UNSUPPORTED, "F16 K and V: that is lfamd_flash_attn"},
+        {q && !block_pair, LFAMD_ERR_UNSUPPORTED, "the K / V types are not (Q8_0, Q8_0) or (Q4_0, Q4_0)"},
         {D != 64 && D != 128, LFAMD_ERR_UNSUPPORTED, "head size is not 64 or 128"},
         {max_bias != 0.0f, LFAMD_ERR_UNSUPPORTED, "max_bias != 0 (ALiBi)"},
         {n_head > 65535 || ne3 > 65535 || (size_t)n_head * (size_t)ne3 > 65535 || (n_q + 127) / 128 > 65535, LFAMD_ERR_UNSUPPORTED,
@@ -563,43 +748,46 @@ static bool fa_check(bool entry, const float *d_Q, size_t q_nb1, size_t q_nb2, s
         {n_kv == 0, LFAMD_ERR_UNSUPPORTED, "n_kv == 0"},
         {!unplaced && (!d_Q || !d_K || !d_V || !d_dst || (!d_workspace && workspace_bytes != 0)), LFAMD_ERR_INVALID, "null pointer"},
         {n_head_kv < 1 || n_head % n_head_kv != 0, LFAMD_ERR_INVALID, "n_head is not a multiple of n_head_kv"},
-        {((uintptr_t)d_Q | q_nb1 | q_nb2 | q_nb3 | (uintptr_t)d_K | k_nb1 | k_nb2 | k_nb3 | (uintptr_t)d_V | v_nb1 | v_nb2 | v_nb3 |
-          (uintptr_t)d_dst | dst_nb1 | dst_nb2 | dst_nb3) % 16 != 0,
-         LFAMD_ERR_INVALID, "a Q / K / V / dst base or stride is not a multiple of 16"},
+        {!q && (qd_bits | kv_bits) % 16 != 0, LFAMD_ERR_INVALID, "a Q / K / V / dst base or stride is not a multiple of 16"},
+        {q && qd_bits % 16 != 0, LFAMD_ERR_INVALID, "a Q / dst base or stride is not a multiple of 16"},
+        {q && kv_bits % 2 != 0, LFAMD_ERR_INVALID, "a K / V base or stride is not a multiple of 2"},
         {d_mask && (((uintptr_t)d_mask | mask_nb1) % 2 != 0 || mask_nb1 < (size_t)n_kv * 2), LFAMD_ERR_INVALID,
          "mask base / row stride is odd or the stride is smaller than the row"},
-        {k_nb1 < (size_t)D * 2 || v_nb1 < (size_t)D * 2 || q_nb1 < (size_t)D * 4 || dst_nb1 < (size_t)D * 4, LFAMD_ERR_INVALID,
+        {k_nb1 < fa_row_size(Ktype, D) || v_nb1 < fa_row_size(Vtype, D) || q_nb1 < (size_t)D * 4 || dst_nb1 < (size_t)D * 4, LFAMD_ERR_INVALID,
          "a row stride is smaller than the row"},
         {reserved != 0, LFAMD_ERR_INVALID, "flags are reserved (0)"},
         {!unplaced && workspace_bytes < need, LFAMD_ERR_WORKSPACE, "workspace smaller than lfamd_flash_attn_workspace()"},
     };
     for (const auto &c : checks)
         if (c.hit) {
-            *rc = c.what ? fa_fail(c.code, c.what) : c.code;
+            *rc = c.what ? fa_fail(q, c.code, c.what) : c.code;
             return false;
         }
     return true;
 }
 
-extern "C" int lfamd_flash_attn_check(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1,
-                                      size_t k_nb2, size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
-                                      const void *d_mask, size_t mask_nb1, long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3,
-                                      float max_bias, const float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
-                                      const void *d_workspace, size_t workspace_bytes, unsigned flags) {
-    int rc = LFAMD_OK;
-    (void)fa_check(false, d_Q, q_nb1, q_nb2, q_nb3, Ktype, d_K, k_nb1, k_nb2, k_nb3, Vtype, d_V, v_nb1, v_nb2, v_nb3, d_mask, mask_nb1, D, n_q, n_kv,
-                   n_head, n_head_kv, ne3, max_bias, d_dst, dst_nb1, dst_nb2, dst_nb3, d_workspace, workspace_bytes, flags, &rc);
-    return rc;
-}
+// the argument lists of the exported calls, written once
+#define FA_CHECK_PARAMS                                                                                                                    \
+    const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,     \
+        int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3, const void *d_mask, size_t mask_nb1, long D, long n_q,       \
+        long n_kv, long n_head, long n_head_kv, long ne3, float max_bias, const float *d_dst, size_t dst_nb1, size_t dst_nb2,              \
+        size_t dst_nb3, const void *d_workspace, size_t workspace_bytes, unsigned flags
+#define FA_CHECK_ARGS                                                                                                                      \
+    d_Q, q_nb1, q_nb2, q_nb3, Ktype, d_K, k_nb1, k_nb2, k_nb3, Vtype, d_V, v_nb1, v_nb2, v_nb3, d_mask, mask_nb1, D, n_q, n_kv, n_head,   \
+        n_head_kv, ne3, max_bias, d_dst, dst_nb1, dst_nb2, dst_nb3, d_workspace, workspace_bytes, flags
+#define FA_CALL_PARAMS                                                                                                                     \
+    const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1, size_t k_nb2, size_t k_nb3,     \
+        int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3, const void *d_mask, size_t mask_nb1, long D, long n_q,       \
+        long n_kv, long n_head, long n_head_kv, long ne3, float scale, float max_bias, float *d_dst, size_t dst_nb1, size_t dst_nb2,       \
+        size_t dst_nb3, void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream
+#define FA_CALL_ARGS                                                                                                                       \
+    d_Q, q_nb1, q_nb2, q_nb3, Ktype, d_K, k_nb1, k_nb2, k_nb3, Vtype, d_V, v_nb1, v_nb2, v_nb3, d_mask, mask_nb1, D, n_q, n_kv, n_head,   \
+        n_head_kv, ne3, scale, max_bias, d_dst, dst_nb1, dst_nb2, dst_nb3, d_workspace, workspace_bytes, flags, stream
 
-extern "C" int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, size_t q_nb3, int Ktype, const void *d_K, size_t k_nb1,
-                                size_t k_nb2, size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3,
-                                const void *d_mask, size_t mask_nb1, long D, long n_q, long n_kv, long n_head, long n_head_kv, long ne3,
-                                float scale, float max_bias, float *d_dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3,
-                                void *d_workspace, size_t workspace_bytes, unsigned flags, void *stream) {
+// the checks, then the launches of the pair
+static int fa_call(bool q, FA_CALL_PARAMS) {
     int rc;
-    if (!fa_check(true, d_Q, q_nb1, q_nb2, q_nb3, Ktype, d_K, k_nb1, k_nb2, k_nb3, Vtype, d_V, v_nb1, v_nb2, v_nb3, d_mask, mask_nb1, D, n_q, n_kv,
-                  n_head, n_head_kv, ne3, max_bias, d_dst, dst_nb1, dst_nb2, dst_nb3, d_workspace, workspace_bytes, flags, &rc))
+    if (!fa_check(q, true, FA_CHECK_ARGS, &rc))
         return rc;
 
     fa_args a{};
@@ -613,29 +801,34 @@ extern "C" int lfamd_flash_attn(const float *d_Q, size_t q_nb1, size_t q_nb2, si
     a.mask16 = d_mask && (((uintptr_t)d_mask | mask_nb1) % 16 == 0);
     a.c = scale * FA_LOG2E;
     hipStream_t s = (hipStream_t)stream;
-    if (n_q <= 8) {
-        const int nc = (int)(a.shared ? n_q * a.group : n_q);
-        const dim3 grid((unsigned)a.n_chunks, (unsigned)(ne3 * (a.shared ? n_head_kv : n_head)), 1);
-        if (D == 64)
-            fa_decode_go<64>(a, nc, grid, s);
-        else
-            fa_decode_go<128>(a, nc, grid, s);
-        if (a.n_chunks > 1) {
-            const unsigned rows = (unsigned)(ne3 * n_head * n_q);
-            if (D == 64)
-                fa_combine_kernel<64><<<rows, 512, 0, s>>>(a);
-            else
-                fa_combine_kernel<128><<<rows, 512, 0, s>>>(a);
-        }
-    } else {
-        const dim3 grid((unsigned)(n_head * ne3), (unsigned)((n_q + 127) / 128), 1);
-        if (D == 64)
-            fa_prefill_kernel<64><<<grid, 256, 0, s>>>(a);
-        else
-            fa_prefill_kernel<128><<<grid, 256, 0, s>>>(a);
-    }
+    if (Ktype == LFAMD_TYPE_Q8_0)
+        fa_go<LFAMD_TYPE_Q8_0, LFAMD_TYPE_Q8_0>(a, D, ne3, s);
+    else if (Ktype == LFAMD_TYPE_Q4_0)
+        fa_go<LFAMD_TYPE_Q4_0, LFAMD_TYPE_Q4_0>(a, D, ne3, s);
+    else
+        fa_go<LFAMD_TYPE_F16, LFAMD_TYPE_F16>(a, D, ne3, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         lfamd_set_error(hipGetErrorString(e));
     return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
+}
+
+extern "C" int lfamd_flash_attn_check(FA_CHECK_PARAMS) {
+    int rc = LFAMD_OK;
+    (void)fa_check(false, false, FA_CHECK_ARGS, &rc);
+    return rc;
+}
+
+extern "C" int lfamd_flash_attn(FA_CALL_PARAMS) {
+    return fa_call(false, FA_CALL_ARGS);
+}
+
+extern "C" int lfamd_flash_attn_q_check(FA_CHECK_PARAMS) {
+    int rc = LFAMD_OK;
+    (void)fa_check(true, false, FA_CHECK_ARGS, &rc);
+    return rc;
+}
+
+extern "C" int lfamd_flash_attn_q(FA_CALL_PARAMS) {
+    return fa_call(true, FA_CALL_ARGS);
 }

@@ -1,6 +1,6 @@
 // ggml_backend_lfamd.hip — the 12 GGML_CALL (ms_abi) symbols llamafile/cuda.c:726-737 imports from ggml-rocm.so, served by
-// this module: a ggml backend whose supports_op says yes to GGML_OP_MUL_MAT / GGML_OP_MUL_MAT_ID, on an F16
-// K / V cache GGML_OP_FLASH_ATTN_EXT (the graph of -fa; reference: ggml_cuda_flash_attn_ext, ggml-cuda.cu.patch:8280-8400), and
+// this module: a ggml backend whose supports_op says yes to GGML_OP_MUL_MAT / GGML_OP_MUL_MAT_ID, on an F16,
+// Q8_0 or Q4_0 K / V cache GGML_OP_FLASH_ATTN_EXT (the graph of -fa; reference: ggml_cuda_flash_attn_ext, ggml-cuda.cu.patch:8280-8400), and
 // GGML_OP_CPY into a cache in this backend's buffers (the K / V store; reference: ggml_cuda_cpy, ggml-cuda.cu.patch:5150-5260).
 //
 // Reference counterparts: ggml_cuda_link (ggml-cuda.cu.patch:468), the buffer interface (:16890-17027, set_tensor :16971),
@@ -149,7 +149,7 @@ struct backend_ctx {
     long sibling_calls = 0; // calls that served more than one node (LFAMD_BACKEND_STATS=1 prints it when the backend is freed)
     long batched_calls = 0; // lfamd_mul_mat_batched calls: a node's slices in one launch (printed beside it)
     long block_k_calls = 0; // lfamd_mul_mat_batched_q calls: the same for a 32-block src0 outside the weights buffers (a third line)
-    long flash_attn_calls = 0; // lfamd_flash_attn calls: one per FLASH_ATTN_EXT node (a fourth line)
+    long flash_attn_calls = 0; // lfamd_flash_attn / lfamd_flash_attn_q calls: one per FLASH_ATTN_EXT node (a fourth line)
     long cpy_calls = 0;        // lfamd_cpy calls: one per CPY node (a fifth line)
 };
 
@@ -825,7 +825,7 @@ const void *address_of(const struct ggml_tensor *t, bool placed) {
 }
 
 // ------------------------------------------------------------------ GGML_OP_FLASH_ATTN_EXT
-// src[0] = Q f32 [D, n_q, n_head, ne3], src[1] = K f16 [D, n_kv, n_head_kv, ne3], src[2] = V f16 (not transposed), src[3] = mask f16
+// src[0] = Q f32 [D, n_q, n_head, ne3], src[1] = K f16 / q8_0 / q4_0 [D, n_kv, n_head_kv, ne3], src[2] = V of K's type (not transposed), src[3] = mask f16
 // [n_kv, >= n_q] or NULL, dst f32 [D, n_head, n_q, ne3]; op_params: scale (f32) at [0], max_bias (f32) at [1], precision at [2]
 // (ggml-cuda.cu.patch:8352-8353, :9987).
 struct fa_call { // lfamd_flash_attn's arguments, but the workspace
@@ -850,7 +850,12 @@ fa_call fa_call_of(const struct ggml_tensor *op, bool placed) {
     return c;
 }
 
-// beside lfamd_flash_attn_check: the switch, the ggml types and nb[0], the extents of K / V / dst / mask against Q, a contiguous dst
+// the entry point is picked by K's type: F16 lfamd_flash_attn, Q8_0 / Q4_0 lfamd_flash_attn_q
+bool fa_block_cache(const fa_call &c) {
+    return c.ktype == LFAMD_TYPE_Q8_0 || c.ktype == LFAMD_TYPE_Q4_0;
+}
+
+// beside lfamd_flash_attn_check / lfamd_flash_attn_q_check: the switch, the ggml types and nb[0], the extents of K / V / dst / mask against Q, a contiguous dst
 // and the precision — what the call's argument list does not carry
 bool flash_attn_supported(const struct ggml_tensor *op) {
     if (env_on("LFAMD_BACKEND_NO_FLASH_ATTN"))
@@ -869,21 +874,29 @@ bool flash_attn_supported(const struct ggml_tensor *op) {
     if (op->op_params[2] != 0 /* GGML_PREC_DEFAULT */)
         return false;
     const fa_call c = fa_call_of(op, false);
+    if (fa_block_cache(c)) // a Q8_0 / Q4_0 K: lfamd_flash_attn_q's table (which refuses a V of another type)
+        return type_ok(c.ktype) && type_ok(c.vtype) &&
+               lfamd_flash_attn_q_check((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype,
+                                        c.v, c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3,
+                                        c.max_bias, (const float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], nullptr, 0,
+                                        LFAMD_CHECK_UNPLACED) == LFAMD_OK;
     return lfamd_flash_attn_check((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v,
                                   c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.max_bias,
                                   (const float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], nullptr, 0, LFAMD_CHECK_UNPLACED) == LFAMD_OK;
 }
 
-// ONE lfamd_flash_attn on the tensors' own pointers and nb[]
+// ONE lfamd_flash_attn / lfamd_flash_attn_q on the tensors' own pointers and nb[]
 enum ggml_status run_flash_attn(backend_ctx *ctx, struct ggml_tensor *dst) {
     const fa_call c = fa_call_of(dst, true);
     if (!grow(ctx->ws, ctx->ws_cap, lfamd_flash_attn_workspace(c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3)))
         return GGML_STATUS_ALLOC_FAILED;
-    const int rc = lfamd_flash_attn((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v,
-                                    c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.scale,
-                                    c.max_bias, (float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], ctx->ws, ctx->ws_cap, 0u, nullptr);
+    const bool q = fa_block_cache(c);
+    const int rc = (q ? lfamd_flash_attn_q : lfamd_flash_attn)(
+        (const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v, c.v_nb[1], c.v_nb[2],
+        c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.scale, c.max_bias, (float *)c.dst, c.dst_nb[1],
+        c.dst_nb[2], c.dst_nb[3], ctx->ws, ctx->ws_cap, 0u, nullptr);
     if (rc != LFAMD_OK) {
-        logf("ggml_backend_lfamd: %s: %s\n", "lfamd_flash_attn", lfamd_last_error());
+        logf("ggml_backend_lfamd: %s: %s\n", q ? "lfamd_flash_attn_q" : "lfamd_flash_attn", lfamd_last_error());
         return GGML_STATUS_FAILED;
     }
     ctx->flash_attn_calls++;
