@@ -37,6 +37,13 @@ _lib = None
 
 _vp, _sz, _l, _i, _u = C.c_void_p, C.c_size_t, C.c_long, C.c_int, C.c_uint
 
+# argument lists that more than one entry point has (lfamd_hip.h: "the argument list is lfamd_...'s")
+_MUL_MAT_BATCHED = [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]
+_FA_OPERANDS = [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l]  # Q .. ne3
+_FA_DST_WS_FLAGS = [_vp, _sz, _sz, _sz, _vp, _sz, _u]
+_FLASH_ATTN = _FA_OPERANDS + [C.c_float, C.c_float] + _FA_DST_WS_FLAGS + [_vp]  # scale, max_bias; the stream
+_FLASH_ATTN_CHECK = _FA_OPERANDS + [C.c_float] + _FA_DST_WS_FLAGS  # max_bias
+
 _SIGS = {
     "lfamd_abi_version": (_i, []),
     "lfamd_last_error": (C.c_char_p, []),
@@ -81,17 +88,13 @@ _SIGS = {
     "lfamd_gemm_strided_batched_f16": (_i, [_l, _l, _l, C.c_float, _vp, _l, C.c_longlong, _vp, _l, C.c_longlong, C.c_float, _vp, _i, _l,
                                             C.c_longlong, _i, _vp]),
     "lfamd_gemm_batched_f16": (_i, [_l, _l, _l, C.c_float, _vp, _l, _vp, _l, C.c_float, _vp, _i, _l, _i, _vp]),
-    "lfamd_mul_mat_batched": (_i, [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]),
-    "lfamd_mul_mat_batched_q": (_i, [_i, _vp, _l, _l, _sz, _sz, _sz, _l, _l, _vp, _l, _sz, _sz, _sz, _l, _l, _vp, _sz, _sz, _sz, _u, _vp]),
+    "lfamd_mul_mat_batched": (_i, _MUL_MAT_BATCHED),
+    "lfamd_mul_mat_batched_q": (_i, _MUL_MAT_BATCHED),
     "lfamd_flash_attn_workspace": (_sz, [_l, _l, _l, _l, _l, _l]),
-    "lfamd_flash_attn": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
-                              C.c_float, C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u, _vp]),
-    "lfamd_flash_attn_check": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
-                                    C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u]),
-    "lfamd_flash_attn_q": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
-                                C.c_float, C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u, _vp]),
-    "lfamd_flash_attn_q_check": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _sz, _vp, _sz, _l, _l, _l, _l, _l, _l,
-                                      C.c_float, _vp, _sz, _sz, _sz, _vp, _sz, _u]),
+    "lfamd_flash_attn": (_i, _FLASH_ATTN),
+    "lfamd_flash_attn_check": (_i, _FLASH_ATTN_CHECK),
+    "lfamd_flash_attn_q": (_i, _FLASH_ATTN),
+    "lfamd_flash_attn_q_check": (_i, _FLASH_ATTN_CHECK),
     "lfamd_cpy": (_i, [_i, _vp, C.POINTER(_l), C.POINTER(_sz), _i, _vp, C.POINTER(_l), C.POINTER(_sz), _u, _vp]),
     "lfamd_cpy_check": (_i, [_i, _vp, C.POINTER(_l), C.POINTER(_sz), _i, _vp, C.POINTER(_l), C.POINTER(_sz), _u]),
     "lfamd_comm_unique_id": (_i, [_vp]),

@@ -14,11 +14,7 @@
 //               a 64 x 32 tile through padded LDS, reads coalesced along dim 1, writes along dim 0 in 16-byte lines of a row.
 //   GENERAL     anything else of a served pair: one element per lane (one block per eight lanes, one whole block per lane for the
 //               same-type moves), the index arithmetic of the reference.
-#include "lfamd_device.h"
-#include "../../include/lfamd_hip.h"
-#include "lfamd_internal.h"
-
-#include <stdio.h>
+#include "entry_checks.h"
 
 #pragma clang fp contract(off)
 
@@ -61,11 +57,6 @@ __device__ static inline size_t src_offset(const cpy_args &A, long i) {
 __device__ static inline size_t dst_offset(const cpy_args &A, long i) {
     return A.d_linear ? (size_t)i * A.d_linear : unit_offset(A.d, i);
 }
-
-template <int DT>
-struct blk { // bytes per block
-    static constexpr int size = DT == LFAMD_TYPE_Q8_0 ? 34 : DT == LFAMD_TYPE_Q4_1 ? 20 : DT == LFAMD_TYPE_Q5_0 ? 22 : DT == LFAMD_TYPE_Q5_1 ? 24 : 18;
-};
 
 __device__ static const float k_iq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
 
@@ -235,7 +226,7 @@ template <int DT>
 __global__ __launch_bounds__(256) void cpy_rows_kernel(const cpy_args A) {
     constexpr bool BLOCKS = DT != LFAMD_TYPE_F16;
     constexpr int UPT = BLOCKS ? CPY_TILE / 32 : CPY_TILE; // units per tile
-    __shared__ __attribute__((aligned(16))) uint8_t lds[16 + (BLOCKS ? (CPY_TILE / 32) * blk<DT>::size : CPY_TILE * 2)];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[16 + (BLOCKS ? (CPY_TILE / 32) * lfamd_block32<DT>::TS : CPY_TILE * 2)];
     const uint32_t run = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
     const long u0 = (long)run * A.run + (long)tile * UPT;                  // first unit of the tile
     const int units = (int)min((long)UPT, (long)A.run - (long)tile * UPT); // units in this tile
@@ -254,14 +245,14 @@ __global__ __launch_bounds__(256) void cpy_rows_kernel(const cpy_args A) {
                 x[c] = sp[e + c];
     }
     if constexpr (BLOCKS) {
-        quant_block<DT>(x, t & 7, (uint16_t *)(lds + a + (t >> 3) * blk<DT>::size), e < T);
+        quant_block<DT>(x, t & 7, (uint16_t *)(lds + a + (t >> 3) * lfamd_block32<DT>::TS), e < T);
     } else {
         uint16_t *o = (uint16_t *)(lds + a) + e;
         for (int c = 0; c < 4; c++)
             if (e + c < T)
                 o[c] = f2h_bits(x[c]);
     }
-    flush_image(lds, a, dp, BLOCKS ? units * blk<DT>::size : units * 2);
+    flush_image(lds, a, dp, BLOCKS ? units * lfamd_block32<DT>::TS : units * 2);
 }
 
 // same-type move: the run is a run of bytes (A.unit bytes per unit).  Where source and destination sit alike in their 16-byte lines:
@@ -389,13 +380,6 @@ __global__ __launch_bounds__(256) void cpy_general_quant_kernel(const cpy_args A
 }
 
 // ------------------------------------------------------------------------------------------------------------------------- host
-int cpy_fail(int code, const char *what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "lfamd_cpy: %s", what);
-    lfamd_set_error(msg);
-    return code;
-}
-
 bool pair_served(int s, int d) {
     if (s == LFAMD_TYPE_F32)
         return d == LFAMD_TYPE_F32 || d == LFAMD_TYPE_F16 || lfamd_block_k_type(d);
@@ -459,7 +443,7 @@ static bool cpy_short_row(int type, const long ne[4], const size_t nb[4]) {
     return false;
 }
 
-// The checks of include/lfamd_hip.h in their documented order, as one table (the idiom of lfamd_batched_check: evaluated whole, so
+// The checks of include/lfamd_hip.h in their documented order, as one table for lfamd_run_checks (entry_checks.h: evaluated whole, so
 // every row guards itself — a NULL ne / nb array is read as four zeros by the rows behind the first); no device call.  `entry`: asked
 // by lfamd_cpy, to which every flag is reserved; else by lfamd_cpy_check, which takes LFAMD_CHECK_UNPLACED.  true: launch.  false:
 // *rc is the answer (LFAMD_OK: an empty call).
@@ -470,19 +454,14 @@ static bool cpy_check(bool entry, int src_type, const void *d_src, const long sr
     const bool arrays = src_ne && src_nb && dst_ne && dst_nb;
     const long *s_ne = arrays ? src_ne : no_ne, *d_ne = arrays ? dst_ne : no_ne;
     const size_t *s_nb = arrays ? src_nb : no_nb, *d_nb = arrays ? dst_nb : no_nb;
-    const bool unplaced = !entry && (flags & LFAMD_CHECK_UNPLACED);
-    const unsigned reserved = entry ? flags : flags & ~LFAMD_CHECK_UNPLACED;
+    const auto [unplaced, reserved] = lfamd_check_flags_of(entry, flags);
     bool negative = false, empty = false;
     for (int i = 0; i < 4; i++)
         negative |= s_ne[i] < 0 || d_ne[i] < 0, empty |= d_ne[i] == 0;
     const long n_src = negative ? -1 : count_elements(s_ne), n_dst = negative ? -1 : count_elements(d_ne);
     const bool blocks = lfamd_block_k_type(dst_type);
     const size_t s_align = src_type == LFAMD_TYPE_F32 ? 4 : 2, d_align = dst_type == LFAMD_TYPE_F32 ? 4 : 2;
-    const struct {
-        bool hit;
-        int code;
-        const char *what;
-    } checks[] = {
+    const lfamd_check_row checks[] = {
         {!arrays, LFAMD_ERR_INVALID, "null ne / nb array"},
         {negative, LFAMD_ERR_INVALID, "negative extent"},
         {empty, LFAMD_OK, nullptr},
@@ -499,12 +478,7 @@ static bool cpy_check(bool entry, int src_type, const void *d_src, const long sr
         {cpy_short_row(src_type, s_ne, s_nb) || cpy_short_row(dst_type, d_ne, d_nb), LFAMD_ERR_INVALID, "a row stride is smaller than the row"},
         {reserved != 0, LFAMD_ERR_INVALID, "flags are reserved (0)"},
     };
-    for (const auto &c : checks)
-        if (c.hit) {
-            *rc = c.what ? cpy_fail(c.code, c.what) : c.code;
-            return false;
-        }
-    return true;
+    return lfamd_run_checks("lfamd_cpy", checks, rc);
 }
 
 extern "C" int lfamd_cpy_check(int src_type, const void *d_src, const long src_ne[4], const size_t src_nb[4], int dst_type, const void *d_dst,
@@ -570,8 +544,5 @@ extern "C" int lfamd_cpy(int src_type, const void *d_src, const long src_ne[4], 
         const unsigned grid = (unsigned)((A.n + 31) / 32);
         CPY_BY_TYPE(cpy_general_quant_kernel, grid)
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        lfamd_set_error(hipGetErrorString(e));
-    return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
+    return lfamd_launch_status(hipGetLastError());
 }

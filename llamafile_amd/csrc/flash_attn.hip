@@ -21,9 +21,8 @@
 // Scores are kept in log2 units: s2 = S * (scale * log2 e) + mask * log2 e, p = exp2(s2 - m).  A row maximum that is still -inf is
 // replaced by 0 inside the exponentials only, so exp2(-inf - -inf) never occurs.
 #include <math.h>
-#include <stdio.h>
 
-#include "lfamd_internal.h"
+#include "entry_checks.h"
 
 // keys per work-group of the decode route: a compile-time constant, so that a row's bits depend on D and n_kv alone
 #ifndef LFAMD_FA_CHUNK
@@ -115,10 +114,12 @@ __device__ static inline void fa_ld_even(const uint8_t *p, uint32_t (&W)[NW]) {
         W[j] = v.w[j];
 }
 
-// A 32-block {f16 d, payload} of TS bytes on a 2-byte boundary; NIB: 16 bytes of nibbles (element j < 16 the low nibble of byte j,
-// j + 16 its high nibble, value d * (nibble - 8)), else 32 int8 codes.
-template <int TS, bool NIB>
+// A 32-block {f16 d, payload} of TS bytes (lfamd_block32<T>) on a 2-byte boundary; NIB: 16 bytes of nibbles (element j < 16 the low
+// nibble of byte j, j + 16 its high nibble, value d * (nibble - 8)), else 32 int8 codes.
+template <int T>
 struct fa_block_op {
+    static constexpr int TS = lfamd_block32<T>::TS;
+    static constexpr bool NIB = !lfamd_block32<T>::BYTES;
     // A lane's 8 elements are 8 payload bytes; the four lanes of a block sit in one quad.  A lane loads those bytes and the two in
     // front of them through ONE address: in the quad's first lane the two are the block's d, which the quad takes from there.
     struct piece {
@@ -136,10 +137,10 @@ struct fa_block_op {
     __device__ static inline void widen8(const piece v, int sl, float (&f)[8]) { // (every lane of the quad is here)
         const float d = h2f((uint16_t)dpp_u32<0x00>(v.x[0])); // quad_perm [0,0,0,0]
         uint32_t w[2] = {(v.x[0] >> 16) | (v.x[1] << 16), (v.x[1] >> 16) | (v.hs << 16)};
-        if constexpr (NIB) { // nibble - 8 per byte (bit 7 set first: no borrow crosses a byte)
+        if constexpr (NIB) { // nibble - 8
 #pragma unroll
             for (int j = 0; j < 2; j++)
-                w[j] = ((((w[j] >> (2 * (sl & 2))) & 0x0F0F0F0Fu) | 0x80808080u) - 0x08080808u) ^ 0x80808080u;
+                w[j] = sub_per_byte<8>((w[j] >> (2 * (sl & 2))) & 0x0F0F0F0Fu);
         }
 #pragma unroll
         for (int e = 0; e < 8; e++)
@@ -199,9 +200,9 @@ struct fa_block_op {
 };
 
 template <>
-struct fa_op<LFAMD_TYPE_Q8_0> : fa_block_op<34, false> {};
+struct fa_op<LFAMD_TYPE_Q8_0> : fa_block_op<LFAMD_TYPE_Q8_0> {};
 template <>
-struct fa_op<LFAMD_TYPE_Q4_0> : fa_block_op<18, true> {};
+struct fa_op<LFAMD_TYPE_Q4_0> : fa_block_op<LFAMD_TYPE_Q4_0> {};
 
 // ------------------------------------------------------------------------------------------------------------------ decode route
 
@@ -656,30 +657,6 @@ static long fa_chunks(long n_q, long n_kv) {
     return n_q > 8 || n_kv <= FA_CHUNK ? 1 : (n_kv + FA_CHUNK - 1) / FA_CHUNK;
 }
 
-static int fa_fail(bool q, int code, const char *what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "lfamd_flash_attn%s: %s", q ? "_q" : "", what);
-    lfamd_set_error(msg);
-    return code;
-}
-
-// bytes of a K / V row of D elements
-static size_t fa_row_size(int type, long D) {
-    return type == LFAMD_TYPE_Q8_0 ? (size_t)(D / 32) * 34 : type == LFAMD_TYPE_Q4_0 ? (size_t)(D / 32) * 18 : (size_t)D * 2;
-}
-
-template <int KT, int VT, int D>
-static void fa_decode_go(const fa_args &a, int nc, dim3 grid, hipStream_t s) {
-    if (nc <= 1)
-        fa_decode_kernel<KT, VT, D, 1><<<grid, 64 * FA_NW, 0, s>>>(a);
-    else if (nc <= 2)
-        fa_decode_kernel<KT, VT, D, 2><<<grid, 64 * FA_NW, 0, s>>>(a);
-    else if (nc <= 4)
-        fa_decode_kernel<KT, VT, D, 4><<<grid, 64 * FA_NW, 0, s>>>(a);
-    else
-        fa_decode_kernel<KT, VT, D, 8><<<grid, 64 * FA_NW, 0, s>>>(a);
-}
-
 // the launches of a checked call on the pair (KT, VT)
 template <int KT, int VT>
 static void fa_go(const fa_args &a, long D, long ne3, hipStream_t s) {
@@ -687,9 +664,9 @@ static void fa_go(const fa_args &a, long D, long ne3, hipStream_t s) {
         const int nc = (int)(a.shared ? a.n_q * a.group : a.n_q);
         const dim3 grid((unsigned)a.n_chunks, (unsigned)(ne3 * (a.shared ? a.n_head_kv : a.n_head)), 1);
         if (D == 64)
-            fa_decode_go<KT, VT, 64>(a, nc, grid, s);
+            lfamd_dispatch_nc(nc, [&](auto c) { fa_decode_kernel<KT, VT, 64, decltype(c)::value><<<grid, 64 * FA_NW, 0, s>>>(a); });
         else
-            fa_decode_go<KT, VT, 128>(a, nc, grid, s);
+            lfamd_dispatch_nc(nc, [&](auto c) { fa_decode_kernel<KT, VT, 128, decltype(c)::value><<<grid, 64 * FA_NW, 0, s>>>(a); });
         if (a.n_chunks > 1) {
             const unsigned rows = (unsigned)(ne3 * a.n_head * a.n_q);
             if (D == 64)
@@ -716,7 +693,7 @@ extern "C" size_t lfamd_flash_attn_workspace(long D, long n_q, long n_kv, long n
     return chunks > 1 ? (size_t)ne3 * (size_t)n_head * (size_t)n_q * (size_t)chunks * (size_t)(D + 2) * 4 : 0;
 }
 
-// The checks of include/lfamd_hip.h in their documented order, as one table (the idiom of lfamd_batched_check: evaluated whole, so
+// The checks of include/lfamd_hip.h in their documented order, as one table for lfamd_run_checks (entry_checks.h: evaluated whole, so
 // every row guards itself); no device call.  `entry`: asked by lfamd_flash_attn, to which every flag is reserved; else by
 // lfamd_flash_attn_check, which takes LFAMD_CHECK_UNPLACED.  `q`: the table of lfamd_flash_attn_q — the pair rule, K / V on 2-byte
 // boundaries, rows of blocks.  true: launch.  false: *rc is the answer (LFAMD_OK: an empty call).
@@ -724,18 +701,13 @@ static bool fa_check(bool q, bool entry, const float *d_Q, size_t q_nb1, size_t 
                      size_t k_nb3, int Vtype, const void *d_V, size_t v_nb1, size_t v_nb2, size_t v_nb3, const void *d_mask, size_t mask_nb1, long D,
                      long n_q, long n_kv, long n_head, long n_head_kv, long ne3, float max_bias, const float *d_dst, size_t dst_nb1, size_t dst_nb2,
                      size_t dst_nb3, const void *d_workspace, size_t workspace_bytes, unsigned flags, int *rc) {
-    const bool unplaced = !entry && (flags & LFAMD_CHECK_UNPLACED);
-    const unsigned reserved = entry ? flags : flags & ~LFAMD_CHECK_UNPLACED;
+    const auto [unplaced, reserved] = lfamd_check_flags_of(entry, flags);
     const size_t need = lfamd_flash_attn_workspace(D, n_q, n_kv, n_head, n_head_kv, ne3);
     const bool f16_pair = Ktype == LFAMD_TYPE_F16 && Vtype == LFAMD_TYPE_F16;
     const bool block_pair = Ktype == Vtype && (Ktype == LFAMD_TYPE_Q8_0 || Ktype == LFAMD_TYPE_Q4_0);
     const uintptr_t qd_bits = (uintptr_t)d_Q | q_nb1 | q_nb2 | q_nb3 | (uintptr_t)d_dst | dst_nb1 | dst_nb2 | dst_nb3;
     const uintptr_t kv_bits = (uintptr_t)d_K | k_nb1 | k_nb2 | k_nb3 | (uintptr_t)d_V | v_nb1 | v_nb2 | v_nb3;
-    const struct {
-        bool hit;
-        int code;
-        const char *what;
-    } checks[] = {
+    const lfamd_check_row checks[] = {
         {D < 0 || n_q < 0 || n_kv < 0 || n_head < 0 || n_head_kv < 0 || ne3 < 0, LFAMD_ERR_INVALID, "negative dimension"},
         {n_q == 0 || n_head == 0 || ne3 == 0, LFAMD_OK, nullptr},
         {!q && !f16_pair, LFAMD_ERR_UNSUPPORTED, "F16 K and V only"},
@@ -753,17 +725,12 @@ static bool fa_check(bool q, bool entry, const float *d_Q, size_t q_nb1, size_t 
         {q && kv_bits % 2 != 0, LFAMD_ERR_INVALID, "a K / V base or stride is not a multiple of 2"},
         {d_mask && (((uintptr_t)d_mask | mask_nb1) % 2 != 0 || mask_nb1 < (size_t)n_kv * 2), LFAMD_ERR_INVALID,
          "mask base / row stride is odd or the stride is smaller than the row"},
-        {k_nb1 < fa_row_size(Ktype, D) || v_nb1 < fa_row_size(Vtype, D) || q_nb1 < (size_t)D * 4 || dst_nb1 < (size_t)D * 4, LFAMD_ERR_INVALID,
+        {k_nb1 < lfamd_row_size(Ktype, D) || v_nb1 < lfamd_row_size(Vtype, D) || q_nb1 < (size_t)D * 4 || dst_nb1 < (size_t)D * 4, LFAMD_ERR_INVALID,
          "a row stride is smaller than the row"},
         {reserved != 0, LFAMD_ERR_INVALID, "flags are reserved (0)"},
         {!unplaced && workspace_bytes < need, LFAMD_ERR_WORKSPACE, "workspace smaller than lfamd_flash_attn_workspace()"},
     };
-    for (const auto &c : checks)
-        if (c.hit) {
-            *rc = c.what ? fa_fail(q, c.code, c.what) : c.code;
-            return false;
-        }
-    return true;
+    return lfamd_run_checks(q ? "lfamd_flash_attn_q" : "lfamd_flash_attn", checks, rc);
 }
 
 // the argument lists of the exported calls, written once
@@ -807,10 +774,7 @@ static int fa_call(bool q, FA_CALL_PARAMS) {
         fa_go<LFAMD_TYPE_Q4_0, LFAMD_TYPE_Q4_0>(a, D, ne3, s);
     else
         fa_go<LFAMD_TYPE_F16, LFAMD_TYPE_F16>(a, D, ne3, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        lfamd_set_error(hipGetErrorString(e));
-    return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
+    return lfamd_launch_status(hipGetLastError());
 }
 
 extern "C" int lfamd_flash_attn_check(FA_CHECK_PARAMS) {

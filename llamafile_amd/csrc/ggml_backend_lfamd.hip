@@ -855,6 +855,20 @@ bool fa_block_cache(const fa_call &c) {
     return c.ktype == LFAMD_TYPE_Q8_0 || c.ktype == LFAMD_TYPE_Q4_0;
 }
 
+// the two argument lists, each written once (the pairs of functions have one signature each)
+int fa_check(const fa_call &c) { // what supports_op asks: no addresses yet, no workspace
+    return (fa_block_cache(c) ? lfamd_flash_attn_q_check : lfamd_flash_attn_check)(
+        (const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v, c.v_nb[1], c.v_nb[2],
+        c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.max_bias, (const float *)c.dst, c.dst_nb[1],
+        c.dst_nb[2], c.dst_nb[3], nullptr, 0, LFAMD_CHECK_UNPLACED);
+}
+int fa_run(const fa_call &c, void *ws, size_t ws_bytes) {
+    return (fa_block_cache(c) ? lfamd_flash_attn_q : lfamd_flash_attn)(
+        (const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v, c.v_nb[1], c.v_nb[2],
+        c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.scale, c.max_bias, (float *)c.dst, c.dst_nb[1],
+        c.dst_nb[2], c.dst_nb[3], ws, ws_bytes, 0u, nullptr);
+}
+
 // beside lfamd_flash_attn_check / lfamd_flash_attn_q_check: the switch, the ggml types and nb[0], the extents of K / V / dst / mask against Q, a contiguous dst
 // and the precision — what the call's argument list does not carry
 bool flash_attn_supported(const struct ggml_tensor *op) {
@@ -874,15 +888,9 @@ bool flash_attn_supported(const struct ggml_tensor *op) {
     if (op->op_params[2] != 0 /* GGML_PREC_DEFAULT */)
         return false;
     const fa_call c = fa_call_of(op, false);
-    if (fa_block_cache(c)) // a Q8_0 / Q4_0 K: lfamd_flash_attn_q's table (which refuses a V of another type)
-        return type_ok(c.ktype) && type_ok(c.vtype) &&
-               lfamd_flash_attn_q_check((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype,
-                                        c.v, c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3,
-                                        c.max_bias, (const float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], nullptr, 0,
-                                        LFAMD_CHECK_UNPLACED) == LFAMD_OK;
-    return lfamd_flash_attn_check((const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v,
-                                  c.v_nb[1], c.v_nb[2], c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.max_bias,
-                                  (const float *)c.dst, c.dst_nb[1], c.dst_nb[2], c.dst_nb[3], nullptr, 0, LFAMD_CHECK_UNPLACED) == LFAMD_OK;
+    if (fa_block_cache(c) && !(type_ok(c.ktype) && type_ok(c.vtype))) // a Q8_0 / Q4_0 K: lfamd_flash_attn_q's table refuses a V of another type
+        return false;
+    return fa_check(c) == LFAMD_OK;
 }
 
 // ONE lfamd_flash_attn / lfamd_flash_attn_q on the tensors' own pointers and nb[]
@@ -890,13 +898,8 @@ enum ggml_status run_flash_attn(backend_ctx *ctx, struct ggml_tensor *dst) {
     const fa_call c = fa_call_of(dst, true);
     if (!grow(ctx->ws, ctx->ws_cap, lfamd_flash_attn_workspace(c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3)))
         return GGML_STATUS_ALLOC_FAILED;
-    const bool q = fa_block_cache(c);
-    const int rc = (q ? lfamd_flash_attn_q : lfamd_flash_attn)(
-        (const float *)c.q, c.q_nb[1], c.q_nb[2], c.q_nb[3], c.ktype, c.k, c.k_nb[1], c.k_nb[2], c.k_nb[3], c.vtype, c.v, c.v_nb[1], c.v_nb[2],
-        c.v_nb[3], c.mask, c.mask_nb1, c.D, c.n_q, c.n_kv, c.n_head, c.n_head_kv, c.ne3, c.scale, c.max_bias, (float *)c.dst, c.dst_nb[1],
-        c.dst_nb[2], c.dst_nb[3], ctx->ws, ctx->ws_cap, 0u, nullptr);
-    if (rc != LFAMD_OK) {
-        logf("ggml_backend_lfamd: %s: %s\n", q ? "lfamd_flash_attn_q" : "lfamd_flash_attn", lfamd_last_error());
+    if (fa_run(c, ctx->ws, ctx->ws_cap) != LFAMD_OK) {
+        logf("ggml_backend_lfamd: %s: %s\n", fa_block_cache(c) ? "lfamd_flash_attn_q" : "lfamd_flash_attn", lfamd_last_error());
         return GGML_STATUS_FAILED;
     }
     ctx->flash_attn_calls++;

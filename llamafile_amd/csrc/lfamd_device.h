@@ -150,6 +150,30 @@ __device__ static inline int sdot4(uint32_t a, uint32_t b, int c) { // signed i8
     return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
 }
 
+// ---- a 32-block of the K / V cache types (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL; include/lfamd_blocks.h): {f16 d, [f16 m,]
+// payload}, the payload [4 bytes of fifth bits,] 16 bytes of nibbles — or Q8_0's 32 codes.  The one description the attention and
+// cache kernels (mul_mat_batched_q.hip, flash_attn.hip, cpy.hip) instantiate on.
+template <int T>
+struct lfamd_block32 {
+    static constexpr bool S1 = T == LFAMD_TYPE_Q4_1 || T == LFAMD_TYPE_Q5_1;   // has m
+    static constexpr bool FIVE = T == LFAMD_TYPE_Q5_0 || T == LFAMD_TYPE_Q5_1; // fifth bits in front of the nibbles
+    static constexpr bool BYTES = T == LFAMD_TYPE_Q8_0;                        // byte codes, else nibbles
+    static constexpr int PAY = S1 ? 4 : 2;              // offset of the payload
+    static constexpr int NW = BYTES ? 8 : FIVE ? 5 : 4; // its dwords
+    static constexpr int TS = PAY + 4 * NW;             // bytes of a block
+};
+static_assert(lfamd_block32<LFAMD_TYPE_Q8_0>::TS == sizeof(lfamd_block_q8_0) && lfamd_block32<LFAMD_TYPE_Q4_0>::TS == sizeof(lfamd_block_q4_0) &&
+                  lfamd_block32<LFAMD_TYPE_Q4_1>::TS == sizeof(lfamd_block_q4_1) && lfamd_block32<LFAMD_TYPE_Q5_0>::TS == sizeof(lfamd_block_q5_0) &&
+                  lfamd_block32<LFAMD_TYPE_Q5_1>::TS == sizeof(lfamd_block_q5_1) && lfamd_block32<LFAMD_TYPE_IQ4_NL>::TS == sizeof(lfamd_block_iq4_nl),
+              "lfamd_block32 and the structs of lfamd_blocks.h differ");
+
+// code - S in each of the four bytes of x (codes below 128, S = 8: a Q4_0 nibble, 16: a Q5_0 code): bit 7 is set first, so no borrow
+// crosses a byte
+template <uint32_t S>
+__device__ __forceinline__ uint32_t sub_per_byte(uint32_t x) {
+    return ((x | 0x80808080u) - S * 0x01010101u) ^ 0x80808080u;
+}
+
 // The 16-entry int8 codebook of IQ4_NL / IQ4_XS (kvalues_iq4nl), four indices (one per byte) -> four values: four constant
 // registers and three v_perm per four codes: the lower and the upper eight entries by the index's low three bits, then byte i of
 // one or the other by its bit 3.

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void mmb_mfma_kernel(const mmb_args a) {
 
 template <int LPR, bool ALIGNED>
 void gemv_go(const mmb_args &a, dim3 grid, hipStream_t s) {
-    lfamd_batched_nc(a.hg * (int)a.n, [&](auto nc) { mmb_gemv_kernel<LPR, decltype(nc)::value, ALIGNED><<<grid, 256, 0, s>>>(a); });
+    lfamd_dispatch_nc(a.hg * (int)a.n, [&](auto nc) { mmb_gemv_kernel<LPR, decltype(nc)::value, ALIGNED><<<grid, 256, 0, s>>>(a); });
 }
 
 } // namespace
@@ -259,8 +259,5 @@ extern "C" int lfamd_mul_mat_batched(int Atype, const void *d_A, long m, long k,
         else
             mmb_mfma_kernel<false><<<grid, 256, 0, s>>>(a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        lfamd_set_error(hipGetErrorString(e));
-    return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
+    return lfamd_launch_status(hipGetLastError());
 }

@@ -3,11 +3,7 @@
 //     C[i3][i2][j][i] = sum_l A[i3 / r3][i2 / r2][i][l] * B[i3][i2][j][l],   r2 = ne2 / a_ne2, r3 = ne3 / a_ne3
 // of include/lfamd_hip.h.  Not shared, on purpose: the load helpers, the arithmetic, the kernels, the units.
 #pragma once
-#include <stdio.h>
-
-#include <type_traits>
-
-#include "lfamd_internal.h"
+#include "entry_checks.h"
 
 // ---- the slice geometry, the head of both kernels' argument structs: initialised from the argument list up to ne2, checked, completed
 struct lfamd_batched_geom {
@@ -60,14 +56,10 @@ struct lfamd_batched_desc { // what an entry point asks of A, and how it says no
 };
 
 // The checks of include/lfamd_hip.h in their documented order (r2 and r3 are not set yet); no device call.  true: launch.  false: *rc
-// is the entry point's answer (LFAMD_OK: an empty call).  The table is evaluated whole, so every condition guards itself.
+// is the entry point's answer (LFAMD_OK: an empty call).  The table is evaluated whole, so every condition guards itself (entry_checks.h).
 static inline bool lfamd_batched_check(const char *name, const lfamd_batched_desc &d, const lfamd_batched_geom &a, long a_ne3, long ne3,
                                        unsigned flags, int *rc) {
-    const struct {
-        bool hit;
-        int code;
-        const char *what;
-    } checks[] = {
+    const lfamd_check_row checks[] = {
         {a.m < 0 || a.k < 0 || a.n < 0 || a.ne2 < 0 || ne3 < 0 || a.a_ne2 < 0 || a_ne3 < 0, LFAMD_ERR_INVALID, "negative dimension"},
         {a.m == 0 || a.n == 0 || a.ne2 == 0 || ne3 == 0, LFAMD_OK, nullptr},
         {!d.type_ok, LFAMD_ERR_UNSUPPORTED, d.type_msg},
@@ -85,16 +77,7 @@ static inline bool lfamd_batched_check(const char *name, const lfamd_batched_des
          "B / C bases / strides are not multiples of 4"},
         {flags != 0, LFAMD_ERR_INVALID, "flags are reserved (0)"},
     };
-    for (const auto &c : checks)
-        if (c.hit) {
-            char msg[192];
-            snprintf(msg, sizeof(msg), "%s: %s", name, c.what ? c.what : "");
-            if (c.what)
-                lfamd_set_error(msg);
-            *rc = c.code;
-            return false;
-        }
-    return true;
+    return lfamd_run_checks(name, checks, rc);
 }
 
 // Of a call that passed the checks: r2, r3, and for the GEMV bodies (n <= 8) hg = min(r2, 8 / n) query heads per item, so that a lane
@@ -103,12 +86,4 @@ static inline void lfamd_batched_groups(lfamd_batched_geom &a, long a_ne3, long 
     a.r2 = a.ne2 / a.a_ne2, a.r3 = ne3 / a_ne3;
     hg = a.n > 8 ? 1 : (int)(8 / a.n < a.r2 ? 8 / a.n : a.r2);
     hchunks = a.n > 8 ? 1 : (int)((a.r2 + hg - 1) / hg);
-}
-
-// f(lfamd_nc<NC>{}) for the smallest NC of 1, 2, 4, 8 that holds nc_max columns: NC reaches the callable as a compile-time constant
-template <int NC>
-using lfamd_nc = std::integral_constant<int, NC>;
-template <typename F>
-static inline void lfamd_batched_nc(int nc_max, F &&f) {
-    nc_max <= 1 ? f(lfamd_nc<1>{}) : nc_max <= 2 ? f(lfamd_nc<2>{}) : nc_max <= 4 ? f(lfamd_nc<4>{}) : f(lfamd_nc<8>{});
 }

@@ -40,16 +40,8 @@ struct mmq_args : lfamd_batched_geom {
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v16i_t __attribute__((ext_vector_type(16)));
 
-// a weight block: {f16 d, [f16 m,] payload}; the payload is [4 bytes of fifth bits,] 16 bytes of nibbles — or Q8_0's 32 codes
 template <int T>
-struct wt {
-    static constexpr bool S1 = T == LFAMD_TYPE_Q4_1 || T == LFAMD_TYPE_Q5_1;   // has m: activations are Q8_1
-    static constexpr bool FIVE = T == LFAMD_TYPE_Q5_0 || T == LFAMD_TYPE_Q5_1; // fifth bits in front of the nibbles
-    static constexpr bool BYTES = T == LFAMD_TYPE_Q8_0;
-    static constexpr int PAY = S1 ? 4 : 2;                // offset of the payload
-    static constexpr int NW = BYTES ? 8 : FIVE ? 5 : 4;   // its dwords
-    static constexpr int TS = PAY + 4 * NW;               // bytes of a block
-};
+using wt = lfamd_block32<T>; // a weight block (S1: the activations are Q8_1)
 
 // 4 NW bytes from the EVEN address p, whose two bytes in front (p - 2, p - 1) belong to the same block: aligned dwords, plus one 2-byte
 // load where p is not a multiple of 4.  Nothing outside [p - 2, p + 4 NW) is read.
@@ -83,10 +75,10 @@ __device__ static inline void w_codes(const uint32_t (&P)[wt<T>::NW], int h, uin
                 const uint32_t t = (P[0] >> (16 * h + 4 * j)) & 0xFu;
                 x |= ((t * 0x00204081u) & 0x01010101u) << 4;
             }
-            if constexpr (T == LFAMD_TYPE_Q4_0) // q - 8 per byte (bit 7 set first: no borrow crosses a byte)
-                x = ((x | 0x80808080u) - 0x08080808u) ^ 0x80808080u;
+            if constexpr (T == LFAMD_TYPE_Q4_0) // q - 8
+                x = sub_per_byte<8>(x);
             else if constexpr (T == LFAMD_TYPE_Q5_0) // q - 16
-                x = ((x | 0x80808080u) - 0x10101010u) ^ 0x80808080u;
+                x = sub_per_byte<16>(x);
             else if constexpr (T == LFAMD_TYPE_IQ4_NL)
                 x = kvalues_lut4(x);
             c[j] = x; // (Q4_1, Q5_1: the unsigned q, below 32)
@@ -376,7 +368,7 @@ hipError_t launch(const mmq_args &a, long ne3, hipStream_t s) {
     using W = wt<T>;
     if (a.n <= 8) {
         const dim3 grid((unsigned)((a.m + 63) / 64), (unsigned)(ne3 * a.a_ne2 * a.hchunks), 1);
-        lfamd_batched_nc(a.hg * (int)a.n, [&](auto nc) { mmq_gemv_kernel<T, decltype(nc)::value><<<grid, 256, 0, s>>>(a); });
+        lfamd_dispatch_nc(a.hg * (int)a.n, [&](auto nc) { mmq_gemv_kernel<T, decltype(nc)::value><<<grid, 256, 0, s>>>(a); });
     } else {
         const size_t smem = (size_t)a.kb * (2048 + 256 * (W::S1 ? 2 : 1));
         if (smem > 64 * 1024) {
@@ -417,8 +409,5 @@ extern "C" int lfamd_mul_mat_batched_q(int Atype, const void *d_A, long m, long 
         return rc;
     a.kb = (int)(k / 32);
     lfamd_batched_groups(a, a_ne3, ne3, a.hg, a.hchunks);
-    const hipError_t e = launch(Atype, a, ne3, (hipStream_t)stream);
-    if (e != hipSuccess)
-        lfamd_set_error(hipGetErrorString(e));
-    return e != hipSuccess ? LFAMD_ERR_HIP : LFAMD_OK;
+    return lfamd_launch_status(launch(Atype, a, ne3, (hipStream_t)stream));
 }

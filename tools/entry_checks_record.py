@@ -1,6 +1,7 @@
-"""Record what lfamd_flash_attn and lfamd_cpy of a library built at the parent commit answer to the refused and the empty calls of
-tests/entry_checks_cases.py: tests/golden/entry_checks_parent.json, (rc, message) per case, which tests/test_entry_checks.py holds
-this tree's lfamd_flash_attn_check and lfamd_cpy_check to.  The calls carry made-up addresses, so only cases their author marked
+"""Record what the entry points of a library built at the parent commit (every operator of tests/entry_checks_cases.py: the two
+flash-attention calls, lfamd_cpy, the two batched products) answer to the refused and the empty calls of that module:
+tests/golden/entry_checks_parent.json, (rc, message) per case, which tests/test_entry_checks.py holds this tree's check functions
+and entry points to.  The calls carry made-up addresses, so only cases their author marked
 REFUSED or EMPTY are sent — a refusal comes before any device call — and never where a GPU is present: a call that passed the checks
 after all would launch on those addresses.  Without a device such a call answers LFAMD_ERR_HIP, which fails the recording.
 
