@@ -1,7 +1,14 @@
-// gemm_common.h — pieces shared by the MFMA GEMM kernels (gemm_mfma.hip, gemm_wide.hip): exact-integer
-// dequantisation of packed K-quant dwords into f16 MFMA fragments, and the XCD-aware tile order.
+// gemm_common.h — what the MFMA batch bodies share (gemm_mfma, gemm_wide_*, gemm_lw, gemm_ks, gemm_kr, gemm_i8, gemm_lf, gemm_sb):
+//   * exact-integer dequantisation of packed K-quant dwords into f16 MFMA fragments;
+//   * the XCD-aware tile order and the work-group tile prologues built on it (XCD_ORDER, WG_TILE_AT, MOE_TILE_OR_RETURN);
+//   * gemm_mats, the by-value table of a fused launch, and its host filler fill_gemm_mats;
+//   * the inline-asm issue forms: loads with their own wait states (gload*, glds*), the lean ones (dma16, dma4, ld16, dsr16).
+// A new body starts from these and writes its own K loop and epilogue.
 #pragma once
 #include "lfamd_device.h"
+#ifndef GEMM_DIAG
+#define GEMM_DIAG 0 // development builds of one unit: 1, 2 ablations (gemm_mfma, gemm_wide); 3, 4, 6, 7 stamps (diag_stamps.h)
+#endif
 
 #define XT_ROW_BYTES 512 // 256 f16 codes of one token for one super-block
 
@@ -209,5 +216,182 @@ __device__ static inline void tile_of(int L, int n_rb, int n_tt, int &rb, int &t
     const int tl = rem / hgt;
     rb = run * SA + (rem - tl * hgt);
     tt = g * SB + tl;
+}
+
+// Up to GEMM_MAX_MATS weight matrices of one type and row length that consume the SAME activations (attn_q/k/v,
+// ffn_gate/up) share one prep and one launch: their 128-row blocks are concatenated (rb_end = exclusive prefix).
+#define GEMM_MAX_MATS 4
+struct gemm_mats {
+    const uint8_t *A[GEMM_MAX_MATS];
+    float *C[GEMM_MAX_MATS];
+    long m[GEMM_MAX_MATS];
+    long ldc[GEMM_MAX_MATS];
+    int rb_end[GEMM_MAX_MATS];
+    int count;
+    // GGML_OP_MUL_MAT_ID batches (MOE kernels only): A[0] = the expert stack, C[0] = result rows; token slots are grouped
+    // by expert on the device (moe.hip, moe_route_kernel): expert e owns slots [poff[e], poff[e] + cnt[e]), slot -> result
+    // row through slot_row.  The grid covers the worst case; work-groups beyond an expert's count exit at once.
+    const int *moe_cnt, *moe_poff, *moe_slot_row;
+    long expert_bytes;
+    int moe_ct_max;
+};
+
+// The matrices of a launch with m > 0, padded to GEMM_MAX_MATS with empty ones; returns their row blocks of 128
+// (mats.count == 0: an empty launch, nothing else is set).
+static inline int fill_gemm_mats(gemm_mats &mats, int count, const void *const *A, const long *m, float *const *C, const long *ldc) {
+    int n_rb = 0;
+    mats.count = 0;
+    mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
+    for (int j = 0; j < count; j++) {
+        if (m[j] <= 0)
+            continue;
+        const int i = mats.count++;
+        mats.A[i] = (const uint8_t *)A[j], mats.C[i] = C[j], mats.m[i] = m[j], mats.ldc[i] = ldc[j];
+        n_rb += (int)((m[j] + 127) / 128);
+        mats.rb_end[i] = n_rb;
+    }
+    for (int i = mats.count; i < GEMM_MAX_MATS && mats.count > 0; i++)
+        mats.A[i] = mats.A[0], mats.C[i] = mats.C[0], mats.m[i] = 0, mats.ldc[i] = 0, mats.rb_end[i] = n_rb;
+    return n_rb;
+}
+
+// ---- the work-group tile prologues
+// Block ids go round-robin over the 8 XCDs.  XCD_ORDER gives every XCD one contiguous run of the linear order of the n_wg
+// work-groups (q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7: XCD xcd starts at xcd * q8 + min(xcd, r8) and takes its (id >> 3)-th):
+// an XCD's resident work-groups then walk neighbouring tiles of tile_of's super-tiles and share weight rows and activation rows
+// in that XCD's L2 (row blocks fastest, the first order tried, had every XCD stream every weight row).
+//
+// The three pieces below are macros, not functions: a helper that returns {rb, ct, mj} leaves the instruction mix of a body as
+// it is but renames registers and reorders its first instructions, even the permutation alone as an inline function commuted the
+// operands of one s_mul in gemm_lw's two-type kernel, and a body whose ISA moved owes a timing.  A macro
+// expands to the statements the bodies held and moves nothing.
+#define XCD_ORDER(block_id, wgs)                                                                                       \
+    ({                                                                                                                 \
+        const int n_wg_ = (wgs); /* (trailing underscores: the arguments may be called n_wg and id) */                 \
+        const int id_ = (block_id), q8_ = n_wg_ >> 3, r8_ = n_wg_ & 7, xcd_ = id_ & 7;                                 \
+        (xcd_ < r8_ ? xcd_ * (q8_ + 1) : r8_ * (q8_ + 1) + (xcd_ - r8_) * q8_) + (id_ >> 3);                           \
+    })
+
+// WG_TILE_AT: position L of the linear order over n_rb x n_ct tiles -> (row block rb, token tile ct) and the matrix mj of a fused
+// launch that the row block belongs to, with rb rebased onto that matrix.  L = XCD_ORDER(block id, n_rb * n_ct); a launch whose K
+// is split over ks work-groups per tile orders n_rb * n_ct * ks of them, K part slowest (L / tiles), and passes L % tiles.
+#define WG_TILE_AT(mats, L, n_rb, n_ct, rb, ct, mj)                                                                    \
+    do {                                                                                                               \
+        tile_of(L, n_rb, n_ct, rb, ct);                                                                                \
+        mj = 0;                                                                                                        \
+        _Pragma("unroll") for (int jj = 1; jj < GEMM_MAX_MATS; jj++)                                                   \
+            if (jj < (mats).count && rb >= (mats).rb_end[jj - 1])                                                      \
+                mj = jj;                                                                                               \
+        if (mj > 0)                                                                                                    \
+            rb -= (mats).rb_end[mj - 1];                                                                               \
+    } while (0)
+
+// GGML_OP_MUL_MAT_ID: work-group `bid` of `gdim` = (token tile of `cols` slots, expert, row block), row blocks fastest and the
+// token tile slowest: consecutive ids go round-robin over the XCDs, so the live tiles (low token-tile index) spread over all
+// eight instead of piling onto XCD 0 and 1, and they are dispatched before the tiles that only exit.  The routing kernel ran
+// earlier on this stream.  Yields rb, ct, moe_left = the token slots of this tile that carry a row, A = the expert's weights and
+// n0 = the tile's first slot — and RETURNS from the kernel when the tile carries none (uniform over the work-group).  It declares
+// per_ct, rem and e, so it stands first in the MUL_MAT_ID block of a kernel.  bid, gdim: ints, or the built-in unsigned block index
+// and grid size as they are (the wide kernel divides them unsigned).
+#define MOE_TILE_OR_RETURN(mats, bid, gdim, n_rb, cols, rb, ct, moe_left, A, n0)                                       \
+    const int per_ct = (int)((gdim) / (mats).moe_ct_max); /* experts * n_rb */                                         \
+    ct = (bid) / per_ct;                                                                                               \
+    const int rem = (bid)-ct * per_ct;                                                                                 \
+    const int e = rem / n_rb;                                                                                          \
+    rb = rem - e * n_rb;                                                                                               \
+    moe_left = (mats).moe_cnt[e] - ct * (cols);                                                                        \
+    if (moe_left <= 0)                                                                                                 \
+        return;                                                                                                        \
+    A = (mats).A[0] + (size_t)e * (mats).expert_bytes;                                                                 \
+    n0 = (long)(mats).moe_poff[e] + (long)ct * (cols)
+
+// ---- issue forms
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// make a wave-uniform pointer provably so (an "s" operand must be), via two v_readfirstlane
+__device__ static inline const uint8_t *uniform_ptr(const void *p) {
+    const uint64_t v = (uint64_t)(uintptr_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return (const uint8_t *)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ static inline uint32_t lds_addr(const void *p) {
+    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)(const uint8_t *)p);
+}
+
+// Forms that carry their own wait states: a VALU write of an SGPR — v_readfirstlane, so uniform_ptr() — needs five wait states
+// before a vector-memory instruction reads that SGPR, and hipcc's hazard recogniser does not see inside an asm statement.  These
+// lead with `s_nop 4`, and the glds* save and restore M0.
+template <int IMM>
+__device__ static inline void gload16(u32x4 &dst, const void *base, uint32_t voff) {
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
+}
+template <int IMM>
+__device__ static inline void gload4(uint32_t &dst, const void *base, uint32_t voff) {
+    asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
+}
+template <int IMM>
+__device__ static inline void gload2(uint32_t &dst, const void *base, uint32_t voff) {
+    asm volatile("s_nop 4\n\tglobal_load_ushort %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
+}
+
+// four LDS-DMA pieces (1 KiB each) to consecutive LDS slots from one SGPR base + per-lane offsets
+__device__ static inline void glds4(const void *base, uint32_t lds_dst, uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3) {
+    uint32_t keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\t"
+                 "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "s"(base), "s"(lds_dst)
+                 : "memory", "scc");
+}
+__device__ static inline void glds1x16(const void *base, uint32_t lds_dst, uint32_t o0) {
+    uint32_t keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(o0), "s"(base), "s"(lds_dst)
+                 : "memory");
+}
+__device__ static inline void glds1x4(const void *base, uint32_t lds_dst, uint32_t o0) {
+    uint32_t keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(o0), "s"(base), "s"(lds_dst)
+                 : "memory");
+}
+
+// LEAN forms, one instruction each (plus the M0 write of an LDS-DMA piece: 64 lanes x 16 B, or x 4 B, from base + voff to LDS at
+// lds_dst + 16, or 4, * lane).  Their asm carries no wait states: the bodies that use them keep their addresses in SGPRs by
+// scalar adds and follow uniform_ptr() with an `s_nop 4` fence that consumes the pointers; tools/isa_hazards.py checks the rule
+// on the final ISA.  M0 is written and never restored (nothing else in those kernels reads it).
+// dma16<IMM>: LDS address lds_dst + IMM (one s_add; a plain offset field would move the global address too)
+template <int IMM>
+__device__ static inline void dma16(const void *base, uint32_t lds_dst, uint32_t voff) {
+    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst), "n"(IMM) : "memory", "scc");
+}
+__device__ static inline void dma16(const void *base, uint32_t lds_dst, uint32_t voff) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
+}
+__device__ static inline void dma4(const void *base, uint32_t lds_dst, uint32_t voff) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
+}
+template <int IMM>
+__device__ static inline void ld16(u32x4 &dst, const void *base, uint32_t voff) {
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
+}
+// LDS fragment read hipcc neither counts nor moves: the K loops keep the next K-step's fragments in flight under the current
+// step's MFMAs and wait with a counted lgkmcnt (left to itself hipcc reuses ONE fragment register and waits lgkmcnt(0) in front
+// of every MFMA — the whole LDS latency, 64 times per super-block).  V: half8_t or u32x4.
+template <int IMM, class V>
+__device__ static inline void dsr16(V &dst, uint32_t addr) {
+    static_assert(sizeof(V) == 16, "ds_read_b128 fills four registers");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
+}
+template <int N>
+__device__ static inline void ds_wait(half8_t &a, half8_t &b) {
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
 }
 

@@ -23,7 +23,7 @@
 // instruction costs its issuer 60-180 cycles, which a computing wave does not have), three stages ahead in a ring of four; ONE
 // barrier per super-block, placed so that the NEXT stage has landed before the current one is computed — its first operands
 // are read before the barrier they would otherwise wait behind.
-#include "gemm_wide_impl.h"
+#include "gemm_common.h"
 #include "lfamd_internal.h"
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
@@ -42,30 +42,18 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 #if GEMM_DIAG == 7 // development: s_memtime stamps of one work-group's waves 0 and 4 (tools/i8_stamps.py)
 #define I8_STAMP_WG 100
-__device__ unsigned long long g_i8_stamps[2 * 256];
-extern "C" int lfamd_debug_i8_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_i8_stamps), sizeof(g_i8_stamps));
-}
+#define DIAG_STAMPS (2 * 256)
+#include "diag_stamps.h"
 #define ISTAMP()                                                                                                     \
     do {                                                                                                             \
         if (blockIdx.x == I8_STAMP_WG && lane == 0 && rw == 0 && stamp_n < 256)                                      \
-            g_i8_stamps[tw * 256 + stamp_n++] = __builtin_amdgcn_s_memtime();                                        \
+            g_stamps[tw * 256 + stamp_n++] = DIAG_CLOCK();                                                           \
     } while (0)
 #else
 #define ISTAMP()
 #endif
 
-// LDS-DMA piece: 64 lanes x 16 B from base + voff to LDS at lds_dst + 16 * lane.  SGPR base kept by scalar adds; M0 written and
-// not restored (nothing else in this kernel reads it).  No offset field: it would move the LDS address too.
-__device__ static inline void i8_dma16(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
-}
-// LDS reads hipcc neither counts nor moves (left alone it fetches a fragment right in front of its MFMA and waits lgkmcnt(0))
-template <int IMM>
-__device__ static inline void i8_dsr(u32x4 &dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
-
+// (everything arrives in the lean issue forms of gemm_common.h: dma16 without an immediate, dsr16)
 __device__ static inline uint32_t pk_mul_u16(uint32_t bytes, uint32_t pair) { // four byte products (<= 105 each: no carries)
     const u16x2_t r = __builtin_bit_cast(u16x2_t, bytes) * __builtin_bit_cast(u16x2_t, pair);
     return __builtin_bit_cast(uint32_t, r);
@@ -74,28 +62,16 @@ __device__ static inline uint32_t pk_mul_u16(uint32_t bytes, uint32_t pair) { //
 __global__ __launch_bounds__(512) void gemm_i8_kernel(const gemm_mats mats, int nb, const int8_t *__restrict__ Xq,
                                                       const float *__restrict__ d8T, const _Float16 *__restrict__ Xs, long n,
                                                       long n_pad, int n_rb, int n_ct) {
-#ifdef I8_CHECK_NB // tools/isa_hazards.py: a fixed trip count
-    nb = I8_CHECK_NB;
+#ifdef GEMM_CHECK_TRIPS // tools/isa_hazards.py: a fixed trip count
+    nb = GEMM_CHECK_TRIPS;
 #endif
     __shared__ __attribute__((aligned(16))) uint8_t lds[I8_STAGES * I8_SLOT];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, h = lane >> 5;
 
-    // ---- tile of this work-group (the order of gemm_ks: XCD-aware super-tiles)
-    int rb, ct;
-    {
-        const int n_wg = n_rb * n_ct;
-        const int id = (int)blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-        tile_of(L, n_rb, n_ct, rb, ct);
-    }
-    int mj = 0;
-#pragma unroll
-    for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-        if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-            mj = jj;
-    if (mj > 0)
-        rb -= mats.rb_end[mj - 1];
+    // ---- tile of this work-group
+    int rb, ct, mj;
+    WG_TILE_AT(mats, XCD_ORDER((int)blockIdx.x, n_rb * n_ct), n_rb, n_ct, rb, ct, mj);
     const uint8_t *__restrict__ A = mats.A[mj];
     float *__restrict__ C = mats.C[mj];
     const long m = mats.m[mj], ldc = mats.ldc[mj];
@@ -136,15 +112,15 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(const gemm_mats mats, int 
         // reads them: hipcc pads such hazards itself, but not in front of an asm statement (tools/isa_hazards.py checks the ISA)
         asm volatile("s_nop 4" ::"s"(wt_n), "s"(xq_n), "s"(p8_n), "s"(d8_n));
         auto dma_stage = [&](uint32_t slot_base) {
-            i8_dma16(wt_n, slot_base + dstW, voffW);
-            i8_dma16(wt_n, slot_base + dstW + 1024, voffW + 1024);
-            i8_dma16(wt_n, slot_base + dstW + 2048, voffW + 2048);
-            i8_dma16(wt_n, slot_base + dstW + 3072, voffW + 3072);
+            dma16(wt_n, slot_base + dstW, voffW);
+            dma16(wt_n, slot_base + dstW + 1024, voffW + 1024);
+            dma16(wt_n, slot_base + dstW + 2048, voffW + 2048);
+            dma16(wt_n, slot_base + dstW + 3072, voffW + 3072);
 #pragma unroll
             for (int e = 0; e < 4; e++)
-                i8_dma16(xq_n, slot_base + dstX + (uint32_t)(e * 1024), voffX[e]);
-            i8_dma16(p8_n, slot_base + dst8, voff8);
-            i8_dma16(d8_n, slot_base + (uint32_t)I8_D, voffD);
+                dma16(xq_n, slot_base + dstX + (uint32_t)(e * 1024), voffX[e]);
+            dma16(p8_n, slot_base + dst8, voff8);
+            dma16(d8_n, slot_base + (uint32_t)I8_D, voffD);
             wt_n += P4K_TILE, xq_n += xstride, p8_n += stride8, d8_n += dstride; // (past the last super-block nothing more is issued)
         };
 #pragma unroll
@@ -207,12 +183,12 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(const gemm_mats mats, int 
     //   loop's back edge (where hipcc may copy registers).
     u32x4 HD, Q[2], XF[4][2], SF[2], DF[8];
     {
-        i8_dsr<0>(HD, adH);
-        i8_dsr<0>(Q[0], adQ);
-        i8_dsr<0>(XF[0][0], adX[0]);
-        i8_dsr<8192>(XF[0][1], adX[0]);
-        i8_dsr<0>(XF[1][0], adX[1]);
-        i8_dsr<8192>(XF[1][1], adX[1]);
+        dsr16<0>(HD, adH);
+        dsr16<0>(Q[0], adQ);
+        dsr16<0>(XF[0][0], adX[0]);
+        dsr16<8192>(XF[0][1], adX[0]);
+        dsr16<0>(XF[1][0], adX[1]);
+        dsr16<8192>(XF[1][1], adX[1]);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(HD), "+v"(Q[0]), "+v"(XF[0][0]), "+v"(XF[0][1]), "+v"(XF[1][0]), "+v"(XF[1][1]));
     }
 
@@ -238,23 +214,23 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(const gemm_mats mats, int 
         for (int jb = 0; jb < 8; jb++) {
             // look-ahead: the fragments of sub-block jb + 2; at even jb the nibble group of sub-blocks jb + 2, jb + 3
             if (jb + 2 < 8) {
-                i8_dsr<0>(XF[(jb + 2) & 3][0], adX[jb + 2] + so);
-                i8_dsr<8192>(XF[(jb + 2) & 3][1], adX[jb + 2] + so);
+                dsr16<0>(XF[(jb + 2) & 3][0], adX[jb + 2] + so);
+                dsr16<8192>(XF[(jb + 2) & 3][1], adX[jb + 2] + so);
                 if ((jb & 1) == 0)
-                    i8_dsr<0>(Q[((jb >> 1) + 1) & 1], adQ + so + (uint32_t)(((jb >> 1) + 1) * 1024));
+                    dsr16<0>(Q[((jb >> 1) + 1) & 1], adQ + so + (uint32_t)(((jb >> 1) + 1) * 1024));
             }
             if (jb == 4) { // the bsums fragments (their MFMAs go right behind the K loop's last)
-                i8_dsr<0>(SF[0], adS + so);
-                i8_dsr<1024>(SF[1], adS + so);
+                dsr16<0>(SF[0], adS + so);
+                dsr16<1024>(SF[1], adS + so);
             } else if (jb == 6) { // both token tiles' d8, early enough to have landed when the epilogue starts
-                i8_dsr<0>(DF[0], adD + so);
-                i8_dsr<32>(DF[1], adD + so);
-                i8_dsr<64>(DF[2], adD + so);
-                i8_dsr<96>(DF[3], adD + so);
-                i8_dsr<128>(DF[4], adD + so);
-                i8_dsr<160>(DF[5], adD + so);
-                i8_dsr<192>(DF[6], adD + so);
-                i8_dsr<224>(DF[7], adD + so);
+                dsr16<0>(DF[0], adD + so);
+                dsr16<32>(DF[1], adD + so);
+                dsr16<64>(DF[2], adD + so);
+                dsr16<96>(DF[3], adD + so);
+                dsr16<128>(DF[4], adD + so);
+                dsr16<160>(DF[5], adD + so);
+                dsr16<192>(DF[6], adD + so);
+                dsr16<224>(DF[7], adD + so);
             }
             // counted wait for XF[jb & 3] (and, at even jb, Q[(jb >> 1) & 1]): what was issued after them may stay in flight
             u32x4 &xa = XF[jb & 3][0], &xb = XF[jb & 3][1];
@@ -329,12 +305,12 @@ __global__ __launch_bounds__(512) void gemm_i8_kernel(const gemm_mats mats, int 
         };
         asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(DF[0]), "+v"(DF[1]), "+v"(DF[2]), "+v"(DF[3]));
         // the next stage's first operands (this stage's once more at the very end: never used)
-        i8_dsr<0>(HD, adH + so_n);
-        i8_dsr<0>(Q[0], adQ + so_n);
-        i8_dsr<0>(XF[0][0], adX[0] + so_n);
-        i8_dsr<8192>(XF[0][1], adX[0] + so_n);
-        i8_dsr<0>(XF[1][0], adX[1] + so_n);
-        i8_dsr<8192>(XF[1][1], adX[1] + so_n);
+        dsr16<0>(HD, adH + so_n);
+        dsr16<0>(Q[0], adQ + so_n);
+        dsr16<0>(XF[0][0], adX[0] + so_n);
+        dsr16<8192>(XF[0][1], adX[0] + so_n);
+        dsr16<0>(XF[1][0], adX[1] + so_n);
+        dsr16<8192>(XF[1][1], adX[1] + so_n);
         epilogue(0, tm0);
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(DF[4]), "+v"(DF[5]), "+v"(DF[6]), "+v"(DF[7]));
         epilogue(1, tm1);
@@ -487,21 +463,9 @@ static hipError_t gemm_i8_go(int count, const void *const *A, const long *m, lon
     const lfamd_i8_image l = lfamd_i8_image_of(k, n);
     const uint8_t *img = (const uint8_t *)image;
     gemm_mats mats;
-    int n_rb = 0;
-    mats.count = 0;
-    mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
-    for (int j = 0; j < count; j++) {
-        if (m[j] <= 0)
-            continue;
-        const int q = mats.count++;
-        mats.A[q] = (const uint8_t *)A[j], mats.C[q] = C[j], mats.m[q] = m[j], mats.ldc[q] = ldc[j];
-        n_rb += (int)((m[j] + 127) / 128);
-        mats.rb_end[q] = n_rb;
-    }
+    const int n_rb = fill_gemm_mats(mats, count, A, m, C, ldc);
     if (mats.count == 0)
         return hipGetLastError();
-    for (int q = mats.count; q < GEMM_MAX_MATS; q++)
-        mats.A[q] = mats.A[0], mats.C[q] = mats.C[0], mats.m[q] = 0, mats.ldc[q] = 0, mats.rb_end[q] = n_rb;
     const int n_ct = (int)((n + I8_COLS - 1) / I8_COLS);
     gemm_i8_kernel<<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nb, (const int8_t *)img, (const float *)(img + l.d8T),
                                                            (const _Float16 *)(img + l.Xs), n, (long)l.n_pad, n_rb, n_ct);

@@ -18,29 +18,15 @@
 //     their fragments fetched before it): the two waves of a SIMD never stand at a barrier, a cold start or a constants
 //     block together;
 //   * a 256 x 128 tile takes in 50 KB per period for 256 MFMAs (the 128 x 128 tile of gemm_lw: 41 KB for 128).
-#include "gemm_wide_impl.h"
+#include "gemm_common.h"
+#include <type_traits>
 
 #define KR_XM 32768
 #define KR_SLOT (32768 + 2048)
 #define KR_STAGES 4
 #define KR_COLS 128
 
-template <int IMM>
-__device__ static inline void kr_dma16(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst), "n"(IMM) : "memory", "scc");
-}
-__device__ static inline void kr_dma4(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
-}
-template <int IMM>
-__device__ static inline void kr_ld16(u32x4 &dst, const void *base, uint32_t voff) {
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
-}
-template <int IMM>
-__device__ static inline void kr_dsr16(half8_t &dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
-
+// (loads and LDS reads go out in the lean issue forms of gemm_common.h: dma16, dma4, ld16, dsr16)
 #ifdef KR_BOUNDS // development: every global access checked against its buffer; the first violation is recorded, not executed
 __device__ unsigned long long g_kr_oob[8];
 extern "C" int lfamd_debug_kr_oob(unsigned long long *dst) {
@@ -67,8 +53,8 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
                                                       const float *__restrict__ d8T, const _Float16 *__restrict__ Xm, long n,
                                                       long n_pad, int n_rb, int n_ct) {
     static_assert(TYPE == LFAMD_TYPE_Q4_K, "resident P4K layout");
-#ifdef KS_CHECK_NB // tools/isa_hazards.py: a fixed trip count unrolls the period loop into straight-line code
-    nb = KS_CHECK_NB;
+#ifdef GEMM_CHECK_TRIPS // tools/isa_hazards.py: a fixed trip count unrolls the period loop into straight-line code
+    nb = GEMM_CHECK_TRIPS;
 #endif
     __shared__ __attribute__((aligned(16))) uint8_t lds[KR_STAGES * KR_SLOT];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -79,28 +65,10 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
     int rb, ct, mj = 0, moe_left = 0;
     long n0;
     const uint8_t *__restrict__ A;
-    if constexpr (MOE) { // (expert, row block) fastest, token tile slowest: the order of gemm_lw's grouped launch
-        const int per_ct = (int)gridDim.x / mats.moe_ct_max;
-        ct = (int)blockIdx.x / per_ct;
-        const int rem = (int)blockIdx.x - ct * per_ct;
-        const int e = rem / n_rb;
-        rb = rem - e * n_rb;
-        moe_left = mats.moe_cnt[e] - ct * KR_COLS;
-        if (moe_left <= 0)
-            return;
-        A = mats.A[0] + (size_t)e * mats.expert_bytes;
-        n0 = (long)mats.moe_poff[e] + (long)ct * KR_COLS;
+    if constexpr (MOE) {
+        MOE_TILE_OR_RETURN(mats, (int)blockIdx.x, (int)gridDim.x, n_rb, KR_COLS, rb, ct, moe_left, A, n0);
     } else {
-        const int n_wg = n_rb * n_ct;
-        const int id = (int)blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-        tile_of(L, n_rb, n_ct, rb, ct);
-#pragma unroll
-        for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-            if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-                mj = jj;
-        if (mj > 0)
-            rb -= mats.rb_end[mj - 1];
+        WG_TILE_AT(mats, XCD_ORDER((int)blockIdx.x, n_rb * n_ct), n_rb, n_ct, rb, ct, mj);
         A = mats.A[mj];
         n0 = (long)ct * KR_COLS;
     }
@@ -202,24 +170,24 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
             }
 #endif
             if (j == 0)
-                kr_dma16<0>(xs_n, slot + xd0, xo[0]);
+                dma16<0>(xs_n, slot + xd0, xo[0]);
             else if (j == 1)
-                kr_dma16<1024>(xs_n, slot + xd0, xo[1]);
+                dma16<1024>(xs_n, slot + xd0, xo[1]);
             else if (j == 2)
-                kr_dma16<2048>(xs_n, slot + xd0, xo[2]);
+                dma16<2048>(xs_n, slot + xd0, xo[2]);
             else if (j == 3)
-                kr_dma16<3072>(xs_n, slot + xd0, xo[3]);
+                dma16<3072>(xs_n, slot + xd0, xo[3]);
             else if (j == 4) {
-                kr_dma4(xm_n, slot + xmd, xmo);
+                dma4(xm_n, slot + xmd, xmo);
                 advance_x();
             } else if (j == 5)
-                kr_ld16<WH * 2048>(qa[wset], wt_n, wlo);
+                ld16<WH * 2048>(qa[wset], wt_n, wlo);
             else if (j == 6) {
-                kr_ld16<WH * 2048 + 1024>(qb[wset], wt_n, wlo);
+                ld16<WH * 2048 + 1024>(qb[wset], wt_n, wlo);
                 if constexpr (WH == 1)
                     advance_w();
             } else if constexpr (WH == 0) { // p + 3 starts a super-block: its row header -> hd[((p + 3) >> 1) & 1] (set 1 -> 0, set 3 -> 1)
-                kr_ld16<0>(hd[set == 1 ? 0 : 1], wt_n, hlo);
+                ld16<0>(hd[set == 1 ? 0 : 1], wt_n, hlo);
             }
         };
         // ---- compute state
@@ -262,10 +230,10 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
             constexpr int set = decltype(setc)::value;
             constexpr int SOFF = (set & 1) * KR_SLOT;
             const uint32_t a = set < 2 ? xoffA[t8] : xoffA[t8] + 2 * KR_SLOT;
-            kr_dsr16<SOFF>(f[0], a);
-            kr_dsr16<SOFF + 8192>(f[1], a);
-            kr_dsr16<SOFF + 16384>(f[2], a);
-            kr_dsr16<SOFF + 24576>(f[3], a);
+            dsr16<SOFF>(f[0], a);
+            dsr16<SOFF + 8192>(f[1], a);
+            dsr16<SOFF + 16384>(f[2], a);
+            dsr16<SOFF + 24576>(f[3], a);
         };
         // the mins operand of 64 tokens: part 0 (token tiles 0, 1) came with the super-block's first stage (slot set - 1 in the odd
         // period that uses it), part 1 (token tiles 2, 3) with the second
@@ -273,8 +241,8 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
             constexpr int set = decltype(setc)::value, slot = decltype(partc)::value ? set : (set + 3) & 3;
             constexpr int SOFF = (slot & 1) * KR_SLOT;
             const uint32_t a = slot < 2 ? xm_offA : xm_offA + 2 * KR_SLOT;
-            kr_dsr16<SOFF>(fxm[0], a);
-            kr_dsr16<SOFF + 1024>(fxm[1], a);
+            dsr16<SOFF>(fxm[0], a);
+            dsr16<SOFF + 1024>(fxm[1], a);
         };
         auto dq = [&](auto setc, int t8) -> half8_t {
             constexpr int set = decltype(setc)::value;
@@ -383,7 +351,7 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
                     asm volatile("s_waitcnt vmcnt(15)" : "+v"(hd[set == 1 ? 1 : 0])::"memory");
                 make_consts(N1{});
             };
-#ifdef KS_CHECK_NB
+#ifdef GEMM_CHECK_TRIPS
 #pragma unroll
 #endif
             for (int p = 0; p < np; p += 4) {
@@ -454,7 +422,7 @@ __global__ __launch_bounds__(512) void gemm_kr_kernel(const gemm_mats mats, int 
                 first_half_of_new(I0{}, dq(I0{}, 0));
                 make_consts(I1{});
             }
-#ifdef KS_CHECK_NB
+#ifdef GEMM_CHECK_TRIPS
 #pragma unroll
 #endif
             for (int p = 1; p < np; p += 4) {

@@ -21,7 +21,8 @@
 //     stages ahead in a ring of three; ONE s_barrier per super-block.
 //   * every wait is counted: a wave's loads retire in issue order (W(b+1), DMA(b+1), W(b+2) = 11 younger than what stage b
 //     needs), so `s_waitcnt vmcnt(11)` + the barrier is "stage b has landed for everybody".
-#include "gemm_wide_impl.h"
+#include "gemm_common.h"
+#include <type_traits>
 
 #define KS_XHALF 16384
 #define KS_XM 32768
@@ -40,65 +41,34 @@ __device__ static inline half8_t as_h8(u32x4 v) {
 
 #if GEMM_DIAG == 6 // development: s_memtime stamps of work-group KS_STAMP_WG, waves 0 and 4 (tools/ks_stamps.py)
 #define KS_STAMP_WG 100
-__device__ unsigned long long g_ks_stamps[2 * 256];
-extern "C" int lfamd_debug_ks_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_ks_stamps), sizeof(g_ks_stamps));
-}
+#define DIAG_STAMPS (2 * 256)
+#include "diag_stamps.h"
 #define KSTAMP()                                                                                                     \
     do {                                                                                                             \
         if (blockIdx.x == KS_STAMP_WG && lane == 0 && rw == 0 && stamp_n < 256)                                      \
-            g_ks_stamps[kh * 256 + stamp_n++] = __builtin_amdgcn_s_memtime();                                        \
+            g_stamps[kh * 256 + stamp_n++] = DIAG_CLOCK();                                                           \
     } while (0)
 #else
 #define KSTAMP()
 #endif
 
-// lean issue forms: the addresses are SGPR values kept by scalar adds (no VALU-written SGPR in front of a vector-memory
-// instruction, so no wait states), M0 is written and never restored (nothing else in this kernel reads it)
-template <int IMM>
-__device__ static inline void ks_dma16(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst), "n"(IMM) : "memory", "scc");
-}
-__device__ static inline void ks_dma4(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
-}
-template <int IMM>
-__device__ static inline void ks_ld16(u32x4 &dst, const void *base, uint32_t voff) {
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
-}
-template <int IMM>
-__device__ static inline void ks_dsr16(half8_t &dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
-
+// (loads and LDS reads go out in the lean issue forms of gemm_common.h: dma16, dma4, ld16, dsr16)
 template <int TYPE>
 __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int nb, const _Float16 *__restrict__ Xh,
                                                       const float *__restrict__ d8T, const _Float16 *__restrict__ Xm, long n,
                                                       long n_pad, int n_rb, int n_ct) {
     static_assert(TYPE == LFAMD_TYPE_Q4_K, "resident P4K layout");
-#ifdef KS_CHECK_NB // tools/isa_hazards.py: a fixed trip count unrolls the stage loop into straight-line code in execution order
-    nb = KS_CHECK_NB;
+#ifdef GEMM_CHECK_TRIPS // tools/isa_hazards.py: a fixed trip count unrolls the stage loop into straight-line code in execution order
+    nb = GEMM_CHECK_TRIPS;
 #endif
     __shared__ __attribute__((aligned(16))) uint8_t lds[KS_STAGES * KS_SLOT];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 31, h = lane >> 5;
     const int rw = wave & 3, kh = wave >> 2;
 
-    // ---- tile of this work-group (the order of gemm_lw: XCD-aware super-tiles)
-    int rb, ct;
-    {
-        const int n_wg = n_rb * n_ct;
-        const int id = (int)blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-        tile_of(L, n_rb, n_ct, rb, ct);
-    }
-    int mj = 0;
-#pragma unroll
-    for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-        if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-            mj = jj;
-    if (mj > 0)
-        rb -= mats.rb_end[mj - 1];
+    // ---- tile of this work-group
+    int rb, ct, mj;
+    WG_TILE_AT(mats, XCD_ORDER((int)blockIdx.x, n_rb * n_ct), n_rb, n_ct, rb, ct, mj);
     const uint8_t *__restrict__ A = mats.A[mj];
     float *__restrict__ C = mats.C[mj];
     const long m = mats.m[mj], ldc = mats.ldc[mj];
@@ -167,22 +137,22 @@ __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int 
         constexpr int wset = (set + 3) & 3;
         const uint32_t slot = lds0 + (uint32_t)(((set + 2) & 3) * KS_SLOT);
         if (j == 0)
-            ks_dma16<0>(xs_n, slot + xd0, xo[0]);
+            dma16<0>(xs_n, slot + xd0, xo[0]);
         else if (j == 1)
-            ks_dma16<1024>(xs_n, slot + xd0, xo[1]);
+            dma16<1024>(xs_n, slot + xd0, xo[1]);
         else if (j == 2)
-            ks_dma16<2048>(xs_n, slot + xd0, xo[2]);
+            dma16<2048>(xs_n, slot + xd0, xo[2]);
         else if (j == 3)
-            ks_dma16<3072>(xs_n, slot + xd0, xo[3]);
+            dma16<3072>(xs_n, slot + xd0, xo[3]);
         else if (j == 4) {
-            ks_dma4(xm_n, slot + xmd, xmo);
+            dma4(xm_n, slot + xmd, xmo);
             advance_x();
         } else if (j == 5)
-            ks_ld16<0>(qa[wset], wt_n, wlo);
+            ld16<0>(qa[wset], wt_n, wlo);
         else if (j == 6)
-            ks_ld16<1024>(qb[wset], wt_n, wlo);
+            ld16<1024>(qb[wset], wt_n, wlo);
         else {
-            ks_ld16<0>(hd[wset], wt_n, hlo);
+            ld16<0>(hd[wset], wt_n, hlo);
             advance_w();
         }
     };
@@ -236,15 +206,15 @@ __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int 
         constexpr int set = decltype(setc)::value;
         constexpr int SOFF = (set & 1) * KS_SLOT; // offset field: slot `set` from address set A (slots 0, 1) or B (slots 2, 3)
         const uint32_t a = set < 2 ? xoffA[t8] : xoffB[t8];
-        ks_dsr16<SOFF>(f[0], a);
-        ks_dsr16<SOFF + 8192>(f[1], a);
+        dsr16<SOFF>(f[0], a);
+        dsr16<SOFF + 8192>(f[1], a);
     };
     auto read_mins = [&](auto setc) {
         constexpr int set = decltype(setc)::value;
         constexpr int SOFF = (set & 1) * KS_SLOT;
         const uint32_t a = set < 2 ? xm_offA : xm_offB;
-        ks_dsr16<SOFF>(fxm[0], a);
-        ks_dsr16<SOFF + 1024>(fxm[1], a);
+        dsr16<SOFF>(fxm[0], a);
+        dsr16<SOFF + 1024>(fxm[1], a);
     };
     // the weight fragment of K-step t8 of the super-block in register set `set`
     auto dq = [&](auto setc, int t8) -> half8_t {
@@ -344,7 +314,7 @@ __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int 
             asm volatile("s_waitcnt vmcnt(" KS_VM_HDR ")" : "+v"(hd[(set + 1) & 3])::"memory");
             make_consts(N1{}, KH{});
         };
-#ifdef KS_CHECK_NB
+#ifdef GEMM_CHECK_TRIPS
 #pragma unroll
 #endif
         for (int b = 0; b < nb; b += 4) {
@@ -444,7 +414,7 @@ __global__ __launch_bounds__(512) void gemm_ks_kernel(const gemm_mats mats, int 
             asm volatile("s_waitcnt vmcnt(" KS_VM_HDR ")" : "+v"(hd[1])::"memory");
             make_consts(I1{}, KH{});
         }
-#ifdef KS_CHECK_NB
+#ifdef GEMM_CHECK_TRIPS
 #pragma unroll
 #endif
         for (int b = 1; b < nb; b += 4) {

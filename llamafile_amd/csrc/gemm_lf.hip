@@ -25,7 +25,7 @@
 //                 The large grids are paced by the loaders (L2 -> LDS, ~10 TB/s over the chip).
 //   activations : f16(d8 * q8) (quantize_row_q8_0 arithmetic, or the caller's Q8_0 blocks), [quad][token][256 B] in the K order
 //                 above, 16-byte chunks XOR-swizzled by token on the source address.
-#include "gemm_wide_impl.h"
+#include "gemm_common.h"
 #include "lfamd_internal.h"
 
 #include <stdlib.h>
@@ -36,18 +36,7 @@ typedef _Float16 lf_half4 __attribute__((ext_vector_type(4)));
 #define LF_WD 16384   // 16 x 64 B of block scales
 #define LF_X 17408    // 32 NT tokens x 256 B
 
-// LDS-DMA pieces: 64 lanes x 16 B (x 4 B) from base + voff to LDS at lds_dst + 16 (4) * lane.  SGPR base kept by scalar adds; M0
-// written and not restored (nothing else in this kernel reads it).
-__device__ static inline void lf_dma16(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
-}
-__device__ static inline void lf_dma4(const void *base, uint32_t lds_dst, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(base), "s"(lds_dst) : "memory");
-}
-template <int IMM>
-__device__ static inline void lf_dsr16(u32x4 &dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
+// (LDS-DMA pieces and 16-byte LDS reads: the lean issue forms of gemm_common.h — dma16 without an immediate, dma4, dsr16)
 __device__ static inline void lf_dsr8(uint2 &dst, uint32_t addr) {
     asm volatile("ds_read_b64 %0, %1" : "=v"(dst) : "v"(addr));
 }
@@ -91,18 +80,16 @@ __device__ static inline void lf_h_mul_second(half2_t &f0, half2_t &f1, half2_t 
 }
 
 #ifdef LF_STAMPS // development (tools/lf_stamps.py): s_memtime sums of one work-group's compute wave 0 and loader wave 4
-__device__ unsigned long long g_lf_stamps[16];
-extern "C" int lfamd_debug_lf_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_lf_stamps), sizeof(g_lf_stamps));
-}
-#define LF_T() __builtin_amdgcn_s_memtime()
+#define DIAG_STAMPS 16
+#include "diag_stamps.h"
+#define LF_T() DIAG_CLOCK()
 #endif
 
 template <int NT>
 __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, int nq, const _Float16 *__restrict__ Xh, long n, long n_pad,
                                                            int n_rb, int n_ct, const float *__restrict__ tok_scale) {
-#ifdef LF_CHECK_NQ // tools/isa_hazards.py: a fixed trip count
-    nq = LF_CHECK_NQ;
+#ifdef GEMM_CHECK_TRIPS // tools/isa_hazards.py: a fixed trip count
+    nq = GEMM_CHECK_TRIPS;
 #endif
     constexpr int SLOT = LF_X + NT * 8192;
     constexpr int RING = NT == 2 ? 4 : 3; // (a ring of three at 128 x 64 measured 3-11 % slower: profiles/r04_q80_batch_body.txt)
@@ -117,21 +104,9 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
     unsigned long long st_a = 0, st_b = 0, st_c = 0;
 #endif
 
-    // ---- tile of this work-group (the order of gemm_ks: XCD-aware super-tiles)
-    int rb, ct;
-    {
-        const int n_wg = n_rb * n_ct;
-        const int id = (int)blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-        tile_of(L, n_rb, n_ct, rb, ct);
-    }
-    int mj = 0;
-#pragma unroll
-    for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-        if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-            mj = jj;
-    if (mj > 0)
-        rb -= mats.rb_end[mj - 1];
+    // ---- tile of this work-group
+    int rb, ct, mj;
+    WG_TILE_AT(mats, XCD_ORDER((int)blockIdx.x, n_rb * n_ct), n_rb, n_ct, rb, ct, mj);
     const uint8_t *__restrict__ A = mats.A[mj];
     float *__restrict__ C = mats.C[mj];
     const long m = mats.m[mj], ldc = mats.ldc[mj];
@@ -176,11 +151,11 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
         auto dma_stage = [&](uint32_t slot_base) {
 #pragma unroll
             for (int T = 0; T < 4; T++)
-                lf_dma16(wt_n, slot_base + dstW + (uint32_t)(T * 1024), voffW[T]);
-            lf_dma4(wt_n, slot_base + dstD, voffD);
+                dma16(wt_n, slot_base + dstW + (uint32_t)(T * 1024), voffW[T]);
+            dma4(wt_n, slot_base + dstD, voffD);
 #pragma unroll
             for (int e = 0; e < 2 * NT; e++)
-                lf_dma16(xh_n, slot_base + dstX + (uint32_t)(e * 1024), voffX[e]);
+                dma16(xh_n, slot_base + dstX + (uint32_t)(e * 1024), voffX[e]);
             wt_n += P80_TILE, xh_n += xstride; // (past the last quad nothing more is issued)
         };
 #pragma unroll
@@ -260,7 +235,7 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
         }
 #ifdef LF_STAMPS
         if (st_on && wave == 4 && lane == 0)
-            g_lf_stamps[8] = st_a, g_lf_stamps[9] = st_b, g_lf_stamps[10] = st_c, g_lf_stamps[11] = LF_T() - st_start;
+            g_stamps[8] = st_a, g_stamps[9] = st_b, g_stamps[10] = st_c, g_stamps[11] = LF_T() - st_start;
 #endif
         return;
     }
@@ -300,11 +275,11 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
 #define LF_WAIT(N) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N))
 #define LF_XREAD(S, BASE)                                                                                                     \
     do {                                                                                                                      \
-        lf_dsr16<0>(XF[(S)&1][0], adX[(S)&7] + (BASE));                                                                        \
-        lf_dsr16<8192>(XF[(S)&1][1], adX[(S)&7] + (BASE));                                                                     \
+        dsr16<0>(XF[(S)&1][0], adX[(S)&7] + (BASE));                                                                        \
+        dsr16<8192>(XF[(S)&1][1], adX[(S)&7] + (BASE));                                                                     \
         if (NT == 4) {                                                                                                        \
-            lf_dsr16<16384>(XF[(S)&1][NT - 2], adX[(S)&7] + (BASE));                                                           \
-            lf_dsr16<24576>(XF[(S)&1][NT - 1], adX[(S)&7] + (BASE));                                                           \
+            dsr16<16384>(XF[(S)&1][NT - 2], adX[(S)&7] + (BASE));                                                           \
+            dsr16<24576>(XF[(S)&1][NT - 1], adX[(S)&7] + (BASE));                                                           \
         }                                                                                                                     \
     } while (0)
 #define LF_XTIE(S)                                                                                                            \
@@ -335,7 +310,7 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
     uint32_t sel_lo, sel_hi, k64;
     asm volatile("v_mov_b32 %0, 0x04010400\n\tv_mov_b32 %1, 0x04030402\n\ts_mov_b32 %2, 0x64646464" : "=v"(sel_lo), "=v"(sel_hi), "=s"(k64));
     LF_XREAD(0, 0u);
-    lf_dsr16<0>(WQ[0], adW[0]);
+    dsr16<0>(WQ[0], adW[0]);
     lf_dsr8(SC, adD);
     LF_WAIT(0);
     asm volatile("" : "+v"(WQ[0]));
@@ -371,7 +346,7 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
             asm volatile("s_barrier" ::: "memory"); /* B2: stage b + 1 has landed for everybody */                            \
         LF_XREAD((S) + 1, (S) == 7 ? so_n : so);                                                                              \
         if (((S)&1) == 0)                                                                                                     \
-            lf_dsr16<0>(WQ[(((S) + 2) >> 1) & 1], adW[(((S) + 2) >> 1) & 3] + ((S) == 6 ? so_n : so));                           \
+            dsr16<0>(WQ[(((S) + 2) >> 1) & 1], adW[(((S) + 2) >> 1) & 3] + ((S) == 6 ? so_n : so));                           \
         if ((S) == 6)                                                                                                         \
             lf_dsr8(SC, adD + so_n);                                                                                          \
         if (NT == 2)                                                                                                          \
@@ -417,7 +392,7 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
     }
 #ifdef LF_STAMPS
     if (st_on && wave == 0 && lane == 0)
-        g_lf_stamps[0] = st_a, g_lf_stamps[1] = st_b, g_lf_stamps[2] = (unsigned long long)nq, g_lf_stamps[3] = LF_T() - st_start;
+        g_stamps[0] = st_a, g_stamps[1] = st_b, g_stamps[2] = (unsigned long long)nq, g_stamps[3] = LF_T() - st_start;
 #endif
     LF_WAIT(0); // (the reads of a stage that does not exist: slot contents never used)
     LF_XTIE(0);
@@ -443,7 +418,7 @@ __global__ __launch_bounds__(512) void gemm_lf_q80_kernel(const gemm_mats mats, 
     }
 #ifdef LF_STAMPS
     if (st_on && wave == 0 && lane == 0)
-        g_lf_stamps[4] = LF_T() - st_start;
+        g_stamps[4] = LF_T() - st_start;
 #endif
 }
 
@@ -549,27 +524,15 @@ __global__ __launch_bounds__(256) void prep_lf_kernel(const uint8_t *__restrict_
 template <bool BF>
 __global__ __launch_bounds__(512) void gemm_lf_float_kernel(const gemm_mats mats, int nq, size_t a_row_bytes, const uint16_t *__restrict__ Xh,
                                                                       long n, long n_pad, int n_rb, int n_ct) {
-#ifdef LF_CHECK_NQ
-    nq = LF_CHECK_NQ;
+#ifdef GEMM_CHECK_TRIPS
+    nq = GEMM_CHECK_TRIPS;
 #endif
     constexpr int RING = 3;
     constexpr int WP = 8, XP = 4, PIECES = WP + XP; // of a loader and stage
     __shared__ __attribute__((aligned(16))) uint8_t lds[RING * LFF_SLOT];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int rb, ct;
-    {
-        const int n_wg = n_rb * n_ct;
-        const int id = (int)blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-        tile_of(L, n_rb, n_ct, rb, ct);
-    }
-    int mj = 0;
-#pragma unroll
-    for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-        if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-            mj = jj;
-    if (mj > 0)
-        rb -= mats.rb_end[mj - 1];
+    int rb, ct, mj;
+    WG_TILE_AT(mats, XCD_ORDER((int)blockIdx.x, n_rb * n_ct), n_rb, n_ct, rb, ct, mj);
     const uint8_t *__restrict__ A = mats.A[mj];
     float *__restrict__ C = mats.C[mj];
     const long m = mats.m[mj], ldc = mats.ldc[mj];
@@ -600,10 +563,10 @@ __global__ __launch_bounds__(512) void gemm_lf_float_kernel(const gemm_mats mats
         auto dma_stage = [&](uint32_t slot_base) {
 #pragma unroll
             for (int e = 0; e < WP; e++)
-                lf_dma16(wt_n, slot_base + dstW + (uint32_t)(e * 1024), voffW[e]);
+                dma16(wt_n, slot_base + dstW + (uint32_t)(e * 1024), voffW[e]);
 #pragma unroll
             for (int e = 0; e < XP; e++)
-                lf_dma16(xh_n, slot_base + dstX + (uint32_t)(e * 1024), voffX[e]);
+                dma16(xh_n, slot_base + dstX + (uint32_t)(e * 1024), voffX[e]);
             wt_n += 256;
             xh_n += (q_n & 1) ? xstride - 256 : 256; // the other half of the token rows / the next super-block
             q_n++;
@@ -655,12 +618,12 @@ __global__ __launch_bounds__(512) void gemm_lf_float_kernel(const gemm_mats mats
     u32x4 W2[2][2], X2[2][4];
 #define LFF_READ(BUF, SX, BASE)                                                                                               \
 do {                                                                                                                          \
-    lf_dsr16<0>(W2[BUF][0], aW[SX] + (BASE));                                                                                 \
-    lf_dsr16<4096>(W2[BUF][1], aW[SX] + (BASE));                                                                              \
-    lf_dsr16<0>(X2[BUF][0], aX[SX] + (BASE));                                                                                 \
-    lf_dsr16<4096>(X2[BUF][1], aX[SX] + (BASE));                                                                              \
-    lf_dsr16<8192>(X2[BUF][2], aX[SX] + (BASE));                                                                              \
-    lf_dsr16<12288>(X2[BUF][3], aX[SX] + (BASE));                                                                             \
+    dsr16<0>(W2[BUF][0], aW[SX] + (BASE));                                                                                 \
+    dsr16<4096>(W2[BUF][1], aW[SX] + (BASE));                                                                              \
+    dsr16<0>(X2[BUF][0], aX[SX] + (BASE));                                                                                 \
+    dsr16<4096>(X2[BUF][1], aX[SX] + (BASE));                                                                              \
+    dsr16<8192>(X2[BUF][2], aX[SX] + (BASE));                                                                              \
+    dsr16<12288>(X2[BUF][3], aX[SX] + (BASE));                                                                             \
 } while (0)
     LFF_READ(0, 0, 0u);
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -721,11 +684,7 @@ extern "C" hipError_t lfamd_launch_gemm_lf_float(int Atype, const void *A, size_
     if (k % 256 || (a_row_bytes & 15) || ((uintptr_t)A & 15) || (Atype != LFAMD_TYPE_F16 && Atype != LFAMD_TYPE_BF16))
         return hipErrorInvalidValue;
     gemm_mats mats;
-    const int n_rb = (int)((m + 127) / 128), n_ct = (int)((n + 63) / 64);
-    mats.count = 1;
-    mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
-    for (int q = 0; q < GEMM_MAX_MATS; q++)
-        mats.A[q] = (const uint8_t *)A, mats.C[q] = C, mats.m[q] = q ? 0 : m, mats.ldc[q] = q ? 0 : ldc, mats.rb_end[q] = n_rb;
+    const int n_rb = fill_gemm_mats(mats, 1, &A, &m, &C, &ldc), n_ct = (int)((n + 63) / 64);
     const int nq = (int)(k / 128);
     const unsigned grid = (unsigned)(n_rb * n_ct);
     if (Atype == LFAMD_TYPE_BF16)
@@ -757,24 +716,13 @@ extern "C" int lfamd_gemm_lf_q80_fits(long m, long k) { // (the loaders address 
 static hipError_t lf_q80_go(int count, const void *const *A, const long *m, long k, const _Float16 *Xh, const float *tok_scale, long n,
                             long n_pad, float *const *C, const long *ldc, hipStream_t s) {
     const int nq = (int)(k / 128);
-    gemm_mats mats;
-    int n_rb = 0;
-    mats.count = 0;
-    mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
-    for (int j = 0; j < count; j++) {
-        if (m[j] <= 0)
-            continue;
-        if (!lfamd_gemm_lf_q80_fits(m[j], k))
+    for (int j = 0; j < count; j++)
+        if (m[j] > 0 && !lfamd_gemm_lf_q80_fits(m[j], k))
             return hipErrorInvalidValue;
-        const int q = mats.count++;
-        mats.A[q] = (const uint8_t *)A[j], mats.C[q] = C[j], mats.m[q] = m[j], mats.ldc[q] = ldc[j];
-        n_rb += (int)((m[j] + 127) / 128);
-        mats.rb_end[q] = n_rb;
-    }
+    gemm_mats mats;
+    const int n_rb = fill_gemm_mats(mats, count, A, m, C, ldc);
     if (mats.count == 0)
         return hipGetLastError();
-    for (int q = mats.count; q < GEMM_MAX_MATS; q++)
-        mats.A[q] = mats.A[0], mats.C[q] = mats.C[0], mats.m[q] = 0, mats.ldc[q] = 0, mats.rb_end[q] = n_rb;
     if (lf_nt(n_rb, n) == 4) {
         const int n_ct = (int)((n + 127) / 128);
         gemm_lf_q80_kernel<4><<<(unsigned)(n_rb * n_ct), 512, 0, s>>>(mats, nq, Xh, n, n_pad, n_rb, n_ct, tok_scale);

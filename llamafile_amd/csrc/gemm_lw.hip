@@ -18,7 +18,8 @@
 //   * stage = HALF a super-block (128 k): 32 KiB of activation codes + 8 KiB of nibbles (+ headers / d8 / mins operand
 //     with the first half), three stages in LDS (157.5 KiB); loaders and compute waves synchronise through two counters
 //     in LDS ("landed" / "released" stages), no work-group barrier inside the K loop.
-#include "gemm_wide_impl.h"
+#include "gemm_common.h"
+#include <type_traits>
 
 #define LW_X 0          // 128 tokens x 256 B, XOR-swizzled 16-byte chunks
 #define LW_W 32768      // 4 row tiles x 2 KiB (the two nibble groups of this half)
@@ -31,14 +32,12 @@
 #define LW_FLAG (LW_STAGES * LW_SLOT) // landed-stage counter (+1 per loader wave and stage), at +4: released-stage counter (+1 per compute wave and stage)
 
 #if GEMM_DIAG == 4 // development: s_memtime stamps around every barrier of work-group 0 (wave 0 computes, wave 4 loads)
-__device__ unsigned long long g_lw_stamps[2 * 128];
-extern "C" int lfamd_debug_lw_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_lw_stamps), sizeof(g_lw_stamps));
-}
+#define DIAG_STAMPS (2 * 128)
+#include "diag_stamps.h"
 #define LSTAMP(role)                                                                                             \
     do {                                                                                                         \
         if (blockIdx.x == 0 && lane == 0 && (wave & 3) == 0 && stamp_n < 128)                                     \
-            g_lw_stamps[(role)*128 + stamp_n++] = __builtin_amdgcn_s_memtime();                                  \
+            g_stamps[(role)*128 + stamp_n++] = DIAG_CLOCK();                                                     \
     } while (0)
 #else
 #define LSTAMP(role)
@@ -68,33 +67,17 @@ __device__ __forceinline__ void gemm_lw_body(const gemm_mats &mats, int nb, cons
     float *__restrict__ C;
     long m, ldc, n0;
     if constexpr (MOE) {
-        const int per_ct = gdim / mats.moe_ct_max;
-        ct = bid / per_ct;
-        const int rem = bid - ct * per_ct;
-        const int e = rem / n_rb;
-        rb = rem - e * n_rb;
-        moe_left = mats.moe_cnt[e] - ct * WD_COLS;
-        if (moe_left <= 0)
-            return;
-        A = mats.A[0] + (size_t)e * mats.expert_bytes;
+        MOE_TILE_OR_RETURN(mats, bid, gdim, n_rb, COLS, rb, ct, moe_left, A, n0);
         C = mats.C[0];
         m = mats.m[0], ldc = mats.ldc[0];
-        n0 = (long)mats.moe_poff[e] + (long)ct * WD_COLS;
     } else {
         // ks > 1 (scaled-operand body, few-token batches of one matrix): K is cut into ks parts, every (tile, part) is a
         // work-group that writes its partial tile to P[part][token][row]; lw_ksplit_reduce sums the parts in order
         const int n_tiles = n_rb * n_ct, n_wg = n_tiles * ks;
-        const int id = bid, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+        const int L = XCD_ORDER(bid, n_wg);
         kpart = L / n_tiles;
-        tile_of(L - kpart * n_tiles, n_rb, n_ct, rb, ct);
-        int mj = 0;
-#pragma unroll
-        for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-            if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-                mj = jj;
-        if (mj > 0)
-            rb -= mats.rb_end[mj - 1];
+        int mj;
+        WG_TILE_AT(mats, L - kpart * n_tiles, n_rb, n_ct, rb, ct, mj);
         A = mats.A[mj];
         C = mats.C[mj];
         m = mats.m[mj], ldc = mats.ldc[mj];
@@ -105,7 +88,7 @@ __device__ __forceinline__ void gemm_lw_body(const gemm_mats &mats, int nb, cons
     const int H = 2 * (b_base + nbs <= nb ? nbs : nb - b_base); // half super-blocks
 #if GEMM_DIAG == 4
     int stamp_n = 0;
-    const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), real0 = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long clk0 = DIAG_CLOCK(), real0 = DIAG_REALTIME();
 #endif
     const uint32_t lds0 = lds_addr(lds);
     const uint32_t flag_addr = lds0 + LW_FLAG, rel_addr = flag_addr + 4;
@@ -585,8 +568,8 @@ __device__ __forceinline__ void gemm_lw_body(const gemm_mats &mats, int nb, cons
 
 #if GEMM_DIAG == 4 // shader clock against the 100 MHz reference over the whole K loop
     if (blockIdx.x == 0 && lane == 0 && wave == 0) {
-        g_lw_stamps[126] = __builtin_amdgcn_s_memtime() - clk0;
-        g_lw_stamps[127] = __builtin_amdgcn_s_memrealtime() - real0;
+        g_stamps[126] = DIAG_CLOCK() - clk0;
+        g_stamps[127] = DIAG_REALTIME() - real0;
     }
 #endif
     // ---- store.  FAST: lane (i, h) holds token n0 + 32nt + i, reg r = weight row 32rt + (r&3) + 8(r>>2) + 4h: four
@@ -648,7 +631,7 @@ __device__ __forceinline__ void gemm_lw_body(const gemm_mats &mats, int nb, cons
 #if GEMM_DIAG == 4 // cycles of this wave's C store, to the last write acknowledged
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (blockIdx.x == 0 && lane == 0 && wave == 0)
-        g_lw_stamps[125] = __builtin_amdgcn_s_memtime() - clk0 - g_lw_stamps[126];
+        g_stamps[125] = DIAG_CLOCK() - clk0 - g_stamps[126];
 #endif
 }
 

@@ -24,9 +24,6 @@
 // work-groups XCD-aware so an XCD's work-groups share a token tile.
 #include "gemm_common.h"
 #include "lfamd_internal.h"
-#ifndef GEMM_DIAG
-#define GEMM_DIAG 0
-#endif
 
 #include <stdlib.h>
 
@@ -62,13 +59,9 @@ __global__ __launch_bounds__(512) void gemm_kq_kernel(const uint8_t *__restrict_
     const int kg = wave >> 2, rw = wave & 3; // K-group, row-tile inside the work-group
     const int i = lane & 31, h = lane >> 5;
 
-    // XCD-aware tile assignment (T1): consecutive block ids go round-robin over the 8 XCDs, so give every
-    // XCD one contiguous run of the linear tile order (row-blocks fastest): the work-groups of an XCD then
-    // share a token tile (512 KiB of activation codes stays in that XCD's L2) and stream distinct weights.
-    const int id = blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+    // XCD-aware tile assignment (gemm_common.h; one matrix per launch here)
     int tt, rb;
-    tile_of(L, n_rb, n_wg / n_rb, rb, tt);
+    tile_of(XCD_ORDER(blockIdx.x, n_wg), n_rb, n_wg / n_rb, rb, tt);
 
     const long n_row_tiles = (m + 31) / 32;
     const long rt = (long)rb * 4 + rw;

@@ -191,24 +191,6 @@ extern "C" int lfamd_gemm_wide_scaled_ok(int Atype, int plain) {
     return !plain && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K);
 }
 
-// The matrices of a launch with m > 0, padded to GEMM_MAX_MATS with empty ones; returns their row blocks of 128.
-static int fill_gemm_mats(gemm_mats &mats, int count, const void *const *A, const long *m, float *const *C, const long *ldc) {
-    int n_rb = 0;
-    mats.count = 0;
-    mats.moe_cnt = mats.moe_poff = mats.moe_slot_row = nullptr, mats.expert_bytes = 0, mats.moe_ct_max = 0;
-    for (int j = 0; j < count; j++) {
-        if (m[j] <= 0)
-            continue;
-        const int i = mats.count++;
-        mats.A[i] = (const uint8_t *)A[j], mats.C[i] = C[j], mats.m[i] = m[j], mats.ldc[i] = ldc[j];
-        n_rb += (int)((m[j] + 127) / 128);
-        mats.rb_end[i] = n_rb;
-    }
-    for (int i = mats.count; i < GEMM_MAX_MATS && mats.count > 0; i++)
-        mats.A[i] = mats.A[0], mats.C[i] = mats.C[0], mats.m[i] = 0, mats.ldc[i] = 0, mats.rb_end[i] = n_rb;
-    return n_rb;
-}
-
 extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const void *const *A, const long *m, long k,
                                                    const void *Xh, const void *d8T, const void *Xm, long n, long n_pad,
                                                    float *const *C, const long *ldc, int mode, void *P, size_t P_bytes,

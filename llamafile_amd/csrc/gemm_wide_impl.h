@@ -18,14 +18,13 @@
 #pragma once
 #include "gemm_common.h"
 #include <type_traits>
-#ifndef GEMM_DIAG
-#define GEMM_DIAG 0
+#if GEMM_DIAG == 3 // development: in-kernel time stamps of work-group 0 (tools/wide_stamps.py)
+#define DIAG_STAMPS (8 * 64)
+#include "diag_stamps.h"
 #endif
 
 #define WD_COLS 128
 #define WD_XSTAGE (WD_COLS * XT_ROW_BYTES) // 64 KiB of f16 codes per super-block
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <int TYPE>
 struct wide_w {
@@ -35,100 +34,6 @@ struct wide_w {
     uint32_t dw; // Q6_K only (f16 bits)
     u32x4 q8[4]; // IQ4_XS byte image: K-steps 8..15 (qs[] holds 0..7)
     u32x4 f[16]; // F16 / BF16: the 16 K-step fragments of the lane's row, straight from the RAW row
-};
-
-template <int IMM>
-__device__ static inline void gload16(u32x4 &dst, const void *base, uint32_t voff) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
-}
-template <int IMM>
-__device__ static inline void gload4(uint32_t &dst, const void *base, uint32_t voff) {
-    asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
-}
-template <int IMM>
-__device__ static inline void gload2(uint32_t &dst, const void *base, uint32_t voff) {
-    asm volatile("s_nop 4\n\tglobal_load_ushort %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
-}
-
-// four LDS-DMA pieces (1 KiB each) to consecutive LDS slots from one SGPR base + per-lane offsets
-__device__ static inline void glds4(const void *base, uint32_t lds_dst, uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3) {
-    uint32_t keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\t"
-                 "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "s"(base), "s"(lds_dst)
-                 : "memory", "scc");
-}
-__device__ static inline void glds1x16(const void *base, uint32_t lds_dst, uint32_t o0) {
-    uint32_t keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(o0), "s"(base), "s"(lds_dst)
-                 : "memory");
-}
-__device__ static inline void glds1x4(const void *base, uint32_t lds_dst, uint32_t o0) {
-    uint32_t keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(o0), "s"(base), "s"(lds_dst)
-                 : "memory");
-}
-
-// make a wave-uniform pointer provably so (an "s" operand must be), via two v_readfirstlane
-__device__ static inline const uint8_t *uniform_ptr(const void *p) {
-    const uint64_t v = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (const uint8_t *)(uintptr_t)(((uint64_t)hi << 32) | lo);
-}
-
-// (gemm_ks.hip / gemm_kr.hip use LEAN load forms whose asm carries no wait states of its own: a VALU write of an SGPR —
-// v_readfirstlane — needs five wait states before a vector-memory instruction reads that SGPR, and hipcc's hazard recogniser
-// does not see inside an asm statement.  They follow uniform_ptr() with an `s_nop 4` fence that consumes the pointers;
-// tools/isa_hazards.py checks the rule on the final ISA.)
-
-// LDS fragment read hipcc neither counts nor moves: the K loop below keeps the next K-step's four fragments in
-// flight under the current step's MFMAs and waits with a counted lgkmcnt (left to itself hipcc reuses ONE
-// fragment register and waits lgkmcnt(0) in front of every MFMA — the whole LDS latency, 64 times per super-block)
-template <int IMM>
-__device__ static inline void dsr16(half8_t &dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
-template <int N>
-__device__ static inline void ds_wait(half8_t &a, half8_t &b) {
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
-}
-
-__device__ static inline uint32_t lds_addr(const void *p) {
-    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)(const uint8_t *)p);
-}
-
-#if GEMM_DIAG == 3
-__device__ unsigned long long g_wide_stamps[8 * 64];
-extern "C" int lfamd_debug_wide_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wide_stamps), sizeof(g_wide_stamps));
-}
-#endif
-
-// Up to GEMM_MAX_MATS weight matrices of one type and row length that consume the SAME activations (attn_q/k/v,
-// ffn_gate/up) share one prep and one launch: their 128-row blocks are concatenated (rb_end = exclusive prefix).
-#define GEMM_MAX_MATS 4
-struct gemm_mats {
-    const uint8_t *A[GEMM_MAX_MATS];
-    float *C[GEMM_MAX_MATS];
-    long m[GEMM_MAX_MATS];
-    long ldc[GEMM_MAX_MATS];
-    int rb_end[GEMM_MAX_MATS];
-    int count;
-    // GGML_OP_MUL_MAT_ID batches (MOE kernels only): A[0] = the expert stack, C[0] = result rows; token slots are grouped
-    // by expert on the device (moe.hip, moe_route_kernel): expert e owns slots [poff[e], poff[e] + cnt[e]), slot -> result
-    // row through slot_row.  The grid covers the worst case; work-groups beyond an expert's count exit at once.
-    const int *moe_cnt, *moe_poff, *moe_slot_row;
-    long expert_bytes;
-    int moe_ct_max;
 };
 
 template <int TYPE, bool MOE = false>
@@ -164,39 +69,15 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
     float *__restrict__ C;
     long m, ldc, n0;
     if constexpr (MOE) {
-        // (expert, row block, token tile of that expert); the routing kernel ran earlier on this stream
-        // block id = (token tile, expert, row block), row blocks fastest: consecutive ids go round-robin over the XCDs,
-        // so the live tiles (low token-tile index) spread over all eight instead of piling onto XCD 0 and 1, and they
-        // are dispatched before the tiles that only exit
-        const int per_ct = (int)(gridDim.x / mats.moe_ct_max); // experts * n_rb
-        ct = blockIdx.x / per_ct;
-        const int rem = blockIdx.x - ct * per_ct;
-        const int e = rem / n_rb;
-        rb = rem - e * n_rb;
-        const int cnt_e = mats.moe_cnt[e];
-        moe_left = cnt_e - ct * WD_COLS; // token slots of this tile that carry a row
-        if (moe_left <= 0)
-            return; // uniform over the work-group
+        MOE_TILE_OR_RETURN(mats, blockIdx.x, gridDim.x, n_rb, WD_COLS, rb, ct, moe_left, A, n0);
         ks = 0;
-        A = mats.A[0] + (size_t)e * mats.expert_bytes;
         C = mats.C[0];
         m = mats.m[0], ldc = mats.ldc[0];
-        n0 = (long)mats.moe_poff[e] + (long)ct * WD_COLS;
     } else {
-        // XCD-aware order: block ids go round-robin over the 8 XCDs; give each XCD a contiguous run of the order
-        // (K-split index slowest, then super-tiles of 8 x 4 tiles, see tile_of)
-        const int n_tiles = n_rb * n_ct, n_wg = n_tiles * ks_n;
-        const int id = blockIdx.x, q8 = n_wg >> 3, r8 = n_wg & 7, xcd = id & 7;
-        const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+        const int n_tiles = n_rb * n_ct, L = XCD_ORDER(blockIdx.x, n_tiles * ks_n);
         ks = L / n_tiles;
-        tile_of(L - ks * n_tiles, n_rb, n_ct, rb, ct);
-        int mj = 0;
-#pragma unroll
-        for (int jj = 1; jj < GEMM_MAX_MATS; jj++)
-            if (jj < mats.count && rb >= mats.rb_end[jj - 1])
-                mj = jj;
-        if (mj > 0)
-            rb -= mats.rb_end[mj - 1];
+        int mj;
+        WG_TILE_AT(mats, L - ks * n_tiles, n_rb, n_ct, rb, ct, mj);
         A = mats.A[mj];
         C = mats.C[mj];
         m = mats.m[mj], ldc = mats.ldc[mj];
@@ -737,12 +618,12 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(const gemm_mats mats, in
     };
 
     // ---- pipeline: super-block it+1 is in flight (registers w[(it+1)&1], LDS stage (it+1)&1) while it computes
-#if GEMM_DIAG == 3 // development: in-kernel time stamps of work-group 0 (s_memtime; never in the product build)
+#if GEMM_DIAG == 3
 #define STAMP(slot)                                                                                              \
     do {                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         if (blockIdx.x == 0 && lane == 0 && stamp_n < 60)                                                        \
-            g_wide_stamps[wave * 64 + stamp_n++] = __builtin_amdgcn_s_memtime();                                 \
+            g_stamps[wave * 64 + stamp_n++] = DIAG_CLOCK();                                                      \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
     } while (0)
     int stamp_n = 0;

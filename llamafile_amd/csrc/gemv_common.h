@@ -64,10 +64,8 @@ __device__ __forceinline__ void x80_copy_blocks(uint8_t *lds, int nquads, const 
 #ifndef GEMV_DIAG_WG
 #define GEMV_DIAG_WG 100 // the second stamped work-group (the first is 0)
 #endif
-static __device__ unsigned long long g_gemv_stamps[4 * 16 * 16];
-extern "C" __attribute__((weak)) int lfamd_debug_gemv_stamps(unsigned long long *dst) { // per TU; dev only
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemv_stamps), sizeof(g_gemv_stamps));
-}
+#define DIAG_STAMPS (4 * 16 * 16)
+#include "diag_stamps.h"
 // entry / exit time and placement (HW_ID, XCC_ID) of wave 0 of every work-group
 static __device__ unsigned long long g_gemv_wg[512 * 4];
 extern "C" __attribute__((weak)) int lfamd_debug_gemv_wgs(unsigned long long *dst) {
@@ -90,7 +88,7 @@ extern "C" __attribute__((weak)) int lfamd_debug_gemv_wgs(unsigned long long *ds
     do {                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         if ((blockIdx.x == 0 || blockIdx.x == GEMV_DIAG_WG) && lane == 0 && stamp_n < 16)                                  \
-            g_gemv_stamps[((blockIdx.x ? 1 : 0) * 16 + wave) * 16 + stamp_n++] = __builtin_amdgcn_s_memrealtime(); \
+            g_stamps[((blockIdx.x ? 1 : 0) * 16 + wave) * 16 + stamp_n++] = DIAG_REALTIME();                      \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
     } while (0)
 // (diagnostic only: drain the loads first, so the stamp is the arrival time of the item's weights)

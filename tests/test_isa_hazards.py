@@ -31,11 +31,11 @@ KS_TUS = [("gemm_ks.hip", nb) for nb in (1, 5, 8)] + [("gemm_kr.hip", nb) for nb
 @pytest.mark.skipif(not os.path.exists(isa_hazards.HIPCC), reason="needs hipcc")
 def test_k_split_and_row_split_bodies():
     """gemm_ks / gemm_kr / gemm_i8 / gemm_lf keep loads in flight across several periods of a rolled loop whose blocks hipcc lays out out of
-    execution order; the linear walk needs straight-line code, which a fixed trip count (-DKS_CHECK_NB) gives.  The
+    execution order; the linear walk needs straight-line code, which a fixed trip count (-DGEMM_CHECK_TRIPS) gives.  The
     VALU-written-SGPR rule is position-local and runs on the shipped (rolled) build as well."""
     def one(arg):
         f, nb = arg
-        return isa_hazards.check_file(os.path.join(ROOT, "llamafile_amd", "csrc", f), (f"-DKS_CHECK_NB={nb}", f"-DI8_CHECK_NB={nb}", f"-DLF_CHECK_NQ={nb}"))
+        return isa_hazards.check_file(os.path.join(ROOT, "llamafile_amd", "csrc", f), (f"-DGEMM_CHECK_TRIPS={nb}",))
     with ThreadPoolExecutor(max_workers=3) as ex:
         results = list(ex.map(one, KS_TUS))
     for (f, nb), res in zip(KS_TUS, results):

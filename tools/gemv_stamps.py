@@ -15,7 +15,7 @@ from llamafile_amd import sgemm, synth, _hip, ggml_types as T
 
 def read_stamps():
     buf = (C.c_ulonglong * 1024)()
-    print("rc", _hip.lib().lfamd_debug_gemv_stamps(buf))
+    print("rc", _hip.lib().lfamd_debug_stamps(buf, C.c_size_t(len(buf))))
     return np.array(buf[:512], dtype=np.int64).reshape(2, 16, 16)
 
 

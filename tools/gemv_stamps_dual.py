@@ -14,7 +14,7 @@ for Ws in sets:
     outs = sgemm.mul_mat_multi(Ws, B, T.F32, n=1)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 1024)()
-print("rc", _hip.lib().lfamd_debug_gemv_stamps(buf))
+print("rc", _hip.lib().lfamd_debug_stamps(buf, C.c_size_t(len(buf))))
 a = np.array(buf[:512], dtype=np.int64).reshape(2, 16, 16)
 t0 = a[a > 0].min()
 for g in (0, 1):

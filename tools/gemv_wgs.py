@@ -30,7 +30,7 @@ for xc in range(8):
 clk = a[:, 3] / np.maximum(1, (a[:, 1] - a[:, 0])) / 10.0  # cycles per ns = GHz
 print(f"shader clock during the launch: median {np.median(clk) * 1000:.0f} MHz")
 buf = (C.c_ulonglong * 1024)()
-print("rc", L.lfamd_debug_gemv_stamps(buf))
+print("rc", L.lfamd_debug_stamps(buf, C.c_size_t(len(buf))))
 s = np.array(buf[:512], dtype=np.int64).reshape(2, 16, 16)
 for g in (0, 1):
     for w in (0, 5, 10, 15):

@@ -15,7 +15,7 @@ for _ in range(2):
         out = sgemm.mul_mat(W, B, T.F32, n=n)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 512)()
-print("rc", _hip.lib().lfamd_debug_i8_stamps(buf))
+print("rc", _hip.lib().lfamd_debug_stamps(buf, C.c_size_t(len(buf))))
 a = np.array(buf[:], dtype=np.int64).reshape(2, 256)
 t = a[0][a[0] > 0]
 print(f"compute wave 0: n {len(t)} total cycles {t[-1] - t[0]}")

@@ -238,7 +238,7 @@ def decode_hygiene(text):
 
 
 def check_file(path, extra_flags=()):
-    """extra_flags: e.g. ("-DKS_CHECK_NB=8",) for kernels whose stage loop is laid out out of execution order (the walk is
+    """extra_flags: e.g. ("-DGEMM_CHECK_TRIPS=8",) for kernels whose stage loop is laid out out of execution order (the walk is
     linear): a fixed trip count turns the loop into straight-line code."""
     with tempfile.NamedTemporaryFile(suffix=".s") as f:
         subprocess.run([HIPCC, *FLAGS, *extra_flags, path, "-o", f.name], check=True, stderr=subprocess.DEVNULL)

@@ -15,7 +15,7 @@ for _ in range(2):
         out = sgemm.mul_mat(W, B, T.F32, n=n)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 16)()
-rc = _hip.lib().lfamd_debug_lf_stamps(buf)
+rc = _hip.lib().lfamd_debug_stamps(buf, C.c_size_t(len(buf)))
 a = [int(v) for v in buf]
 nq = max(1, a[2])
 print(f"{m} x {k} x {n}, LFAMD_LF_NT={os.environ.get('LFAMD_LF_NT', 'default')}: rc {rc}, {nq} stages (s_memtime ticks)")

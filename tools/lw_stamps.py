@@ -11,7 +11,7 @@ for _ in range(3):
     out = sgemm.mul_mat(W, B, T.F32, n=n)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 256)()
-print("rc", _hip.lib().lfamd_debug_lw_stamps(buf))
+print("rc", _hip.lib().lfamd_debug_stamps(buf, C.c_size_t(len(buf))))
 a = np.array(buf[:], dtype=np.int64).reshape(2, 128)
 print("memtime", a[0,126], "realtime", a[0,127], "clock MHz", a[0,126] / max(a[0,127],1) * 100)
 print("store cycles", a[0,125])

@@ -13,7 +13,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 512)()
 L = _hip.lib()
-print("rc", L.lfamd_debug_wide_stamps(buf))
+print("rc", L.lfamd_debug_stamps(buf, C.c_size_t(len(buf))))
 a = np.array(buf[:], dtype=np.int64).reshape(8, 64)
 for w in (0, 3, 4, 7):
     t = a[w]
