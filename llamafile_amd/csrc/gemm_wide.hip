@@ -85,47 +85,69 @@ static void split_mats(const gemm_mats &mats, int rb_cut, size_t row_tile_bytes,
         hi.A[i] = hi.A[0], hi.C[i] = hi.C[0], hi.m[i] = 0, hi.ldc[i] = 0, hi.rb_end[i] = hi_end;
 }
 
+// Which launch form a scaled-operand call that is not MUL_MAT_ID takes, from the grid alone (count matrices of n_rb row blocks of 128
+// together, nb super-blocks, n tokens staged as n_pad rows, P_bytes of K-split workspace or 0).  wide_go switches on the answer and
+// lfamd_gemm_wide_plan_of hands it to the tests: there is no second copy of this rule.
+static lfamd_wide_plan wide_scaled_plan(int Atype, int count, int n_rb, int nb, long n, long n_pad, size_t P_bytes) {
+    const int n_ct = (int)(n_pad / WD_COLS), tiles = n_rb * n_ct;
+    // 128 x 128 tiles when they fill the chip, else 128 x 64 (twice the work-groups, no K split)
+    if (tiles >= LW_FULL_GRID) {
+        if (Atype == LFAMD_TYPE_Q4_K) // 256 x 128 tiles on the row-split body (gemm_kr.hip)
+            return {LFAMD_WIDE_KR, 0, 1};
+        // full rounds of 128 x 128 tiles; a last round of at most 128 of them (half the CUs idle) runs as one round of
+        // 128 x 64 tiles instead (0.73 of the time): ffn_gate + ffn_up at 512 tokens = 896 tiles = 3 rounds + 128
+        const int rem = tiles % 256;
+        if (tiles > 256 && rem > 0 && rem <= 128 && rem % n_ct == 0)
+            return {LFAMD_WIDE_LW128_THEN_LW64, (tiles - rem) / n_ct, 1};
+        return {LFAMD_WIDE_LW128, 0, 1};
+    }
+    const int n_ct2 = (int)((n + 63) / 64);
+    const int ksp = (count == 1 && P_bytes && n_pad == 128) ? lw_ksplit(n_rb * n_ct2, nb) : 1;
+    if (ksp > 1 && P_bytes >= (size_t)ksp * 128 * (size_t)n_rb * 128 * sizeof(float))
+        return {LFAMD_WIDE_LW64_KSPLIT, 0, ksp};
+    // 128 x 64 tiles: Q4_K on the K-split-waves body (gemm_ks.hip)
+    return {Atype == LFAMD_TYPE_Q4_K ? LFAMD_WIDE_KS : LFAMD_WIDE_LW64, 0, 1};
+}
+
+static size_t row_tile_bytes_of(int Atype, int nb) { // one 32-row tile of a K-quant image
+    return (size_t)nb * (Atype == LFAMD_TYPE_Q5_K ? P5K_TILE : Atype == LFAMD_TYPE_Q6_K ? P6K_TILE : P4K_TILE);
+}
+
 static hipError_t wide_go(int Atype, int mode, float *P, size_t P_bytes, WIDE_ARGS) {
     const int g_scaled = (mode >> 1) & 1;
     const bool q45 = Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K;
     if ((q45 || (Atype == LFAMD_TYPE_Q6_K && g_scaled)) && lw_allowed(mode)) {
         if (g_scaled && !moe) {
-            // scaled operands: 128 x 128 tiles when they fill the chip, else 128 x 64 (twice the work-groups, no K split)
-            if (n_rb * n_ct >= LW_FULL_GRID && Atype == LFAMD_TYPE_Q4_K) // 256 x 128 tiles on the row-split body (gemm_kr.hip)
-                return lfamd_kr_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_ct, s);
-            if (n_rb * n_ct >= LW_FULL_GRID) {
-                // full rounds of 128 x 128 tiles; a last round of at most 128 of them (half the CUs idle) runs as one round of
-                // 128 x 64 tiles instead (0.73 of the time): ffn_gate + ffn_up at 512 tokens = 896 tiles = 3 rounds + 128
-                const int tiles = n_rb * n_ct, rem = tiles % 256;
-                if (tiles > 256 && rem > 0 && rem <= 128 && rem % n_ct == 0) {
-                    const int rb_cut = (tiles - rem) / n_ct;
-                    const size_t tile_bytes = (size_t)nb * (Atype == LFAMD_TYPE_Q5_K ? P5K_TILE : Atype == LFAMD_TYPE_Q6_K ? P6K_TILE : P4K_TILE);
-                    gemm_mats lo, hi;
-                    split_mats(mats, rb_cut, tile_bytes, lo, hi);
-                    hipError_t e = lfamd_lw_go(Atype, lo, nb, Xh, d8T, Xm, n, n_pad, rb_cut, n_ct, (unsigned)(rb_cut * n_ct), 0, 1, 4, 1,
-                                               nullptr, s);
-                    if (e != hipSuccess)
-                        return e;
-                    const int n_ct2 = (int)((n + 63) / 64), rb_hi = n_rb - rb_cut;
-                    if (Atype == LFAMD_TYPE_Q4_K) // (the K-split-waves body, gemm_ks.hip)
-                        return lfamd_ks_go(Atype, hi, nb, Xh, d8T, Xm, n, n_pad, rb_hi, n_ct2, s);
-                    return lfamd_lw_go(Atype, hi, nb, Xh, d8T, Xm, n, n_pad, rb_hi, n_ct2, (unsigned)(rb_hi * n_ct2), 0, 1, 2, 1, nullptr, s);
-                }
-                return lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, (unsigned)(n_rb * n_ct), 0, 1, 4, 1, nullptr, s);
-            }
+            const lfamd_wide_plan p = wide_scaled_plan(Atype, mats.count, n_rb, nb, n, n_pad, P ? P_bytes : 0);
             const int n_ct2 = (int)((n + 63) / 64);
-            const int ksp = (mats.count == 1 && P && n_pad == 128) ? lw_ksplit(n_rb * n_ct2, nb) : 1;
-            if (ksp > 1 && P_bytes >= (size_t)ksp * 128 * (size_t)n_rb * 128 * sizeof(float)) {
-                hipError_t e = lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, (unsigned)(n_rb * n_ct2 * ksp), 0, 1, 2,
-                                           ksp, P, s);
+            switch (p.form) {
+            case LFAMD_WIDE_KR:
+                return lfamd_kr_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_ct, s);
+            case LFAMD_WIDE_LW128:
+                return lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, (unsigned)(n_rb * n_ct), 0, 1, 4, 1, nullptr, s);
+            case LFAMD_WIDE_LW128_THEN_LW64: {
+                gemm_mats lo, hi;
+                split_mats(mats, p.rb_cut, row_tile_bytes_of(Atype, nb), lo, hi);
+                hipError_t e = lfamd_lw_go(Atype, lo, nb, Xh, d8T, Xm, n, n_pad, p.rb_cut, n_ct, (unsigned)(p.rb_cut * n_ct), 0, 1, 4, 1,
+                                           nullptr, s);
                 if (e != hipSuccess)
                     return e;
-                return lfamd_lw_ksplit_reduce(P, ksp, n, n_pad, (long)n_rb * 128, mats.m[0], mats.C[0], mats.ldc[0],
+                const int rb_hi = n_rb - p.rb_cut;
+                return lfamd_lw_go(Atype, hi, nb, Xh, d8T, Xm, n, n_pad, rb_hi, n_ct2, (unsigned)(rb_hi * n_ct2), 0, 1, 2, 1, nullptr, s);
+            }
+            case LFAMD_WIDE_LW64_KSPLIT: {
+                hipError_t e = lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, (unsigned)(n_rb * n_ct2 * p.ksp), 0, 1, 2,
+                                           p.ksp, P, s);
+                if (e != hipSuccess)
+                    return e;
+                return lfamd_lw_ksplit_reduce(P, p.ksp, n, n_pad, (long)n_rb * 128, mats.m[0], mats.C[0], mats.ldc[0],
                                               (const float *)d8T, s);
             }
-            if (Atype == LFAMD_TYPE_Q4_K) // 128 x 64 tiles on the K-split-waves body (gemm_ks.hip)
+            case LFAMD_WIDE_KS:
                 return lfamd_ks_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, s);
-            return lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, (unsigned)(n_rb * n_ct2), 0, 1, 2, 1, nullptr, s);
+            default: // LFAMD_WIDE_LW64
+                return lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct2, (unsigned)(n_rb * n_ct2), 0, 1, 2, 1, nullptr, s);
+            }
         }
         if (ks == 1 && (q45 || (moe && g_scaled))) // exact codes; the grouped MUL_MAT_ID launch also on scaled operands (Q6_K: only)
             return lfamd_lw_go(Atype, mats, nb, Xh, d8T, Xm, n, n_pad, n_rb, n_ct, n_wg, moe, moe ? g_scaled : 0, 4, 1, nullptr, s);
@@ -189,6 +211,44 @@ extern "C" int lfamd_gemm_wide_ksplit(long m, long k, long n_pad) {
 // Will a wide launch of these (fused) matrices run the loader-wave body, i.e. may the caller stage scaled activations?
 extern "C" int lfamd_gemm_wide_scaled_ok(int Atype, int plain) {
     return !plain && (Atype == LFAMD_TYPE_Q4_K || Atype == LFAMD_TYPE_Q5_K || Atype == LFAMD_TYPE_Q6_K);
+}
+
+// The form wide_go gives a scaled-operand call (not MUL_MAT_ID) of `count` matrices of m[] rows, nb super-blocks, n tokens staged
+// as n_pad rows, with P_bytes of K-split workspace (0: none), for the tests (tests/test_gemm_wide_plan.py); no device is touched.
+// parts, when given: 2 * GEMM_MAX_MATS entries of {matrix, first row, rows, weight byte offset}, what split_mats hands the two
+// launches of LFAMD_WIDE_LW128_THEN_LW64 (the 128 x 128 launch's matrices first; matrix = -1 ends a launch's list early); any
+// other form leaves every entry at -1.  Returns 0, or -1 for arguments no such call has.
+extern "C" int lfamd_gemm_wide_plan_of(int Atype, int count, const long *m, int nb, long n, long n_pad, size_t P_bytes,
+                                       lfamd_wide_plan *p, long *parts) {
+    if (!lfamd_gemm_wide_scaled_ok(Atype, 0) || count <= 0 || count > GEMM_MAX_MATS || !m || !p || nb <= 0 || n <= 0 || n_pad < n ||
+        n_pad % WD_COLS)
+        return -1;
+    // stand-in addresses 2^40 apart, so that a part's pointers say which matrix and which offset split_mats gave it
+    const uintptr_t step = (uintptr_t)1 << 40;
+    const void *A[GEMM_MAX_MATS];
+    float *C[GEMM_MAX_MATS];
+    for (int j = 0; j < count; j++)
+        A[j] = (const void *)((j + 1) * step), C[j] = (float *)((j + 1) * step);
+    gemm_mats mats;
+    const int n_rb = fill_gemm_mats(mats, count, A, m, C, m);
+    if (mats.count == 0)
+        return -1;
+    *p = wide_scaled_plan(Atype, mats.count, n_rb, nb, n, n_pad, P_bytes);
+    if (!parts)
+        return 0;
+    for (int i = 0; i < 2 * GEMM_MAX_MATS * 4; i++)
+        parts[i] = -1;
+    if (p->form != LFAMD_WIDE_LW128_THEN_LW64)
+        return 0;
+    gemm_mats half[2];
+    split_mats(mats, p->rb_cut, row_tile_bytes_of(Atype, nb), half[0], half[1]);
+    for (int h = 0; h < 2; h++)
+        for (int i = 0; i < half[h].count; i++) {
+            long *e = parts + (h * GEMM_MAX_MATS + i) * 4;
+            const uintptr_t c = (uintptr_t)half[h].C[i], a = (uintptr_t)half[h].A[i];
+            e[0] = (long)(c / step) - 1, e[1] = (long)((c % step) / sizeof(float)), e[2] = half[h].m[i], e[3] = (long)(a % step);
+        }
+    return 0;
 }
 
 extern "C" hipError_t lfamd_launch_gemm_wide_multi(int Atype, int count, const void *const *A, const long *m, long k,

@@ -103,6 +103,21 @@ struct lfamd_gemv_plan {
     int lds;                 // dynamic LDS bytes
 };
 
+// The launch form of a scaled-operand wide call that is not MUL_MAT_ID (gemm_wide.hip: wide_go switches on it).
+enum {
+    LFAMD_WIDE_KR,              // 256 x 128 tiles, the row-split body (gemm_kr.hip)
+    LFAMD_WIDE_LW128,           // 128 x 128 tiles, the loader-wave body (gemm_lw.hip)
+    LFAMD_WIDE_LW128_THEN_LW64, // the tail split: row blocks [0, rb_cut) as LW128, the rest as one round of 128 x 64 tiles
+    LFAMD_WIDE_LW64,            // 128 x 64 tiles, the loader-wave body
+    LFAMD_WIDE_KS,              // 128 x 64 tiles, the K-split-waves body (gemm_ks.hip)
+    LFAMD_WIDE_LW64_KSPLIT      // 128 x 64 tiles with K cut into ksp parts over work-groups, then the reduce
+};
+struct lfamd_wide_plan {
+    int form;
+    int rb_cut; // LW128_THEN_LW64: the first row block of the 128 x 64 launch, else 0
+    int ksp;    // LW64_KSPLIT: the parts of K (2, 4, 8), else 1
+};
+
 extern "C" {
 void lfamd_set_error(const char *); // (api.hip: sets lfamd_last_error)
 size_t lfamd_mul_mat_workspace_upto(int, long, long, long);
@@ -163,6 +178,8 @@ hipError_t lfamd_launch_gemm_kq(int, const void *, long, long, const void *, con
 // (the wide launchers take `mode`: bit 0 plain body, bit 1 activations staged scaled — gemm_wide.hip)
 int lfamd_gemm_wide_scaled_ok(int, int);
 int lfamd_gemm_wide_dual_ok(long, long, long);
+// (Atype, count, m[], nb, n, n_pad, K-split workspace bytes or 0, plan out, parts out or NULL): pure host arithmetic, no device
+int lfamd_gemm_wide_plan_of(int, int, const long *, int, long, long, size_t, struct lfamd_wide_plan *, long *);
 size_t lfamd_gemm_lw_ksplit_bytes(long, long);
 hipError_t lfamd_launch_gemm_wide(int, const void *, long, long, const void *, const void *, const void *, long, long, float *, long, int, void *,
                                   size_t, hipStream_t);

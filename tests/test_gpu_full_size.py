@@ -138,14 +138,15 @@ def test_prefill_gemm_full_size_properties(gpu, t, m, k):
 
 
 def test_gate_up_fused_launch_tail_split(gpu):
-    """ffn_gate + ffn_up at 512 tokens as ONE call: 896 tiles of 128 x 128 = three full rounds + 128, whose last round runs
-    as 128 x 64 tiles (the second matrix is split at a row-block boundary).  Against the two separate calls, which run
-    128 x 128 tiles only (448 tiles each: no such tail): the rows that keep their tile shape are bit-identical; the Q4_K
-    128 x 64 tail runs the K-split-waves body (gemm_ks.hip) since round 3, whose two wave groups sum their K halves
-    separately — the same products in another f32 order (<= 4e-6 of the output scale; it was bit-identical on the
-    loader-wave body, which the Q5_K / Q6_K tails still run)."""
+    """ffn_gate + ffn_up at 512 tokens as ONE call: 896 tiles of 128 x 128 = three full rounds + 128.  Q4_K grids of 129 tiles and
+    more run the row-split body (gemm_kr.hip, 256 x 128 tiles) whole, the fused launch (112 blocks of 256 rows) as well as the two
+    separate calls (56 each): no Q4_K launch has a 128 x 64 tail (the tail split is Q5_K's and Q6_K's, tests/test_gpu_wide_routes.py),
+    which the library is asked first.  A 256-row block computes the same products in the same order wherever it sits in the grid,
+    so EVERY row of the fused launch has the bits of the separate call."""
     from llamafile_amd import synth
+    import wide_routes as R
     t, m, k = T.Q4_K, 14336, 4096
+    assert R.call_form(t, [m, m], k, PREFILL) == (R.KR, 0, 1) and R.call_form(t, [m], k, PREFILL) == (R.KR, 0, 1)
     Ws = [gpu.upload_weights(t, synth.random_weights_torch(t, m, k, 31 + i), m, k) for i in range(2)]
     x = torch.from_numpy(synth.random_activations(PREFILL, k, 32)).cuda()
     xb = x.view(torch.uint8).view(PREFILL, k * 4)
@@ -155,17 +156,18 @@ def test_gate_up_fused_launch_tail_split(gpu):
         assert torch.isfinite(f).all()
         same = (_bits(f) == _bits(sep)).all(dim=0)  # per weight row
         assert float((f - sep).abs().max()) / float(sep.abs().max()) <= 4e-6
-        # the tail = 128 tiles of 128 x 128 = 32 row blocks of the SECOND matrix
-        assert int(same.sum()) >= m - (4096 if W is Ws[1] else 0), "rows outside the 128 x 64 tail changed"
+        assert int(same.sum()) == m, "rows of the fused launch differ from the separate call"
 
 
 @pytest.mark.parametrize("ta", [T.Q4_K, T.Q5_K], ids=lambda t: T.NAMES[t])
 def test_qkv_two_types_one_gemm_launch(gpu, ta):
     """attn_q / attn_k (Q4_K or Q5_K) and attn_v (Q6_K) at 512 tokens through lfamd_mul_mat_multi_types: 192 tiles of
-    128 x 128 in ONE launch whose work-groups run their own type's body.  Against the three separate calls (which run
-    128 x 64 tiles): bit-identical where both run the loader-wave body (Q5_K, Q6_K); the separate Q4_K calls run the
-    K-split-waves body (gemm_ks.hip, another f32 order of the same products: <= 4e-6 of the output scale) or, the 4096-row one, the
-    int8 body (gemm_i8.hip: exact integer dots, so the scaled-operand launch is <= 1e-3 away)."""
+    128 x 128 in ONE launch of the loader-wave body whose work-groups run their own type's code (gemm_lw.hip: lfamd_lw_dual_go).
+    Against the three separate calls.  Q5_K and Q6_K: bit-identical; the separate calls run the same body on 128 x 64 tiles
+    (`lw64`: 128 and 32 tiles of 128 x 128 are below the 129 that get the big tile), and the loader-wave body gives the same
+    bits on both tile shapes.  Q4_K: the separate 1024-row call runs the K-split-waves body
+    (gemm_ks.hip, another f32 order of the same products: <= 4e-6 of the output scale), the 4096-row one the int8 body
+    (gemm_i8.hip: exact integer dots, so the scaled-operand launch is <= 1e-3 away)."""
     from llamafile_amd import synth
     k = 4096
     specs = [(ta, 4096), (T.Q6_K, 1024), (ta, 1024)]
