@@ -12,6 +12,23 @@ __device__ static inline void load_piece(float (&v)[16], const float *x, int p) 
     }
 }
 
+// N values times `scale`, rounded to int8 codes and OR-ed into y, four codes to a dword, first code lowest.  K: Q8_K's rule, nearest
+// even and clamped at 127 (quantize_row_q8_K's nearest_int); otherwise Q8_0's, roundf of v * scale (quantize_row_q8_0).
+template <bool K, int N>
+__device__ static inline void pack_codes(uint32_t (&y)[N / 4], const float (&v)[N], float scale) {
+#pragma unroll
+    for (int e = 0; e < N; e++) {
+        int q;
+        if constexpr (K) {
+            q = (int)rintf(scale * v[e]);
+            q = q > 127 ? 127 : q;
+        } else {
+            q = (int)roundf(v[e] * scale);
+        }
+        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
+    }
+}
+
 // The Q8_0 decode kernels' LDS image of the activations (X80_QUAD per quad, gemv_launch.h), written by both of them
 // (gemv_q80_impl.h, gemv_q80r_impl.h) through the two functions below, so the quantiser exists once.
 //
@@ -26,11 +43,7 @@ __device__ __forceinline__ void x80_quantise_piece(uint8_t *lds, int nquads, con
     const float d = amax / 127.0f;
     const float id = d != 0.0f ? 1.0f / d : 0.0f;
     uint32_t y[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        int q = (int)roundf(v[e] * id);
-        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-    }
+    pack_codes<false>(y, v, id);
     const int l = p >> 1, hf = p & 1;
     uint8_t *dst = lds + (size_t)(c * nquads + (l >> 2)) * X80_QUAD + (l & 3) * 4;
 #pragma unroll

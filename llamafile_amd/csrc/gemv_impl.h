@@ -73,6 +73,7 @@ __device__ static inline void stage_q8k(uint8_t *lds, const uint8_t *B, size_t b
     }
 }
 
+// (pack_codes, the rounding and packing of the quantisers below: gemv_common.h)
 // f32 rows, quantised here exactly like quantize_row_q8_K (upstream ggml-quants.c; restated in
 // quantize.hip): first index of the largest |x| fixes the sign of iscale = -128/max, codes are
 // nearest_int (round-half-even) clamped at 127, d = 1/iscale.  One "piece" = 16 consecutive floats;
@@ -104,12 +105,7 @@ __device__ static inline void quantise_piece_q8k(uint8_t *dst, const float (&v)[
     float d = 0.0f;
     if (amax != 0.0f) {
         const float iscale = -128.0f / val;
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            int q = (int)rintf(iscale * v[e]);
-            q = q > 127 ? 127 : q;
-            y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-        }
+        pack_codes<true>(y, v, iscale);
         d = 1.0f / iscale;
     }
     // this lane's 16 codes = groups 2*l16 (h = 0) and 2*l16+1 (h = 1) of K-step dd = l16 & 3
@@ -160,11 +156,7 @@ __device__ static inline void quantise_piece_q80(uint8_t *dst, const float (&v)[
     const float d = amax / 127.0f;
     const float id = d != 0.0f ? 1.0f / d : 0.0f;
     uint32_t y[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const int q = (int)roundf(v[e] * id);
-        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-    }
+    pack_codes<false>(y, v, id);
     const int hs0 = put_group(dst, 2 * l16 + 0, y[0], y[1]);
     const int hs1 = put_group(dst, 2 * l16 + 1, y[2], y[3]);
     const int o0 = __shfl_xor(hs0, 1, 64), o1 = __shfl_xor(hs1, 1, 64);
@@ -275,6 +267,66 @@ __device__ static inline void stage_x(uint8_t *lds, const uint8_t *B, size_t b_r
 
 #define GEMV_CH_MAX 4
 
+// ---- What the traits' dots share (which sites use it, which kept their text and why).  The readers return small
+// structs by value: the arrays are indexed with constants after unrolling and stay in registers.
+// The reading side of a staged activation block (XBLK, XBLK_HB, XBLK_PS, XBLK_D: gemv_launch.h) for lane (gsel, h):
+// its 16 code dwords: K-step t8 = 4 gi + dd of the lane is w[2 t8] (low nibbles' codes) and w[2 t8 + 1] (high nibbles')
+struct kq_codes {
+    uint32_t w[16];
+};
+__device__ static inline kq_codes kq_codes_of(const uint8_t *xb, int gsel, int h) {
+    const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
+    const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
+    return {{ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w, yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w}};
+}
+// its four int16 pair sums: v[jj] = code sum of K-steps 2 jj, 2 jj + 1 (a 32-wide sub-block's half)
+struct kq_sums4 {
+    int v[4];
+};
+__device__ static inline kq_sums4 kq_pair_sums_of(const uint8_t *xb, int gsel, int h) {
+    const uint2 psw = *(const uint2 *)(xb + XBLK_PS + 16 * gsel + 8 * h);
+    return {{(int)(int16_t)(psw.x & 0xffff), (int)(int16_t)(psw.x >> 16), (int)(int16_t)(psw.y & 0xffff), (int)(int16_t)(psw.y >> 16)}};
+}
+// its eight int16 group sums as four dwords: w[p] = K-steps (2p, 2p + 1)
+struct kq_words4 {
+    uint32_t w[4];
+};
+__device__ static inline kq_words4 kq_group_sums_of(const uint8_t *xb, int gsel, int h) {
+    const uint4 hbw = *(const uint4 *)(xb + XBLK_HB + 32 * gsel + 16 * h);
+    return {{hbw.x, hbw.y, hbw.z, hbw.w}};
+}
+
+// the lane's eight code dwords of the nibble lattice, w[t8]: groups 2 gsel (q0) and 2 gsel + 1 (q1)
+struct kq_words8 {
+    uint32_t w[8];
+};
+__device__ static inline kq_words8 kq_words_of(const uint4 q0, const uint4 q1) {
+    return {{q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w}};
+}
+// K-step t8 of a nibble dword against the staged codes, added to isum; LUT: the nibbles are kvalues_iq4nl indices (lfamd_device.h)
+template <bool LUT = false>
+__device__ static inline int kq_nib_dot(uint32_t x, const kq_codes &y, int t8, int isum) {
+    if constexpr (LUT) {
+        isum = sdot4(kvalues_lut4(x & 0x0F0F0F0Fu), y.w[2 * t8], isum);
+        return sdot4(kvalues_lut4((x >> 4) & 0x0F0F0F0Fu), y.w[2 * t8 + 1], isum);
+    } else {
+        isum = sdot4(x & 0x0F0F0F0F, y.w[2 * t8], isum);
+        return sdot4((x >> 4) & 0x0F0F0F0F, y.w[2 * t8 + 1], isum);
+    }
+}
+// ... with a fifth bit per weight: Hd = the K-step's fifth-bit dword (P5K lattice) shifted down by dd = t8 & 3
+__device__ static inline int kq_nib5_dot(uint32_t x, uint32_t Hd, const kq_codes &y, int t8, int isum) {
+    const uint32_t c0 = (x & 0x0F0F0F0F) | (Hd & 0x10101010);
+    const uint32_t c1 = ((x >> 4) & 0x0F0F0F0F) | ((Hd >> 4) & 0x00100010) | ((Hd << 12) & 0x10001000);
+    isum = sdot4(c0, y.w[2 * t8], isum);
+    return sdot4(c1, y.w[2 * t8 + 1], isum);
+}
+// f16 number jj of a uint2 of four (a row's block scales 4 gsel .. 4 gsel + 3); by reference: by value, the Q4_1 kernels change
+__device__ static inline float kq_h4(const uint2 &hd, int jj) {
+    const uint32_t dw = jj < 2 ? hd.x : hd.y;
+    return h2f((uint16_t)((jj & 1) ? (dw >> 16) : (dw & 0xffff)));
+}
+
 struct q4k_traits {
     static constexpr int ACT = LFAMD_TYPE_Q8_K; // activation quantisation the reference uses for this type
     static constexpr int TILE = P4K_TILE;
@@ -295,14 +347,9 @@ struct q4k_traits {
         q4k_scales_bytes(hd.y, hd.z, hd.w, sc03, sc47, mn03, mn47);
         // this lane's four sub-blocks: j = 2g + e, g = 2*gsel + gi  ->  j = 4*gsel + 2*gi + e
         const uint32_t scw = gsel ? sc47 : sc03, mnw = gsel ? mn47 : mn03;
-        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
-        const uint2 psw = *(const uint2 *)(xb + XBLK_PS + 16 * gsel + 8 * h);
-        const int ps[4] = {(int)(int16_t)(psw.x & 0xffff), (int)(int16_t)(psw.x >> 16), (int)(int16_t)(psw.y & 0xffff),
-                           (int)(int16_t)(psw.y >> 16)};
+        const kq_words8 qw = kq_words_of(q0, q1);
+        const kq_codes y = kq_codes_of(xb, gsel, h);
+        const kq_sums4 ps = kq_pair_sums_of(xb, gsel, h);
         int sumi = 0, summ = 0;
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) { // jj = 2 gi + e
@@ -310,12 +357,10 @@ struct q4k_traits {
 #pragma unroll
             for (int d2 = 0; d2 < 2; d2++) {
                 const int t8 = 2 * jj + d2; // = 4 gi + dd
-                const uint32_t x = qw[t8];
-                isum = sdot4(x & 0x0F0F0F0F, yw[2 * t8], isum);
-                isum = sdot4((x >> 4) & 0x0F0F0F0F, yw[2 * t8 + 1], isum);
+                isum = kq_nib_dot(qw.w[t8], y, t8, isum);
             }
             sumi += (int)((scw >> (8 * jj)) & 0xff) * isum;
-            summ += (int)((mnw >> (8 * jj)) & 0xff) * ps[jj];
+            summ += (int)((mnw >> (8 * jj)) & 0xff) * ps.v[jj];
         }
         const float d8 = *(const float *)(xb + XBLK_D);
         // d*d8*sumi - dmin*d8*summ  (iqk_mul_mat.inc:284-291, 632)
@@ -323,32 +368,38 @@ struct q4k_traits {
     }
 };
 
-// Q4_0 (legacy 32-blocks, activations Q8_0; mul_mat_qX_0_q8_0_T, iqk_mul_mat.inc:998-1349): the P4K nibble image with
-// eight f16 block scales per row as header; w = d*(q - 8).  Per 32-block: d*d8*(<q, q8> - 8*sum(q8)), the sum taken
-// from the staged pair sums like the Q4_K mins.
-struct q40_traits {
+// Q4_0 and IQ4_NL (legacy 32-blocks {f16 d, 16 nibble bytes}, activations Q8_0) on ONE resident image (P40): the P4K nibble
+// image with eight f16 block scales per row as header.
+//   Q4_0 (mul_mat_qX_0_q8_0_T, iqk_mul_mat.inc:998-1349): w = d*(q - 8).  Per 32-block: d*d8*(<q, q8> - 8*sum(q8)), the sum
+//        taken from the staged pair sums like the Q4_K mins.
+//   IQ4_NL (CODEBOOK): the nibbles are codebook indices (the lookup kvalues_lut4: lfamd_device.h).  Per 32-block:
+//        (d * d8) * <kvalue[q], q8>; no offset, so the staged pair sums are not read.
+struct p40_chunk {
+    uint4 q0[GEMV_CH_MAX], q1[GEMV_CH_MAX];
+    uint2 hd[GEMV_CH_MAX];
+};
+template <bool CODEBOOK>
+struct p40_traits {
     static constexpr int ACT = LFAMD_TYPE_Q8_0;
     static constexpr int TILE = P4K_TILE;
-    struct chunk {
-        uint4 q0[GEMV_CH_MAX], q1[GEMV_CH_MAX];
-        uint2 hd[GEMV_CH_MAX];
-    };
+    using chunk = p40_chunk;
     __device__ static inline void load(chunk &ch, int s, lfamd_rsrc r, uint32_t off, int gsel, int slot, int hrow) {
-        ch.q0[s] = buf_ld16_nt(r, off + (2 * gsel + 0) * 1024 + slot * 16);
-        ch.q1[s] = buf_ld16_nt(r, off + (2 * gsel + 1) * 1024 + slot * 16);
-        ch.hd[s] = buf_ld8(r, off + P4K_HDR + hrow * 16 + gsel * 8); // scales of blocks 4 gsel .. 4 gsel + 3
+        if constexpr (CODEBOOK) { // (one inlining level more, as IQ4_NL always had: without it its address arithmetic comes out differently)
+            p40_traits<false>::load(ch, s, r, off, gsel, slot, hrow);
+        } else {
+            ch.q0[s] = buf_ld16_nt(r, off + (2 * gsel + 0) * 1024 + slot * 16);
+            ch.q1[s] = buf_ld16_nt(r, off + (2 * gsel + 1) * 1024 + slot * 16);
+            ch.hd[s] = buf_ld8(r, off + P4K_HDR + hrow * 16 + gsel * 8); // scales of blocks 4 gsel .. 4 gsel + 3
+        }
     }
     __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
         const uint4 q0 = ch.q0[s], q1 = ch.q1[s];
         const uint2 hd = ch.hd[s];
-        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
-        const uint2 psw = *(const uint2 *)(xb + XBLK_PS + 16 * gsel + 8 * h);
-        const int ps[4] = {(int)(int16_t)(psw.x & 0xffff), (int)(int16_t)(psw.x >> 16), (int)(int16_t)(psw.y & 0xffff),
-                           (int)(int16_t)(psw.y >> 16)};
+        const kq_words8 qw = kq_words_of(q0, q1);
+        const kq_codes y = kq_codes_of(xb, gsel, h);
+        kq_sums4 ps = {};
+        if constexpr (!CODEBOOK)
+            ps = kq_pair_sums_of(xb, gsel, h);
         const float4 d8 = *(const float4 *)(xb + XBLK_D + 16 * gsel);
         const float d8v[4] = {d8.x, d8.y, d8.z, d8.w};
         float acc = 0.0f;
@@ -358,56 +409,16 @@ struct q40_traits {
 #pragma unroll
             for (int d2 = 0; d2 < 2; d2++) {
                 const int t8 = 2 * jj + d2;
-                const uint32_t x = qw[t8];
-                isum = sdot4(x & 0x0F0F0F0F, yw[2 * t8], isum);
-                isum = sdot4((x >> 4) & 0x0F0F0F0F, yw[2 * t8 + 1], isum);
+                isum = kq_nib_dot<CODEBOOK>(qw.w[t8], y, t8, isum);
             }
-            const uint32_t dw = jj < 2 ? hd.x : hd.y;
-            const float d = h2f((uint16_t)((jj & 1) ? (dw >> 16) : (dw & 0xffff)));
-            acc = fmaf(d * d8v[jj], (float)(isum - 8 * ps[jj]), acc);
+            acc = fmaf(kq_h4(hd, jj) * d8v[jj], (float)(isum - (CODEBOOK ? 0 : 8) * ps.v[jj]), acc);
         }
         return acc;
     }
 };
-
-// (the codebook lookup kvalues_lut4: lfamd_device.h)
-// IQ4_NL (32-blocks {f16 d, 16 index bytes}, activations Q8_0): Q4_0's resident image byte for byte (P40), the nibbles being
-// codebook indices.  Per 32-block: (d * d8) * <kvalue[q], q8>; no offset, so the staged pair sums are not read.
-struct iq4nl_traits {
-    static constexpr int ACT = LFAMD_TYPE_Q8_0;
-    static constexpr int TILE = P4K_TILE;
-    using chunk = q40_traits::chunk;
-    __device__ static inline void load(chunk &ch, int s, lfamd_rsrc r, uint32_t off, int gsel, int slot, int hrow) {
-        q40_traits::load(ch, s, r, off, gsel, slot, hrow);
-    }
-    __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
-        const uint4 q0 = ch.q0[s], q1 = ch.q1[s];
-        const uint2 hd = ch.hd[s];
-        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
-        const float4 d8 = *(const float4 *)(xb + XBLK_D + 16 * gsel);
-        const float d8v[4] = {d8.x, d8.y, d8.z, d8.w};
-        float acc = 0.0f;
-#pragma unroll
-        for (int jj = 0; jj < 4; jj++) { // block 4 gsel + jj
-            int isum = 0;
-#pragma unroll
-            for (int d2 = 0; d2 < 2; d2++) {
-                const int t8 = 2 * jj + d2;
-                const uint32_t x = qw[t8];
-                isum = sdot4(kvalues_lut4(x & 0x0F0F0F0Fu), yw[2 * t8], isum);
-                isum = sdot4(kvalues_lut4((x >> 4) & 0x0F0F0F0Fu), yw[2 * t8 + 1], isum);
-            }
-            const uint32_t dw = jj < 2 ? hd.x : hd.y;
-            const float d = h2f((uint16_t)((jj & 1) ? (dw >> 16) : (dw & 0xffff)));
-            acc = fmaf(d * d8v[jj], (float)isum, acc);
-        }
-        return acc;
-    }
-};
+// (derived, not aliases: the kernels' symbols keep the names q40_traits / iq4nl_traits)
+struct q40_traits : p40_traits<false> {};
+struct iq4nl_traits : p40_traits<true> {};
 
 // Q5_K: Q4_K with a fifth bit per weight (DequantizerQ5K, iqk_mul_mat.inc:496-511): codes 0..31, same scales / mins.
 struct q5k_traits {
@@ -430,14 +441,9 @@ struct q5k_traits {
         uint32_t sc03, sc47, mn03, mn47;
         q4k_scales_bytes(hd.y, hd.z, hd.w, sc03, sc47, mn03, mn47);
         const uint32_t scw = gsel ? sc47 : sc03, mnw = gsel ? mn47 : mn03;
-        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
-        const uint2 psw = *(const uint2 *)(xb + XBLK_PS + 16 * gsel + 8 * h);
-        const int ps[4] = {(int)(int16_t)(psw.x & 0xffff), (int)(int16_t)(psw.x >> 16), (int)(int16_t)(psw.y & 0xffff),
-                           (int)(int16_t)(psw.y >> 16)};
+        const kq_words8 qw = kq_words_of(q0, q1);
+        const kq_codes y = kq_codes_of(xb, gsel, h);
+        const kq_sums4 ps = kq_pair_sums_of(xb, gsel, h);
         int sumi = 0, summ = 0;
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) { // jj = 2 gi + e
@@ -445,15 +451,10 @@ struct q5k_traits {
 #pragma unroll
             for (int d2 = 0; d2 < 2; d2++) {
                 const int t8 = 2 * jj + d2; // = 4 gi + dd
-                const uint32_t x = qw[t8];
-                const uint32_t Hd = hw[t8 >> 2] >> (t8 & 3);
-                const uint32_t c0 = (x & 0x0F0F0F0F) | (Hd & 0x10101010);
-                const uint32_t c1 = ((x >> 4) & 0x0F0F0F0F) | ((Hd >> 4) & 0x00100010) | ((Hd << 12) & 0x10001000);
-                isum = sdot4(c0, yw[2 * t8], isum);
-                isum = sdot4(c1, yw[2 * t8 + 1], isum);
+                isum = kq_nib5_dot(qw.w[t8], hw[t8 >> 2] >> (t8 & 3), y, t8, isum);
             }
             sumi += (int)((scw >> (8 * jj)) & 0xff) * isum;
-            summ += (int)((mnw >> (8 * jj)) & 0xff) * ps[jj];
+            summ += (int)((mnw >> (8 * jj)) & 0xff) * ps.v[jj];
         }
         const float d8 = *(const float *)(xb + XBLK_D);
         return fmaf(d * d8, (float)sumi, -(dmin * d8) * (float)summ);
@@ -489,14 +490,10 @@ struct q6k_traits {
         const uint4 l0 = ch.l0[s], l1 = ch.l1[s], hq = ch.hq[s];
         const uint2 scb = ch.sc[s];
         const float d = h2f((uint16_t)ch.d[s]);
-        const uint32_t lw[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
+        const kq_words8 lw = kq_words_of(l0, l1);
         const uint32_t hw[4] = {hq.x, hq.y, hq.z, hq.w}; // [gi*2 + e]
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
-        const uint4 hbw = *(const uint4 *)(xb + XBLK_HB + 32 * gsel + 16 * h);
-        const uint32_t hbv[4] = {hbw.x, hbw.y, hbw.z, hbw.w}; // int16 group sums of K-steps (2p, 2p + 1)
+        const kq_codes y = kq_codes_of(xb, gsel, h);
+        const kq_words4 hbv = kq_group_sums_of(xb, gsel, h); // int16 group sums of K-steps (2p, 2p + 1)
         // int16 pairs (sc_2p, sc_2p+1): bytes (s, sign s, s', sign s') — v_perm selectors 8-11 copy the sign of bytes 1, 3,
         // 5, 7 of {a, b}, so b = scales << 8 puts s0 / s2 there and a = scales s1 / s3
         const uint32_t scw[2] = {scb.x, scb.y};
@@ -505,8 +502,8 @@ struct q6k_traits {
         for (int u = 0; u < 2; u++) {
             const uint32_t sh = scw[u] << 8;
             const uint32_t p01 = __builtin_amdgcn_perm(scw[u], sh, 0x0A050801), p23 = __builtin_amdgcn_perm(scw[u], sh, 0x0B070903);
-            sums = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, p01), __builtin_bit_cast(short2_t, hbv[2 * u]), sums, false);
-            sums = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, p23), __builtin_bit_cast(short2_t, hbv[2 * u + 1]), sums, false);
+            sums = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, p01), __builtin_bit_cast(short2_t, hbv.w[2 * u]), sums, false);
+            sums = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2_t, p23), __builtin_bit_cast(short2_t, hbv.w[2 * u + 1]), sums, false);
         }
         int sumi = 0;
 #pragma unroll
@@ -516,11 +513,11 @@ struct q6k_traits {
 #pragma unroll
             for (int e = 0; e < 2; e++) {
                 const int t8 = 2 * p + e;
-                const uint32_t x = lw[t8];
+                const uint32_t x = lw.w[t8];
                 const uint32_t clo = (x & 0x0F0F0F0F) | ((e ? H >> 2 : H) & 0x30303030);
                 const uint32_t chi = ((x >> 4) & 0x0F0F0F0F) | ((e ? P << 2 : P << 4) & 0x30303030);
-                int isum = sdot4(clo, yw[2 * t8], 0);
-                isum = sdot4(chi, yw[2 * t8 + 1], isum);
+                int isum = sdot4(clo, y.w[2 * t8], 0);
+                isum = sdot4(chi, y.w[2 * t8 + 1], isum);
                 const int sc = (int)(int8_t)((scw[t8 >> 2] >> (8 * (t8 & 3))) & 0xff);
                 sumi += sc * ((int)((uint32_t)isum << 8) >> 8); // (an i24 operand: v_mul_i32_i24, the shifts fold away)
             }
@@ -557,19 +554,13 @@ struct pcl_traits {
     __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
         const uint4 q0 = ch.q0[s], q1 = ch.q1[s];
         const uint2 hd = ch.hd[s];
-        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
+        const kq_words8 qw = kq_words_of(q0, q1);
+        const kq_codes y = kq_codes_of(xb, gsel, h);
         const uint4 dsw = *(const uint4 *)(xb + XBLK_D + 16 * gsel); // Q8_0: four f32 d8; Q8_1: four {f16 d8, f16 s}
         const uint32_t dsv[4] = {dsw.x, dsw.y, dsw.z, dsw.w};
-        int ps[4] = {0, 0, 0, 0};
-        if constexpr (!HAS_M) {
-            const uint2 psw = *(const uint2 *)(xb + XBLK_PS + 16 * gsel + 8 * h);
-            ps[0] = (int)(int16_t)(psw.x & 0xffff), ps[1] = (int)(int16_t)(psw.x >> 16);
-            ps[2] = (int)(int16_t)(psw.y & 0xffff), ps[3] = (int)(int16_t)(psw.y >> 16);
-        }
+        kq_sums4 ps = {};
+        if constexpr (!HAS_M)
+            ps = kq_pair_sums_of(xb, gsel, h);
         float acc = 0.0f;
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) { // block 4 gsel + jj
@@ -577,26 +568,26 @@ struct pcl_traits {
 #pragma unroll
             for (int d2 = 0; d2 < 2; d2++) {
                 const int t8 = 2 * jj + d2;
-                const uint32_t x = qw[t8];
+                // (written out: both codes before the fifth bits and the dots.  Through kq_nib_dot / kq_nib5_dot the same
+                // operations reach the scheduler in another order and the Q4_1 / Q5_0 / Q5_1 kernels come out renamed)
+                const uint32_t x = qw.w[t8];
                 uint32_t c0 = x & 0x0F0F0F0F, c1 = (x >> 4) & 0x0F0F0F0F;
                 if constexpr (HAS_H) {
                     const uint32_t Hd = (t8 < 4 ? ch.hq[s].x : ch.hq[s].y) >> (t8 & 3);
                     c0 |= Hd & 0x10101010;
                     c1 |= ((Hd >> 4) & 0x00100010) | ((Hd << 12) & 0x10001000);
                 }
-                isum = sdot4(c0, yw[2 * t8], isum);
-                isum = sdot4(c1, yw[2 * t8 + 1], isum);
+                isum = sdot4(c0, y.w[2 * t8], isum);
+                isum = sdot4(c1, y.w[2 * t8 + 1], isum);
             }
-            const uint32_t dw = jj < 2 ? hd.x : hd.y;
-            const float d = h2f((uint16_t)((jj & 1) ? (dw >> 16) : (dw & 0xffff)));
+            const float d = kq_h4(hd, jj);
             if constexpr (HAS_M) {
-                const uint32_t mw = jj < 2 ? ch.hm[s].x : ch.hm[s].y;
-                const float m = h2f((uint16_t)((jj & 1) ? (mw >> 16) : (mw & 0xffff)));
+                const float m = kq_h4(ch.hm[s], jj);
                 const float d8 = h2f((uint16_t)(dsv[jj] & 0xffff)), s8 = h2f((uint16_t)(dsv[jj] >> 16));
                 acc = fmaf(d * d8, (float)isum, acc);
                 acc = fmaf(m, h ? 0.0f : s8, acc);
             } else {
-                acc = fmaf(d * __builtin_bit_cast(float, dsv[jj]), (float)(isum - 16 * ps[jj]), acc);
+                acc = fmaf(d * __builtin_bit_cast(float, dsv[jj]), (float)(isum - 16 * ps.v[jj]), acc);
             }
         }
         return acc;
@@ -632,12 +623,8 @@ struct pk_traits {
         const uint32_t dw = ch.dd[s];
         const float d = h2f((uint16_t)(dw & 0xffff));
         const uint32_t cw[4] = {qc.x, qc.y, qc.z, qc.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
-        const uint4 hbw = *(const uint4 *)(xb + XBLK_HB + 32 * gsel + 16 * h);
-        const uint32_t hbv[4] = {hbw.x, hbw.y, hbw.z, hbw.w};
+        const kq_codes y = kq_codes_of(xb, gsel, h);
+        const kq_words4 hbv = kq_group_sums_of(xb, gsel, h);
         int sumi = 0, summ = 0;
 #pragma unroll
         for (int t8 = 0; t8 < 8; t8++) { // t8 = 4 gi + dd
@@ -646,9 +633,8 @@ struct pk_traits {
                 const uint32_t H = (t8 < 4 ? ch.hb[s].x : ch.hb[s].y) >> (t8 & 3);
                 x |= (H & 0x11111111u) << 2;
             }
-            int isum = sdot4(x & 0x0F0F0F0F, yw[2 * t8], 0);
-            isum = sdot4((x >> 4) & 0x0F0F0F0F, yw[2 * t8 + 1], isum);
-            const int hs = (int)(int16_t)((hbv[t8 >> 1] >> (16 * (t8 & 1))) & 0xffff);
+            const int isum = kq_nib_dot(x, y, t8, 0);
+            const int hs = (int)(int16_t)((hbv.w[t8 >> 1] >> (16 * (t8 & 1))) & 0xffff);
             const uint32_t sbyte = ((t8 < 4 ? scb.x : scb.y) >> (8 * (t8 & 3))) & 0xff;
             if constexpr (Q3) {
                 sumi += (int)(int8_t)sbyte * (isum - OFF * hs);
@@ -680,11 +666,8 @@ struct iq4c_traits {
     }
     __device__ static inline float dot(const chunk &ch, int s, const uint8_t *xb, int gsel, int h) {
         const uint4 q0 = ch.q0[s], q1 = ch.q1[s], hd = ch.hd[s];
-        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-        const uint4 *yq = (const uint4 *)(xb + 128 * gsel + 64 * h);
-        const uint4 ya = yq[0], yb = yq[1], yc = yq[2], yd = yq[3];
-        const uint32_t yw[16] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w,
-                                 yc.x, yc.y, yc.z, yc.w, yd.x, yd.y, yd.z, yd.w};
+        const kq_words8 qw = kq_words_of(q0, q1);
+        const kq_codes y = kq_codes_of(xb, gsel, h);
         const uint32_t scw = gsel ? hd.y : hd.x; // scales of sub-blocks 4 gsel .. 4 gsel + 3
         int sumi = 0;
 #pragma unroll
@@ -692,9 +675,7 @@ struct iq4c_traits {
             int isum = 0;
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                const uint32_t x = qw[2 * u + e];
-                isum = sdot4(kvalues_lut4(x & 0x0F0F0F0Fu), yw[2 * (2 * u + e)], isum);
-                isum = sdot4(kvalues_lut4((x >> 4) & 0x0F0F0F0Fu), yw[2 * (2 * u + e) + 1], isum);
+                isum = kq_nib_dot<true>(qw.w[2 * u + e], y, 2 * u + e, isum);
             }
             sumi += (int)(int8_t)((scw >> (8 * u)) & 0xff) * isum;
         }
@@ -823,12 +804,7 @@ __device__ static inline void stage_f32_q8k_wave2(uint8_t *dst, const float4 va,
     const float val = nz ? (hi ? val_hi : val_lo) : 1.0f;
     const float iscale = -128.0f / val;
     uint32_t y[2] = {0, 0};
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-        int q = (int)rintf(iscale * v[e]);
-        q = q > 127 ? 127 : q;
-        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-    }
+    pack_codes<true>(y, v, iscale);
     const uint32_t y0 = nz ? y[0] : 0u, y1 = nz ? y[1] : 0u;
     const float d = nz ? 1.0f / iscale : 0.0f;
     const int grp = lane & 31;
@@ -849,11 +825,7 @@ __device__ static inline void stage_f32_q80_wave2(uint8_t *dst, const float4 va,
     const float d = am / 127.0f;
     const float id = d != 0.0f ? 1.0f / d : 0.0f;
     uint32_t y[2] = {0, 0};
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-        const int q = (int)roundf(v[e] * id);
-        y[e >> 2] |= (uint32_t)(q & 0xff) << (8 * (e & 3));
-    }
+    pack_codes<false>(y, v, id);
     const int grp = lane & 31;
     const int pair = put_group_pair(dst, grp, y[0], y[1]); // groups grp, grp ^ 2; with the neighbour pair: the four groups of the 32-block
     const int sum = pair + (int)dpp_u32<DPP_XOR1>((uint32_t)pair); // (all lanes active: a DPP source lane must be)
